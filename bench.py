@@ -15,14 +15,19 @@ Multi-GPU: voices are sharded over ranks (weak scaling: --voices per GPU; strong
 ranks), each rank renders its partial master bus on its GPU, and the partial buses meet in one RCCL sum-reduce to rank 0 per
 super-block (the reference's caller-side sum of worker outputs, src/source/mixed.rs:522-536).
 
-The timed region is a series of legs of exactly `--steps` blocks, each bracketed by barrier + torch.cuda.synchronize() on both sides and
-reduced with MAX over ranks, repeated until `--min-seconds` (0.5 s) of wall time are covered (`--repeats` fixes the count);
-`ms_per_step` / `value` come from the MEDIAN leg and the spread is printed under `repeats`. At one GPU a second set of legs pulls the
-same graph with ONE write call per block — the reference's real-time call pattern — and lands in `config.realtime`.
+A plain run sets up, renders `--warmup` blocks, times ONE leg of exactly `--steps` blocks (bracketed by barrier +
+torch.cuda.synchronize() on both sides, MAX over ranks) and prints the line: `ms_per_step` / `value` come from that leg, and `roofline`
+(dominant kernel launch(es) of the graph, named in `roofline.kernel`, hipEvent-timed on the launching stream) from the same leg.
+`--dump-outputs DIR` then also writes the master bus of the last timed step (what a caller of pg_graph_write_device receives) as
+DIR/master_bus.npy (float32, block_frames x 2); the inputs are seeded, so the same arguments render the same audio from run to run.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel launch(es) of the graph, named in `roofline.kernel`, hipEvent-timed
-on the launching stream) and `cpu_baseline` (the CPU oracle — a C++ port of the reference path, NOT the Rust binary — on this
-box's host cores, bounded sample of about 12 s).
+`--full` adds everything else the benchmark measures: the legs are repeated until `--min-seconds` (0.5 s) of wall time are covered
+(`--repeats` fixes the count), `ms_per_step` / `value` come from the MEDIAN leg and the spread is printed under `repeats`; at one GPU
+a second set of legs pulls the same graph with ONE write call per block — the reference's real-time call pattern — and lands in
+`config.realtime`; `config.strong_c5` (BASELINE config 5 at 8192 voices), `config.clocks` (the card's clocks while the legs ran) and
+`cpu_baseline` (the CPU oracle — a C++ port of the reference path, NOT the Rust binary — on this box's host cores, bounded sample of
+about 12 s). With `--full` the dump is taken after the last headline leg, whose position in the stream follows the number of legs:
+give `--repeats` too for outputs that compare from run to run.
 """
 import argparse
 import json
@@ -472,8 +477,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=0, help="timed legs of exactly --steps blocks each, the median leg is reported (default: as many as --min-seconds needs, "
-                    "at least 5 — a 20-step leg lasts 2 ms and single legs scatter by +-8 % with the clock state of the box)")
+    ap.add_argument("--full", action="store_true", help="measure everything, not just the headline figure: repeated legs (--repeats / --min-seconds), the real-time "
+                    "legs, config.strong_c5, config.clocks and cpu_baseline (a plain run times one leg of exactly --steps blocks and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the master bus of the last timed step as DIR/master_bus.npy "
+                    "(float32, block_frames x 2: what the write call handed back)")
+    ap.add_argument("--repeats", type=int, default=0, help="--full: timed legs of exactly --steps blocks each, the median leg is reported (default: as many as --min-seconds needs, "
+                    "at least 5 — a 20-step leg lasts 2 ms and single legs scatter by +-8 %% with the clock state of the box)")
     ap.add_argument("--workload", default="headline", choices=sorted(B_ALG) + ["dyn"])
     ap.add_argument("--churn", type=float, default=0.0, help="--workload dyn: %% of the voices that end and restart per second of audio, at random sample times")
     ap.add_argument("--events", type=float, default=0.0, help="--workload dyn: parameter / volume / panning commands per second of audio, at random sample times")
@@ -488,16 +497,20 @@ def main():
     ap.add_argument("--max-frames", type=int, default=0, help="the graph's max_frames: the kernels' piece size (default: min(--block, 1024) — a write is walked in the "
                     "reference's <= 4096-frame chunks whatever this is; the staged kernels take pieces of <= 1024 frames)")
     ap.add_argument("--superblock", type=int, default=32, help="blocks rendered per pg_graph_write_device call (offline pull loop; 1 = one call per block, the real-time setting)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-clocks", action="store_true", help="do not poll the card's sysfs clock / power / temperature files during the legs (config.clocks)")
-    ap.add_argument("--no-realtime", action="store_true", help="skip the second set of legs (one write call per block) behind config.realtime")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="timed legs are repeated until this much wall time is covered (unless --repeats is given)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-clocks", action="store_true", help="--full: do not poll the card's sysfs clock / power / temperature files during the legs (config.clocks)")
+    ap.add_argument("--no-realtime", action="store_true", help="--full: skip the second set of legs (one write call per block) behind config.realtime")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="--full: timed legs are repeated until this much wall time is covered (unless --repeats is given)")
     ap.add_argument("--exact", action="store_true", help="disable the time-parallel paths (exact serial evaluation)")
     ap.add_argument("--time-every", type=int, default=1, help="hipEvent-time the dominant kernel every n-th launch round (the event pair costs ~8 us of stream time: once per super-block by default)")
     ap.add_argument("--reduce-every", type=int, default=0, help="multi-GPU: blocks per RCCL master-bus reduce (default: the super-block; 1 = per block, the real-time setting)")
-    ap.add_argument("--strong-c5-voices", type=int, default=8192, help="voices of the BASELINE config 5 leg reported under config.strong_c5 (split over the GPUs; 0 = skip it)")
+    ap.add_argument("--strong-c5-voices", type=int, default=8192, help="--full: voices of the BASELINE config 5 leg reported under config.strong_c5 (split over the GPUs; 0 = skip it)")
     ap.add_argument("--staged", type=int, default=1, help="reverb sub-mixers: 1 = staged kernel (default), 2 = one launch per stage, 0 = fused fast kernel")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "dyn":
+        ap.error("--dump-outputs: not for --workload dyn")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -559,7 +572,7 @@ def main():
     sb = max(1, min(sb, 64 // pieces_per_block))
     dist_on = world > 1 or force_dist  # (a forced one-rank group goes through the same barriers and reductions)
 
-    def measure(name, scaling, voices_arg, total_voices_arg, min_seconds, with_realtime, sampler=None):
+    def measure(name, scaling, voices_arg, total_voices_arg, min_seconds, with_realtime, sampler=None, want_dump=False):
         """Builds the workload's graph on this rank, renders warm-up and timed legs; returns what the result line is made of."""
         if scaling == "strong":
             total_voices = total_voices_arg or (8192 if name == "c5" else DEFAULT_VOICES[name])
@@ -654,6 +667,13 @@ def main():
             """Timed legs of exactly --steps blocks until `seconds` of wall time are covered (at least 5, at most 2001; --repeats overrides):
             a 20-step leg lasts 2 ms, single legs scatter with the clock state of the box. Returns (legs, per-leg seconds, MAX over ranks)."""
             first = leg(args.steps, per_call)
+            if not args.full:   # a plain run: exactly --steps timed blocks, one leg
+                dts = [first[0]]
+                if dist_on:
+                    t = torch.tensor(dts, dtype=torch.float64, device=f"cuda:{local_rank}")
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    dts = [float(t.item())]
+                return [first], dts
             d0 = first[0]
             if dist_on:
                 t = torch.tensor([d0], dtype=torch.float64, device=f"cuda:{local_rank}")
@@ -689,6 +709,12 @@ def main():
         del calls[:]
         legs, dts = legs_for(min_seconds)
         offline_calls = sorted(calls)
+        dump = None
+        if want_dump and rank == 0:   # the last timed step's master bus (on the root: the sum over ranks), before any further leg renders
+            last = ring.last_block()
+            if last is None:
+                raise RuntimeError("--dump-outputs: no step was timed")
+            dump = last.detach().to("cpu", torch.float32).numpy().reshape(block, 2).copy()
         # the real-time call pattern — ONE write call per block, as the reference's WavOutput and cpal callbacks pull (src/output/wav.rs:210-250,
         # src/output/cpal.rs:700-723) — timed in the same run on the same graph: no super-block launches, every block its own launch sequence
         rt_legs, rt_dts = (legs_for(min_seconds / 2, 1) if (sb > 1 and world == 1 and with_realtime) else (None, None))
@@ -714,7 +740,7 @@ def main():
         dev_err = g.device_errors()
         if dev_err:
             raise RuntimeError(f"kernel consistency flags raised: {dev_err}")
-        res = dict(name=name, scaling=scaling, v_per_gpu=v_per_gpu, total_voices=total_voices, M=M, dts=dts, legs=legs, rt_dts=rt_dts, rt_legs=rt_legs, rt_sync=rt_sync, peak=peak,
+        res = dict(name=name, scaling=scaling, v_per_gpu=v_per_gpu, total_voices=total_voices, M=M, dts=dts, legs=legs, rt_dts=rt_dts, rt_legs=rt_legs, rt_sync=rt_sync, peak=peak, dump=dump,
                    offline_calls=offline_calls, kernel=g.dominant_kernel(), bus_kernel=g.bus_kernel(), roofline_of=roofline_of)
         torch.cuda.set_stream(torch.cuda.default_stream(local_rank))
         del ring
@@ -723,13 +749,16 @@ def main():
 
     if args.workload == "dyn":
         return measure_dyn(args, local_rank, block, mf, sb)
-    sampler = ClockSampler(local_rank) if rank == 0 and not args.no_clocks else None
-    R = measure(args.workload, args.scaling, args.voices, args.total_voices, args.min_seconds, not args.no_realtime, sampler)
+    sampler = ClockSampler(local_rank) if rank == 0 and args.full and not args.no_clocks else None
+    R = measure(args.workload, args.scaling, args.voices, args.total_voices, args.min_seconds, args.full and not args.no_realtime, sampler, want_dump=bool(args.dump_outputs))
+    if R["dump"] is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "master_bus.npy"), R["dump"])
     # BASELINE config 5 as north_star states it — 8192 voices with the full chain, voice-sharded over the GPUs of the node — rides along in
     # the same line (config.strong_c5): the driver's 1 / 2 / 4 / 8-GPU runs then measure the >= 6x claim itself, next to the
     # weak-scaling `value` of the headline. --strong-c5-voices 0 switches it off.
     S5 = None
-    if args.strong_c5_voices > 0 and not (args.workload == "c5" and args.scaling == "strong"):
+    if args.full and args.strong_c5_voices > 0 and not (args.workload == "c5" and args.scaling == "strong"):
         S5 = measure("c5", "strong", 0, args.strong_c5_voices, min(args.min_seconds, 0.25), False)
     name, v_per_gpu, total_voices, M = R["name"], R["v_per_gpu"], R["total_voices"], R["M"]
     dts, legs, rt_dts, rt_legs, peak, offline_calls, roofline_of = R["dts"], R["legs"], R["rt_dts"], R["rt_legs"], R["peak"], R["offline_calls"], R["roofline_of"]
@@ -874,7 +903,7 @@ def main():
                 "roofline_frac": ach5 / HBM_PEAK_GBS, "kernel": S5["kernel"], "kernel_ms_per_block": ms5 / bpl5 if bpl5 else 0.0, "repeats": len(S5["dts"]),
                 "bus_peak": S5["peak"],
             }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(name, block)
         print(json.dumps(out))
     if world > 1 or force_dist:

@@ -236,7 +236,7 @@ def test_baseline_configs_full_size_against_oracle(name, voices, blocks):
         assert rms(acc - a) <= 1e-6 and np.abs(acc - a).max() <= 1e-5
 
 
-def _run_bench(args, env_extra, launcher=None, timeout=900):
+def _run_bench(args, env_extra, launcher=None, timeout=900, full=True):
     import json
     import os
     import subprocess
@@ -248,6 +248,8 @@ def _run_bench(args, env_extra, launcher=None, timeout=900):
         env.pop(k, None)
     if "--strong-c5-voices" not in args:
         args = args + ["--strong-c5-voices", "0"]     # (the BASELINE config 5 leg of the default line: its own test below)
+    if full:
+        args = args + ["--full"]                      # (repeated legs, real-time legs, strong_c5, clocks, cpu_baseline: behind --full)
     cmd = (launcher or [sys.executable]) + [os.path.join(root, "bench.py")] + args
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
@@ -297,6 +299,33 @@ def test_bench_single_gpu_line_shape():
     assert d["config"]["blocks_per_call_requested"] == 32 and d["config"]["blocks_per_call"] == 20      # (as issued: a 20-step leg is one call of 20 blocks)
     assert c["single_thread"]["cores"] == 1 and 0 < c["single_thread"]["value"] <= c["value"] * 1.5
     assert "strong_c5" not in d["config"]
+
+
+def test_bench_plain_run_times_exactly_its_steps(tmp_path):
+    """A plain run (no --full) times ONE leg of exactly --steps blocks and carries the headline figure alone; --dump-outputs writes the master
+    bus of the last timed step, the last of warmup + steps blocks of the seeded graph: the same samples as the ABI's host write path renders there,
+    and the same from run to run."""
+    from phonic_amd import workloads as wl
+    from phonic_amd.graph import Graph
+
+    steps, warmup, voices = 12, 4, 64
+    d = _run_bench(["--steps", str(steps), "--warmup", str(warmup), "--voices", str(voices), "--dump-outputs", str(tmp_path / "out")], {}, full=False)
+    assert d["steps"] == steps and d["warmup"] == warmup and d["repeats"]["n"] == 1 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert abs(d["value"] - voices * 1024 * steps / (d["ms_per_step"] * steps * 1e-3)) / d["value"] < 1e-6
+    assert abs(d["repeats"]["timed_seconds"] - d["ms_per_step"] * steps * 1e-3) < 1e-9
+    assert "cpu_baseline" not in d and "realtime" not in d["config"] and "strong_c5" not in d["config"] and "clocks" not in d["config"]
+    assert d["roofline"]["launches"] > 0 and d["roofline"]["kernel_ms"] > 0
+    bus = np.load(tmp_path / "out" / "master_bus.npy")
+    assert bus.dtype == np.float32 and bus.shape == (1024, 2) and np.isfinite(bus).all()
+    assert abs(float(np.abs(bus).max()) - d["config"]["bus_peak"]) < 1e-7
+    g = Graph(SR, 2, 1024, 0)
+    wl.build_headline(g, voices, 0, voices, 2.0)
+    ref = g.render(warmup + steps, 1024)[-2048:].reshape(1024, 2)
+    g.close()
+    assert np.abs(bus - ref).max() <= 1e-6, float(np.abs(bus - ref).max())
+    again = tmp_path / "again"
+    _run_bench(["--steps", str(steps), "--warmup", str(warmup), "--voices", str(voices), "--dump-outputs", str(again)], {}, full=False)
+    assert np.array_equal(np.load(again / "master_bus.npy"), bus)
 
 
 def test_bench_line_carries_the_strong_scaling_leg_of_config_5():
@@ -378,7 +407,7 @@ def test_bench_two_ranks_on_one_gpu_control_flow(steps, warmup, reduce_every):
     env = dict(os.environ, PHONIC_BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", str(warmup), "--voices", "64", "--reduce-every", str(reduce_every),
-           "--superblock", str(min(reduce_every, 4)), "--repeats", "2", "--strong-c5-voices", "0"]
+           "--superblock", str(min(reduce_every, 4)), "--repeats", "2", "--strong-c5-voices", "0", "--full"]
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

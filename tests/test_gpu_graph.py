@@ -1208,6 +1208,8 @@ def test_write_allocates_nothing_and_never_blocks_on_a_callers_stream():
     staging inside the first write after a change, command lists go through a pre-allocated ring — so the library's own HIP call
     counters (pg_debug_hip_calls) must not move across writes: no allocation, no release, and on a caller's stream no host wait and no
     blocking copy either — including the FIRST write after add_voice / add_effect and writes that carry parameter automation."""
+    import gc
+
     import torch
     from phonic_amd.graph import Graph, hip_calls
 
@@ -1227,6 +1229,7 @@ def test_write_allocates_nothing_and_never_blocks_on_a_callers_stream():
         assert g.write_device(buf.data_ptr(), n_blocks * 2048, pos, stream.cuda_stream) == n_blocks * 2048
         pos += n_blocks * 1024
 
+    gc.collect()   # (the counters are process-wide: graphs of earlier tests that sit in reference cycles are released here, not by a collection inside the window)
     before = hip_calls()
     write()                                    # first write after construction: topology upload + patch kernel, all asynchronous
     for _ in range(4):
@@ -2043,6 +2046,8 @@ def test_device_failure_makes_the_graph_silent_for_good():
     stays failed (every later write returns 0 at once, nothing is launched), pg_last_error_message names the cause, and the control calls are
     still accepted (a handle may outlive its source). Injected with pg_debug_fail_launch_round; the sharded handle fails as a whole when one
     of its shards does; other graphs of the process are untouched."""
+    import gc
+
     from phonic_amd.graph import Graph, ShardedGraph, hip_calls
 
     lib = _capi.load()
@@ -2064,6 +2069,7 @@ def test_device_failure_makes_the_graph_silent_for_good():
     out[:] = 3.0
     assert g.write(out, 2 * N) == 0                          # the second fails: 0, like a panicked GuardedSource
     assert b"injected device failure" in lib.pg_last_error_message()
+    gc.collect()   # (the counters are process-wide: graphs of earlier tests that sit in reference cycles are released here, not by a collection inside the window)
     launches_before = hip_calls()
     for b in range(3, 6):
         assert g.write(out, b * N) == 0                      # ... and stays silent

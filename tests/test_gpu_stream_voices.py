@@ -241,6 +241,8 @@ def test_fed_voices_in_super_block_launches_equal_single_block_launches():
 def test_feed_and_write_allocate_nothing():
     """The rings are reserved by add_stream_voice; feeding copies into pinned memory, the write moves it with asynchronous copies on the caller's
     stream: no allocation, no release, no host wait, no blocking copy (pg_debug_hip_calls)."""
+    import gc
+
     import torch
     from phonic_amd.graph import hip_calls
 
@@ -254,6 +256,7 @@ def test_feed_and_write_allocate_nothing():
     bus = torch.zeros(2048, device="cuda:0")
     g.feed_voice(v, tone[:2 * 4096]); g.feed_voice(v2, tone[:4096:2].copy())
     assert g.write_device(bus.data_ptr(), 2048, 0, stream.cuda_stream) == 2048        # (the first write after a change uploads the topology)
+    gc.collect()   # (the counters are process-wide: graphs of earlier tests that sit in reference cycles are released here, not by a collection inside the window)
     before = hip_calls()
     for b in range(1, 9):
         g.feed_voice(v, tone[2 * 4096 * b // 4:2 * 4096 * (b + 1) // 4] if b < 3 else tone[:2 * 900])

@@ -5,7 +5,7 @@ O=gpurun_out/$T
 mkdir -p $O
 for rep in 1 2; do
   for sb in 1 4 16 32; do
-    timeout -k 10 200 python bench.py --superblock $sb --steps 96 --warmup 32 --no-cpu-baseline > $O/sb${sb}_$rep.json 2> $O/sb${sb}_$rep.err || echo "FAILED sb=$sb"
+    timeout -k 10 200 python bench.py --full --superblock $sb --steps 96 --warmup 32 --no-cpu-baseline > $O/sb${sb}_$rep.json 2> $O/sb${sb}_$rep.err || echo "FAILED sb=$sb"
     python - $O/sb${sb}_$rep.json $sb <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

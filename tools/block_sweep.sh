@@ -6,7 +6,7 @@ O=gpurun_out/profiles_$R
 mkdir -p $O
 for rep in 1 2; do
   for b in 1024 2048 4096; do
-    python bench.py --block $b --steps $((20480 / b)) --warmup $((4096 / b * 2)) --no-cpu-baseline > $O/${R}_headline_block${b}_rep${rep}.json 2>> $O/bench.err || { echo "bench --block $b failed"; tail -5 $O/bench.err; exit 1; }
+    python bench.py --full --block $b --steps $((20480 / b)) --warmup $((4096 / b * 2)) --no-cpu-baseline > $O/${R}_headline_block${b}_rep${rep}.json 2>> $O/bench.err || { echo "bench --block $b failed"; tail -5 $O/bench.err; exit 1; }
   done
 done
 python - $O $R <<'PY'

@@ -49,7 +49,7 @@ def bench_row(label, name, extra=""):
         add("C5 at 8192 voices on this GPU (`config.strong_c5`)", f"{s5['value'] / 1e9:.2f} G voice-frames/s, {s5['ms_per_step']:.4f} ms per step, {s5['roofline_frac']:.3f}", name)
 
 
-bench_row("H, default line (`python bench.py`)", "headline_bench.json")
+bench_row("H, full line (`python bench.py --full`)", "headline_bench.json")
 bench_row("H, the driver's arguments (`--steps 20 --warmup 5`)", "headline_bench_driver_args.json")
 dk = load("headline_rocprofv3_dominant_kernel.json")
 if dk:

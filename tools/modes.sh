@@ -1,6 +1,6 @@
 # usage (GPU box): bash tools/modes.sh [reps]  — bench the three reverb render modes interleaved on the same box, report the best of reps
 cd $GRAFT_REPO_ROOT
-for rep in $(seq 1 ${1:-3}); do for m in 1 2 0; do python bench.py --steps 80 --warmup 20 --no-cpu-baseline --staged $m 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print($m, d['ms_per_step'], d['roofline']['kernel_ms'])"; done; done > /tmp/modes.txt
+for rep in $(seq 1 ${1:-3}); do for m in 1 2 0; do python bench.py --full --steps 80 --warmup 20 --no-cpu-baseline --staged $m 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print($m, d['ms_per_step'], d['roofline']['kernel_ms'])"; done; done > /tmp/modes.txt
 python - <<'PY'
 import collections
 b = collections.defaultdict(lambda: [9, 9])

@@ -6,7 +6,7 @@ i=0
 for c in "SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VMEM" "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64"; do
   i=$((i+1))
   rm -rf /tmp/pmci_$i
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmci_$i -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --staged 2 --superblock 1 > /tmp/pmci_$i.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmci_$i -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --staged 2 --superblock 1 > /tmp/pmci_$i.log 2>&1
   f=$(find /tmp/pmci_$i -name "*counter_collection.csv" | head -1)
   if [ -z "$f" ]; then echo "# pass '$c' produced no counters"; tail -3 /tmp/pmci_$i.log; continue; fi
   python3 - "$f" <<'PY'

@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmcs_$c
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcs_$c -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --staged 2 > /tmp/pmcs_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcs_$c -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --staged 2 > /tmp/pmcs_$c.log 2>&1
   python3 - $(find /tmp/pmcs_$c -name "*counter_collection.csv" | head -1) $c <<'PY'
 import csv, sys, collections
 acc = collections.defaultdict(list)

@@ -14,7 +14,7 @@ rm -rf $O; mkdir -p $O
 SB=16
 COMMON="--no-cpu-baseline --strong-c5-voices 0 --no-realtime --superblock $SB"
 rm -rf /tmp/kt_$tag
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python3 bench.py $COMMON --repeats 3 --steps 96 --warmup 32 "$@" > $O/${R}_${tag}_bench_under_rocprofv3.json 2> /tmp/kt_$tag.err || { echo "bench under rocprofv3 failed"; tail -5 /tmp/kt_$tag.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$tag -- python3 bench.py --full $COMMON --repeats 3 --steps 96 --warmup 32 "$@" > $O/${R}_${tag}_bench_under_rocprofv3.json 2> /tmp/kt_$tag.err || { echo "bench under rocprofv3 failed"; tail -5 /tmp/kt_$tag.err; exit 1; }
 cp $(find /tmp/kt_$tag -name "*kernel_stats.csv" | head -1) $O/${R}_${tag}_rocprofv3_kernel_stats.csv
 python3 - $(find /tmp/kt_$tag -name "*kernel_trace.csv" | head -1) $SB $K $O/${R}_${tag}_bench_under_rocprofv3.json > $O/${R}_${tag}_rocprofv3_dominant_kernel.json <<'PY'
 import csv, json, sys
@@ -37,7 +37,7 @@ cat $O/${R}_${tag}_rocprofv3_dominant_kernel.json
 [ "${PROFILE_PMC:-1}" = "0" ] && exit 0
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_${tag}_$c
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$c -- python3 bench.py $COMMON --repeats 2 --steps 64 --warmup 32 "$@" > /tmp/pmc_${tag}_$c.log 2>&1 || { echo "counter pass $c failed"; tail -5 /tmp/pmc_${tag}_$c.log; exit 1; }
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$c -- python3 bench.py --full $COMMON --repeats 2 --steps 64 --warmup 32 "$@" > /tmp/pmc_${tag}_$c.log 2>&1 || { echo "counter pass $c failed"; tail -5 /tmp/pmc_${tag}_$c.log; exit 1; }
   python3 - $(find /tmp/pmc_${tag}_$c -name "*counter_collection.csv" | head -1) $SB > $O/${R}_${tag}_pmc_$c.csv <<'PY'
 import csv, sys, collections
 acc = collections.defaultdict(list)
@@ -68,7 +68,7 @@ d = {"workload": b["config"]["workload"], "voices_per_gpu": b["config"]["voices_
      "FETCH_SIZE_KiB_per_block": f, "WRITE_SIZE_KiB_per_block": w,
      "correction": "gfx950: FETCH_SIZE reports half of the bytes read (MI355X_MICROARCH.md, HBM/rocprofv3 section): read bytes = 2 x FETCH_SIZE x 1024; WRITE_SIZE exact; calibration on this library's access pattern: profiles/r04/r04_ringstream_pmc.json",
      "traffic_bytes_per_block": t, "algorithmic_bytes_per_block": alg, "traffic_over_algorithmic": (t / alg) if t else None,
-     "command": "tools/profile_workload.sh: rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace --output-format csv -- python3 bench.py <workload args> --superblock 16 --steps 64 --warmup 32 --repeats 2 --no-cpu-baseline --strong-c5-voices 0 --no-realtime (one pass per counter; per block = the 16-block dispatches / 16)"}
+     "command": "tools/profile_workload.sh: rocprofv3 --pmc <FETCH_SIZE|WRITE_SIZE> --kernel-trace --output-format csv -- python3 bench.py --full <workload args> --superblock 16 --steps 64 --warmup 32 --repeats 2 --no-cpu-baseline --strong-c5-voices 0 --no-realtime (one pass per counter; per block = the 16-block dispatches / 16)"}
 json.dump(d, open(os.path.join(O, f"{R}_{tag}_pmc_traffic.json"), "w"), indent=1)
 print(json.dumps(d))
 PY

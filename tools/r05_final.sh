@@ -4,7 +4,7 @@
 O=gpurun_out/r05_final; mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; tail -2 $O/pytest.log
 for b in 128 256 512 1024 2048 4096; do
-  python bench.py --steps $((40960 / b > 160 ? 160 : 40960 / b)) --warmup 10 --block $b --no-cpu-baseline --strong-c5-voices 0 > $O/r05_headline_block${b}_bench.json 2>> $O/err.log; echo "block $b rc=$?"
+  python bench.py --full --steps $((40960 / b > 160 ? 160 : 40960 / b)) --warmup 10 --block $b --no-cpu-baseline --strong-c5-voices 0 > $O/r05_headline_block${b}_bench.json 2>> $O/err.log; echo "block $b rc=$?"
 done
 python tools/per_effect.py 1024 > $O/r05_per_effect.jsonl 2>> $O/err.log; echo "per_effect rc=$?"
 python tools/exp_generic_paths.py 1024 headline,stream,resampled,nested > $O/r05_generic_paths.jsonl 2>> $O/err.log; echo "generic_paths rc=$?"

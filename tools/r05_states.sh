@@ -3,14 +3,14 @@
 # a few seconds of continuous load — clocks, power and the power limit's throttle residency in every line
 O=gpurun_out/r05_states; mkdir -p $O
 A="--no-cpu-baseline --strong-c5-voices 0 --no-realtime"
-python bench.py --steps 20 --warmup 5 $A > $O/a1_steps20.json 2>> $O/err.log
-python bench.py --steps 20 --warmup 5 $A > $O/a2_steps20.json 2>> $O/err.log
-python bench.py --steps 40 --warmup 10 $A > $O/b1_steps40.json 2>> $O/err.log
-python bench.py --steps 20 --warmup 5 $A > $O/a3_steps20.json 2>> $O/err.log
-python bench.py --steps 100 --warmup 20 $A > $O/c1_steps100.json 2>> $O/err.log
-python bench.py --steps 20 --warmup 5 --min-seconds 3 $A > $O/a4_steps20_3s.json 2>> $O/err.log
-python bench.py --steps 40 --warmup 10 --min-seconds 3 $A > $O/b2_steps40_3s.json 2>> $O/err.log
-python bench.py --steps 20 --warmup 2000 $A > $O/a5_steps20_warm2000.json 2>> $O/err.log
+python bench.py --full --steps 20 --warmup 5 $A > $O/a1_steps20.json 2>> $O/err.log
+python bench.py --full --steps 20 --warmup 5 $A > $O/a2_steps20.json 2>> $O/err.log
+python bench.py --full --steps 40 --warmup 10 $A > $O/b1_steps40.json 2>> $O/err.log
+python bench.py --full --steps 20 --warmup 5 $A > $O/a3_steps20.json 2>> $O/err.log
+python bench.py --full --steps 100 --warmup 20 $A > $O/c1_steps100.json 2>> $O/err.log
+python bench.py --full --steps 20 --warmup 5 --min-seconds 3 $A > $O/a4_steps20_3s.json 2>> $O/err.log
+python bench.py --full --steps 40 --warmup 10 --min-seconds 3 $A > $O/b2_steps40_3s.json 2>> $O/err.log
+python bench.py --full --steps 20 --warmup 2000 $A > $O/a5_steps20_warm2000.json 2>> $O/err.log
 python - $O <<'PY'
 import json, sys, glob, os
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "*.json"))):

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 rm -rf /tmp/kt
-rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --steps 40 --warmup 10 --no-cpu-baseline "$@" > /tmp/kt.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --full --steps 40 --warmup 10 --no-cpu-baseline "$@" > /tmp/kt.log 2>&1
 f=$(find /tmp/kt -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

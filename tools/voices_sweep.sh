@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 T=${1:-sweep}; O=gpurun_out/$T; mkdir -p $O
 for v in 512 1024 2048 4096; do
-  timeout -k 10 300 python bench.py --voices $v --steps 64 --warmup 32 --repeats 3 --no-cpu-baseline > $O/headline_${v}v.json 2> $O/headline_${v}v.err || echo FAILED
+  timeout -k 10 300 python bench.py --full --voices $v --steps 64 --warmup 32 --repeats 3 --no-cpu-baseline > $O/headline_${v}v.json 2> $O/headline_${v}v.err || echo FAILED
   python - $O/headline_${v}v.json $v <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
