@@ -268,6 +268,29 @@ int pg_graph_stop_all_voices(pg_graph* g);
 int pg_graph_set_voice_speed(pg_graph* g, int voice_id, double speed, float glide_semitones_per_second, uint64_t sample_time);
 int pg_graph_seek_voice(pg_graph* g, int voice_id, double position_seconds, uint64_t sample_time);
 
+/* Per-voice AHDSR volume envelope: AhdsrParameters / AhdsrEnvelope (src/utils/ahdsr.rs) as the sampler puts them around every voice chain
+ * (src/generator/sampler/voice.rs:28-30, :469-486). Times are f32 seconds — the value Duration::as_secs_f32() returns for the reference's
+ * Duration; 0 skips the stage (a rate of f32::MAX, ahdsr.rs:160-169, :205-214, :240-249). Scalings in [-1, 1]: 0 linear, > 0 logarithmic,
+ * < 0 exponential (AhdsrParameters::apply_scaling, ahdsr.rs:324-345). As in the reference, a decay scaling only has a range to work on when
+ * the attack time is 0: a timed attack leaves target_volume at the sustain level (ahdsr.rs:456-468, :526-542). */
+typedef struct pg_ahdsr_params { float attack_s, attack_scaling, hold_s, decay_s, decay_scaling, sustain_level, release_s, release_scaling; } pg_ahdsr_params;
+/* AhdsrParameters::default (ahdsr.rs:348-359): attack 10 ms, hold 1 s, decay 500 ms, sustain 0.75, release 1 s, scalings 0 */
+void pg_ahdsr_params_default(pg_ahdsr_params* p);
+/* SamplerVoice::start (voice.rs:181-184): AhdsrParameters::new_with_scaling(..) + set_sample_rate(graph rate) (ahdsr.rs:75-98, :123-136), then
+ * AhdsrEnvelope::note_on(params, 1.0) (ahdsr.rs:402-419). Only before the voice has rendered a frame (PG_ERR_STATE afterwards). Errors as
+ * the reference's setters (ahdsr.rs:143-152, :179-188, :224-233, :259-268): a scaling outside [-1, 1], a sustain level outside [0, 1]; also
+ * a negative or non-finite time (no Duration holds one) and a null `p` — PG_ERR_PARAMETER, checked before anything touches the device.
+ * The envelope multiplies what the voice's panning step wrote (voice.rs:469-486); when it reaches Idle the voice ends with that write
+ * (voice.rs:488-495). A unit that holds a living enveloped voice is rendered by the exact kernel. */
+int pg_graph_set_voice_envelope(pg_graph* g, int voice_id, const pg_ahdsr_params* p);
+/* SamplerVoice::stop (voice.rs:196-212): AhdsrEnvelope::note_off (ahdsr.rs:422-436) at exactly `sample_time` (0: the next write's first frame)
+ * — the release runs from the envelope's current level; a voice without an envelope stops there like pg_graph_stop_voice (voice.rs:207-208).
+ * Any thread. */
+int pg_graph_release_voice(pg_graph* g, int voice_id, uint64_t sample_time);
+/* AhdsrEnvelope::stage (ahdsr.rs:389-393): 0 Idle, 1 Attack, 2 Hold, 3 Decay, 4 Sustain, 5 Release; -1: the voice has no envelope (or is
+ * gone). Waits for the graph's stream: call it after pg_graph_write / a synchronize. */
+int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
+
 /* Source::write(&mut output, &SourceTime{pos_in_frames}) of the main MixedSource
  * (src/source/mixed.rs:659-719): returns the samples written == n_samples, or 0 when the
  * graph is empty (or after a device failure: GuardedSource, src/source/guarded.rs:87-107).
@@ -392,6 +415,10 @@ int pg_sharded_stop_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_tim
 int pg_sharded_stop_all_voices(pg_sharded_graph* s);
 int pg_sharded_remove_voice(pg_sharded_graph* s, int voice_id);
 int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id);
+/* pg_graph_set_voice_envelope / _release_voice / _voice_envelope_stage (src/utils/ahdsr.rs, src/generator/sampler/voice.rs:181-212) on the voice's shard */
+int pg_sharded_set_voice_envelope(pg_sharded_graph* s, int voice_id, const pg_ahdsr_params* p);
+int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time);
+int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id);
 /* Source::write: host buffer (waits for the result) / buffer on the root device (asynchronous on the shards' streams, several calls may be
  * enqueued before pg_sharded_synchronize). A call of ANY length is ONE write of the one main mixer — messages processed once on every shard,
  * one call end — walked on the reference's chunk grid (min(remaining, 4096) frames from the call's start and from every main-mixer event of

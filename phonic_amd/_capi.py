@@ -73,6 +73,21 @@ class ParamDesc(C.Structure):
     ]
 
 
+class AhdsrParams(C.Structure):
+    """pg_ahdsr_params: AhdsrParameters::new_with_scaling's arguments, times as f32 seconds."""
+    _fields_ = [(n, C.c_float) for n in ("attack_s", "attack_scaling", "hold_s", "decay_s", "decay_scaling", "sustain_level", "release_s", "release_scaling")]
+
+
+def ahdsr_params(**kw):
+    """AhdsrParameters::default() (reference src/utils/ahdsr.rs:348-359) with overrides."""
+    p = AhdsrParams(0.010, 0.0, 1.0, 0.5, 0.0, 0.75, 1.0, 0.0)
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, float(v))
+    return p
+
+
 def make_init(params=None, reverb_seeds=None, lfo_seed=None):
     """Build a pg_effect_init. params: dict {fourcc-str: raw value}; reverb_seeds: (fpd_l, fpd_r, [16 phases]); lfo_seed: the four u64 of the
     Delay LFO's Xoshiro256++ state (Random / Smooth Random shapes)."""
@@ -267,6 +282,13 @@ def load():
     lib.pg_graph_deferred_units.argtypes = [vp]
     lib.pg_graph_is_voice_playing.restype = C.c_int
     lib.pg_graph_is_voice_playing.argtypes = [vp, C.c_int]
+    lib.pg_ahdsr_params_default.restype = None
+    lib.pg_ahdsr_params_default.argtypes = [P(AhdsrParams)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        for name, args in (("set_voice_envelope", [C.c_int, P(AhdsrParams)]), ("release_voice", [C.c_int, C.c_uint64]), ("voice_envelope_stage", [C.c_int])):
+            fn = getattr(lib, prefix + name)
+            fn.restype = C.c_int
+            fn.argtypes = [vp] + args
     lib.pg_graph_kernel_ms.restype = C.c_double
     lib.pg_graph_kernel_ms.argtypes = [vp, C.c_int, P(C.c_uint64)]
     lib.pg_graph_kernel_stats.restype = C.c_int

@@ -171,6 +171,20 @@ class GraphHandle:
     def stop_voice(self, voice, sample_time):
         self._check(self._fn("graph_stop_voice")(self._h, voice, sample_time))
 
+    def set_voice_envelope(self, voice, params=None, **kw):
+        """AHDSR volume envelope of a voice (SamplerVoice::start: parameters at the graph's rate + note_on(1.0)); before the voice renders.
+        `params`: a _capi.AhdsrParams, or keyword overrides of AhdsrParameters::default()."""
+        p = params if params is not None else _capi.ahdsr_params(**kw)
+        self._check(self._fn("graph_set_voice_envelope")(self._h, voice, C.byref(p)))
+
+    def release_voice(self, voice, sample_time):
+        """SamplerVoice::stop: the envelope's note_off at exactly sample_time (a voice without an envelope stops there)."""
+        self._check(self._fn("graph_release_voice")(self._h, voice, sample_time))
+
+    def voice_envelope_stage(self, voice):
+        """0 Idle .. 5 Release, -1: no envelope (waits for the graph's stream)."""
+        return int(self._fn("graph_voice_envelope_stage")(self._h, voice))
+
     def remove_voice(self, voice):
         """MixerMessage::RemoveSource: the source leaves its mixer at the start of the next write, at once (no fade)."""
         self._check(self._fn("graph_remove_voice")(self._h, voice))

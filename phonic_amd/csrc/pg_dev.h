@@ -216,6 +216,36 @@ struct PgVoice {
   int32_t persistent;  // host: !PlayingSource::is_transient — an exhausted source stays in the mixer's list (mixed.rs:612-620)
 };
 
+// AhdsrEnvelope + AhdsrParameters of one voice (src/utils/ahdsr.rs:26-39, :367-373): the sampler's volume envelope around the voice chain
+// (src/generator/sampler/voice.rs:28-30, :469-486). Kept in a side table indexed by the voice's device index (PgLaunch::env) — PgVoice is
+// staged in LDS one dword per lane by every kernel and does not grow for a feature only the exact kernel renders.
+enum PgAhdsrStage { PG_AHDSR_IDLE = 0, PG_AHDSR_ATTACK = 1, PG_AHDSR_HOLD = 2, PG_AHDSR_DECAY = 3, PG_AHDSR_SUSTAIN = 4, PG_AHDSR_RELEASE = 5 };
+enum { PG_AHDSR_HOLD_ZERO = 1, PG_AHDSR_DECAY_ZERO = 2, PG_AHDSR_RELEASE_ZERO = 4 };   // PgEnvParams::zero_times: `Duration::is_zero()` of the three times
+struct PgEnvState {  // AhdsrEnvelope
+  int32_t stage;
+  float target_volume, hold_samples_remaining, release_output, output;
+};
+struct PgEnvParams {  // AhdsrParameters after set_sample_rate(graph rate); a zero attack / decay / release time is a rate of f32::MAX
+  float attack_rate, decay_rate, release_rate;
+  float attack_scaling, decay_scaling, release_scaling;
+  float sustain_level;
+  float hold_samples;   // hold_time.as_secs_f32() * sample_rate as f32
+  int32_t zero_times;
+};
+struct PgEnv {
+  int32_t on;           // 0: the voice has no envelope
+  PgEnvState state;
+  PgEnvParams params;
+  int32_t pad;
+};
+// The side table in device memory: this header, then one PgEnv per voice, indexed like PgLaunch::voices. `done`: one word per voice in mapped
+// host memory that the exact kernel sets when an enveloped voice has ended — the host then takes the voice's unit off the exact kernel again.
+struct PgEnvTable {
+  int32_t* done;
+  uint64_t cap;         // entries behind the header: the kernel takes no entry at or beyond it
+};
+static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 16, "the entries follow the header, 16-byte aligned");
+
 // Parameter indices per effect kind = order of `Effect::parameters()` in the reference.
 enum { P_GAIN_GAIN = 0, P_GAIN_DCFM };
 enum { P_PAN_PAN = 0, P_PAN_WIDTH, P_PAN_INVL, P_PAN_INVR };
@@ -292,6 +322,7 @@ enum PgCmdType {
   // main chunk but beyond this piece. The kernels close per-chunk / per-call state at a piece's end when the marker's position is that end.
   CMD_CHUNK_END = 9,
   CMD_CALL_END = 10,
+  CMD_VOICE_RELEASE = 11,  // target = voice index: AhdsrEnvelope::note_off at `frame`; a voice without an envelope stops (stop_time = value64), voice.rs:196-212
 };
 #define PG_MAX_CALLS 64  // calls of one sub-mixer per launch round (bits of PgUnit::call_audible); the host bounds the round accordingly
 struct PgCmd {
@@ -355,7 +386,12 @@ struct PgLaunch {
   int32_t* error_word;    // device word of sticky consistency flags (PG_DEVERR_*), nullptr: not collected
   uint32_t fast_scratch_bytes;  // host: LDS arena of the fast kernels for the effect kinds this graph holds (0: the full arena)
   uint32_t pad_scratch;
-  int32_t* index_log;     // test hook (generic kernel only, see FastCtx::idx_log): read indices of the time-parallel delay-line paths
+  // One pointer, two launch families (the staged kernels keep a copy of this record in LDS — it must not grow): a standalone effect's launches
+  // (voices == nullptr, pg_effect.hip) may carry the index log; a graph's launches (voices != nullptr) the envelope table. pg_unit_kernel only.
+  union {
+    int32_t* index_log;   // test hook (see FastCtx::idx_log): read indices of the time-parallel delay-line paths
+    PgEnvTable* env;      // volume envelopes (pg_graph_set_voice_envelope); nullptr: no voice of the graph ever had one
+  };
   // Per-block `audible` results of this level's units: block c of launch slot b -> audible_tab[c * audible_stride + b]. PgUnit::audible holds
   // the last block only; the mixer sum ORs one row of this table per block (audible_input of process_effects, mixed.rs:696-706), so the bus
   // chain behind a super-block launch sees every block's own flag. nullptr: not collected (standalone effects, bus launches).

@@ -114,6 +114,8 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
       if (!(k == PG_FX_GAIN || k == PG_FX_PANNING || k == PG_FX_FILTER || k == PG_FX_EQ5 || k == PG_FX_DELAY || k == PG_FX_REVERB || k == PG_FX_CHORUS || k == PG_FX_COMPRESSOR || k == PG_FX_GATE || k == PG_FX_DISTORTION)) u.static_defer = 1;
       if (m != 0 && k == PG_FX_GAIN && (int)g->fx[f]->init_raw[1] != 0) g->wide = true;  // DC filter: blocked scan, compiled into the wide variants only
     }
+    // a living voice with a volume envelope: the exact kernel renders it (pg_graph_set_voice_envelope); the mixer's other units keep their kernels
+    if (m != 0) for (int v : mx.voices) if (g->voices[v].env_live) u.static_defer = 1;
     // staged pipeline: a sub-mixer whose chain is [Gain (no DC filter) | Panning]* -> Reverb
     u.staged = 0;
     if (m != 0 && !u.static_defer && !mx.fx.empty() && g->fx[mx.fx.back()]->kind == PG_FX_REVERB) {
@@ -162,7 +164,7 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
     int slot = g->source_unit_of_voice[v];
     PgUnit& u = topo[slot];
     u.voice_off = (int)vidx.size(); u.n_voices = 1; u.n_fx = 0; u.fx_off = 0;
-    u.static_defer = 0;
+    u.static_defer = g->voices[v].env_live ? 1 : 0;
     if (g->voices[v].outer) g->any_outer = true;
     u.voice0 = g->voices[v].dev_index;
     vidx.push_back(g->voices[v].dev_index);
@@ -223,6 +225,46 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
   return PG_OK;
 }
 
+// The envelope side table and its `ended` words for `n` voices (grow-by-doubling; the graph is quiescent: nothing in flight reads the old ones).
+static int graph_env_reserve(pg_graph* g, size_t n) {
+  if (n <= g->env_cap) return PG_OK;
+  const size_t cap = std::max<size_t>(next_pow2(n), 64);
+  PgEnvTable* nt = nullptr;
+  int32_t* nh = nullptr;
+  int32_t* ndd = nullptr;
+  HIP_TRY(pg_malloc((void**)&nt, sizeof(PgEnvTable) + cap * sizeof(PgEnv)));
+  PgEnv* const nd = (PgEnv*)(nt + 1);
+  if (pg_memset(nt, 0, sizeof(PgEnvTable) + cap * sizeof(PgEnv)) != hipSuccess || pg_host_malloc((void**)&nh, cap * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { (void)pg_free(nt); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
+  memset(nh, 0, cap * sizeof(int32_t));
+  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
+  PgEnvTable head;
+  head.done = ndd; head.cap = cap;
+  if (pg_memcpy(nt, &head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table upload failed"); }
+  PgEnvTable* const old_tab = g->d_env_tab;
+  int32_t* const old_done = g->h_env_done;
+  if (g->d_env) {
+    if (pg_memcpy(nd, g->d_env, g->env_cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table copy failed"); }
+    memcpy(nh, g->h_env_done, g->env_cap * sizeof(int32_t));
+  }
+  // (the new table is complete: swap first, then let go of the old one — a failure above leaves the graph on its old table)
+  g->d_env_tab = nt; g->d_env = nd; g->h_env_done = nh; g->env_cap = cap;
+  if (old_tab) (void)pg_free(old_tab);
+  if (old_done) (void)pg_host_free(old_done);
+  return PG_OK;
+}
+// Enveloped voices the exact kernel has reported as ended (or that left the graph): their units go back to the time-parallel kernels with the
+// next topology upload. Reads mapped host words: no wait.
+static void graph_poll_envelopes(pg_graph* g) {
+  for (size_t i = 0; i < g->env_voices.size();) {
+    HostVoice& hv = g->voices[g->env_voices[i]];
+    if (hv.mixer < 0 || *(volatile int32_t*)(g->h_env_done + hv.dev_index) != 0) {
+      hv.env_live = false;
+      g->env_voices.erase(g->env_voices.begin() + i);
+      g->topo_dirty = true;
+    } else ++i;
+  }
+}
+
 // Per-unit output tables the write path needs: one per block of a super-block launch, and one per piece of a chunk (the mixer sum runs
 // behind a chunk's last piece).
 static size_t graph_table_blocks(const pg_graph* g) { return std::max<size_t>(g->max_blocks, (PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames); }
@@ -234,6 +276,7 @@ static int graph_reserve(pg_graph* g) {
   if ((rc = g->d_topo.reserve(n_units)) || (rc = g->d_order.reserve(n_units)) || (rc = g->d_slot_info.reserve(n_units)) || (rc = g->d_slot_fx.reserve(n_units)) || (rc = g->d_slot_lead.reserve(n_units)) ||
       (rc = g->d_voice_index.reserve(n_voices)) || (rc = g->d_fx_index.reserve(n_fx)) || (rc = g->d_child_rows.reserve(n_mixers)))
     return rc;
+  if (g->d_env && n_voices > g->env_cap) { if ((rc = graph_env_reserve(g, n_voices))) return rc; }
   if (!g->d_cmd_ring) {
     HIP_TRY(pg_malloc((void**)&g->d_cmd_ring, PG_CMD_RING * sizeof(PgCmd)));
     HIP_TRY(pg_host_malloc((void**)&g->h_cmd_ring, PG_CMD_RING * sizeof(PgCmd), hipHostMallocDefault));
@@ -284,6 +327,19 @@ static int graph_reserve(pg_graph* g) {
 static int graph_flush_blocking(pg_graph* g) {
   int rc;
   if ((rc = g->d_units.flush()) || (rc = g->d_fx.flush()) || (rc = g->d_voices.flush()) || (rc = g->d_sched.flush())) return rc;
+  return PG_OK;
+}
+
+// The reference's parameter errors (ahdsr.rs:143-152, :179-188, :224-233, :259-268) + what no Duration can hold; touches no graph and no device.
+int pg_ahdsr_params_check(const pg_ahdsr_params* p) {
+  if (!p) return set_error(PG_ERR_PARAMETER, "envelope parameters must not be null");
+  const float times[4] = {p->attack_s, p->hold_s, p->decay_s, p->release_s};
+  static const char* const names[4] = {"attack", "hold", "decay", "release"};
+  for (int i = 0; i < 4; ++i) if (!std::isfinite(times[i]) || times[i] < 0.0f) return set_error(PG_ERR_PARAMETER, "Invalid %s time: %g. Must be finite and >= 0", names[i], (double)times[i]);
+  if (!(p->attack_scaling >= -1.0f && p->attack_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid attack scaling: %g. Must be in range [-1.0, 1.0]", (double)p->attack_scaling);
+  if (!(p->decay_scaling >= -1.0f && p->decay_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid decay scaling: %g. Must be in range [-1.0, 1.0]", (double)p->decay_scaling);
+  if (!(p->sustain_level >= 0.0f && p->sustain_level <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid sustain level: %g. Must be in range [0.0, 1.0]", (double)p->sustain_level);
+  if (!(p->release_scaling >= -1.0f && p->release_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid release scaling: %g. Must be in range [-1.0, 1.0]", (double)p->release_scaling);
   return PG_OK;
 }
 
@@ -364,6 +420,8 @@ void pg_graph_destroy(pg_graph* g) {
   if (g->d_bus_progress) (void)pg_free(g->d_bus_progress);
   if (g->h_pinned) (void)pg_host_free(g->h_pinned);
   if (g->h_feedback) (void)pg_host_free(g->h_feedback);
+  if (g->d_env_tab) (void)pg_free(g->d_env_tab);
+  if (g->h_env_done) (void)pg_host_free(g->h_env_done);
   for (auto& e : g->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_bus_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_gen_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -609,7 +667,7 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   int rc = g->d_voices.push(v, &dev_index);
   if (rc) return -graph_fail(g, rc);
   int id = (int)g->voices.size();
-  { HostVoice hv; hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.d_pcm = d_pcm; hv.d_stage = d_stage; hv.outer = inner_rate != g->sample_rate;
+  { HostVoice hv; hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_pcm; hv.d_stage = d_stage; hv.outer = inner_rate != g->sample_rate;
     hv.transient = opt->non_transient == 0; g->voices.push_back(hv); }
   g->source_unit_of_voice.push_back(-1);
   // AddSource: sort by start time, insert BEFORE equal start times (mixed.rs:324-329)
@@ -687,7 +745,7 @@ int pg_graph_add_stream_voice(pg_graph* g, int mixer_id, uint32_t channels, uint
   if (rc) { release(); return -graph_fail(g, rc); }
   const int id = (int)g->voices.size();
   HostVoice hv;
-  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.d_pcm = d_ring; hv.d_stage = d_stage; hv.outer = rate != g->sample_rate;
+  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_ring; hv.d_stage = d_stage; hv.outer = rate != g->sample_rate;
   hv.stream = true; hv.h_ring = h_ring; hv.channels = channels; hv.cap_frames = capacity_frames;
   hv.transient = opt->non_transient == 0;
   g->voices.push_back(hv);
@@ -808,6 +866,74 @@ int pg_graph_seek_voice(pg_graph* g, int voice_id, double position_seconds, uint
 int pg_graph_stop_voice(pg_graph* g, int voice_id, uint64_t sample_time) {  // MixerMessage::StopSource (mixed.rs:389-400): not an event
   return voice_message(g, voice_id, pgc::CT_VOICE_STOP, 0.0f, 0.0, sample_time);
 }
+// SamplerVoice::stop (generator/sampler/voice.rs:196-212): an event of the voice's mixer, like the other voice commands — the block is split at its frame
+int pg_graph_release_voice(pg_graph* g, int voice_id, uint64_t sample_time) {
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return voice_message(g, voice_id, pgc::CT_VOICE_RELEASE, 0.0f, 0.0, sample_time);
+}
+void pg_ahdsr_params_default(pg_ahdsr_params* p) {  // AhdsrParameters::default (utils/ahdsr.rs:348-359)
+  if (!p) return;
+  p->attack_s = 0.010f; p->attack_scaling = 0.0f; p->hold_s = 1.0f; p->decay_s = 0.5f; p->decay_scaling = 0.0f; p->sustain_level = 0.75f; p->release_s = 1.0f; p->release_scaling = 0.0f;
+}
+// AhdsrParameters::new_with_scaling + set_sample_rate(sample_rate) (ahdsr.rs:75-98, :123-136), setter by setter in the reference's order: the
+// first setup runs at the placeholder rate with the sustain level still 0 when set_decay_time divides (:205-214, :307-309); the second one —
+// set_sample_rate's, skipped when the rate IS the placeholder — is what gives decay_rate its final value.
+static PgEnvParams ahdsr_build_params(const pg_ahdsr_params& a, uint32_t sample_rate) {
+  PgEnvParams p;
+  memset(&p, 0, sizeof p);
+  uint32_t sr = 66666;  // UNINITIALIZED_SAMPLE_RATE
+  auto set_attack = [&]() { p.attack_rate = a.attack_s == 0.0f ? FLT_MAX : 1.0f / (a.attack_s * (float)sr); };
+  auto set_decay = [&]() { p.decay_rate = a.decay_s == 0.0f ? FLT_MAX : (1.0f - p.sustain_level) / (a.decay_s * (float)sr); };
+  auto set_release = [&]() { p.release_rate = a.release_s == 0.0f ? FLT_MAX : 1.0f / (a.release_s * (float)sr); };
+  set_attack(); p.attack_scaling = a.attack_scaling; set_decay(); p.decay_scaling = a.decay_scaling; p.sustain_level = a.sustain_level; set_release(); p.release_scaling = a.release_scaling;
+  if (sr != sample_rate) { sr = sample_rate; set_attack(); set_decay(); p.sustain_level = a.sustain_level; set_release(); }
+  p.hold_samples = a.hold_s * (float)sr;
+  p.zero_times = (a.hold_s == 0.0f ? PG_AHDSR_HOLD_ZERO : 0) | (a.decay_s == 0.0f ? PG_AHDSR_DECAY_ZERO : 0) | (a.release_s == 0.0f ? PG_AHDSR_RELEASE_ZERO : 0);
+  return p;
+}
+int pg_graph_set_voice_envelope(pg_graph* g, int voice_id, const pg_ahdsr_params* p) {
+  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  drain_control_messages(g);
+  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  HostVoice& hv = g->voices[voice_id];
+  // note_on belongs to the voice's start (voice.rs:181-184): no envelope for a voice that has rendered frames already
+  // (a voice renders in every write that ends behind its start time — a start time at or before a write's position starts it at once,
+  // voice_process — so it has rendered iff a write issued since it was added ended behind its start time, wherever the earlier ones stood)
+  uint64_t end_since_add = 0;
+  for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) { end_since_add = w.second; break; }
+  if (end_since_add > hv.start_time) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: an envelope is attached before the voice starts", voice_id);
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size(), (size_t)hv.dev_index + 1))) return graph_fail(g, PG_ERR_DEVICE);
+  PgEnv e;
+  memset(&e, 0, sizeof e);
+  e.on = 1;
+  e.params = ahdsr_build_params(*p, g->sample_rate);
+  // AhdsrEnvelope::note_on(parameters, 1.0) (ahdsr.rs:402-419)
+  e.state.target_volume = 1.0f;
+  if (e.params.attack_rate == FLT_MAX) {
+    e.state.output = 1.0f;
+    if (!(e.params.zero_times & PG_AHDSR_HOLD_ZERO)) { e.state.stage = PG_AHDSR_HOLD; e.state.hold_samples_remaining = e.params.hold_samples; }
+    else e.state.stage = PG_AHDSR_DECAY;
+  } else { e.state.output = 0.0f; e.state.stage = PG_AHDSR_ATTACK; }
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_memcpy(g->d_env + hv.dev_index, &e, sizeof e, hipMemcpyHostToDevice));
+  g->h_env_done[hv.dev_index] = 0;
+  if (!hv.env_live) g->env_voices.push_back(voice_id);
+  hv.env = true; hv.env_live = true;
+  g->topo_dirty = true;
+  return PG_OK;
+}
+int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id) {
+  if (!g || voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].mixer < 0 || !g->voices[voice_id].env || !g->d_env) return -1;
+  (void)hipSetDevice(g->device);
+  if (pg_stream_sync(g->stream) != hipSuccess) return -1;
+  if (g->last_stream && g->last_stream != g->stream && pg_stream_sync(g->last_stream) != hipSuccess) return -1;
+  PgEnv e;
+  if (pg_memcpy(&e, g->d_env + g->voices[voice_id].dev_index, sizeof e, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return e.on ? (int)e.state.stage : -1;
+}
 int pg_graph_remove_voice(pg_graph* g, int voice_id) {  // MixerMessage::RemoveSource (mixed.rs:149-151,400-402)
   const int rc = voice_message(g, voice_id, pgc::CT_VOICE_REMOVE, 0.0f, 0.0, 0);
   // the id is dead for every later call from here on (a second remove, a volume change: PG_ERR_NOT_FOUND as the header says), not only once the
@@ -865,7 +991,7 @@ static void drain_control_messages(pg_graph* g) {
           mx.messages.erase(std::remove_if(mx.messages.begin(), mx.messages.end(), [&](const PgCmd& x) { return x.param == m.id; }), mx.messages.end());
           // events already queued for the source stay the mixer's events: when they come due they find no source (mixed.rs:810-845) but still
           // split the block there — like the events of a removed effect
-          for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK) && e.cmd.param == m.id) {
+          for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK || e.cmd.type == CMD_VOICE_RELEASE) && e.cmd.param == m.id) {
             e.cmd.type = CMD_NOP; e.cmd.target = 0;
             if (hv.mixer == 0) e.cmd.param = -1;
           }
@@ -882,6 +1008,7 @@ static void drain_control_messages(pg_graph* g) {
         if (m.type == pgc::CT_VOICE_VOLUME) { c.type = CMD_VOICE_VOLUME; c.value = m.value; }
         else if (m.type == pgc::CT_VOICE_PAN) { c.type = CMD_VOICE_PAN; c.value = m.value; }
         else if (m.type == pgc::CT_VOICE_SPEED) { c.type = CMD_VOICE_SPEED; c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }
+        else if (m.type == pgc::CT_VOICE_RELEASE) { c.type = CMD_VOICE_RELEASE; c.value64 = m.sample_time; }
         else { c.type = CMD_VOICE_SEEK; memcpy(&c.value64, &m.dvalue, 8); }
         push_event(g, hv.mixer, m.sample_time, c);
       } break;
@@ -1172,6 +1299,7 @@ static void fill_launch(pg_graph* g, const LaunchSpan& sp, PgLaunch& L) {
   L.fast_scratch_bytes = (uint32_t)pg_fast_scratch_bytes(g->fast_kind_mask);
   L.round = (uint32_t)sp.round; L.host_feedback = g->d_feedback;
   L.grid_off = sp.grid_off; L.grid_span = sp.grid_span;
+  L.env = g->d_env_tab;
   // (a super-block runs without the resampler schedule cache: its banks alternate per launch, not per block; voices of a cached
   // class replay their schedule serially, and the cache re-validates itself by key when single-block rounds resume)
   L.sched = sp.n_chunks > 1 ? nullptr : g->d_sched.d; L.sched_bank = (int)(sp.round & 1);
@@ -1464,6 +1592,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
   if (g->last_stream && g->last_stream != stream) { if (pg_stream_sync(g->last_stream) != hipSuccess) { g->failed = true; return 0; } g->cmds_since_sync = 0; }
   g->last_stream = stream;
   if (begin) { graph_begin_write(g, pos); g->call_end = pos + n_samples / 2; }
+  if (!g->env_voices.empty()) graph_poll_envelopes(g);
   if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return 0; } }
   if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return 0; } }
   if (g->overlap_stream != stream) { g->rows_free_fresh = false; g->overlap_stream = stream; }
@@ -1625,7 +1754,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
         // deferred for those alone is back on its kernel in the next block, so the host need not wait for the device to say so — offline
         // calls keep their super-block launches between such commands (notes that stop and start: bench.py --workload dyn --churn).
         bool may_ramp = false;
-        for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK);
+        for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK || c.type == CMD_VOICE_RELEASE);
         // (the round AFTER this one is the first whose scan sees what the commands left behind: this round's own count of state-deferred units
         // was taken in front of them)
         if (may_ramp) g->last_change_round = sp.round + 1;
@@ -1677,6 +1806,11 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
     }
     done += chunk_n;
     if (g->defer_bus && span_ends_at_event && chunk_n == span && done < frames) g->defer_cuts.push_back(done);
+  }
+  if (done) {  // suffix maxima of the writes' end positions (one entry while the position only moves forward): pg_graph_set_voice_envelope
+    g->write_count += 1;
+    while (!g->write_end_max.empty() && g->write_end_max.back().second <= pos + done) g->write_end_max.pop_back();
+    g->write_end_max.emplace_back(g->write_count, pos + done);
   }
   return (size_t)done * 2;
 }

@@ -7,6 +7,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -194,6 +196,9 @@ struct HostVoice {
   size_t cap_frames = 0;
   uint64_t fed = 0, sent = 0;      // frames accepted from the host / frames whose copy to the device ring has been enqueued
   uint64_t consumed_known = 0;     // frames the device is known to have read (pg_graph_stream_voice_consumed): bounds what may be overwritten
+  uint64_t added_at_write = 0;     // pg_graph::write_count when the voice was added (an envelope is attached before the voice renders a frame)
+  bool env = false;                // an envelope was attached (pg_graph_set_voice_envelope): its state sits in pg_graph::d_env[dev_index]
+  bool env_live = false;           // ... and the voice has not ended yet: its unit is rendered by the exact kernel (PgUnit::static_defer)
 };
 struct HostMixer {
   int unit_slot = -1;              // sub-mixer unit; for the main mixer: the bus unit
@@ -339,10 +344,20 @@ struct pg_graph {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_gen_pool;
   size_t ev_gen_used = 0;
   uint64_t stat_unit_blocks = 0, stat_generic_launches = 0;
+  // volume envelopes (pg_graph_set_voice_envelope): side table indexed by the voices' device index, allocated with the first envelope; one word
+  // per voice in mapped host memory that the exact kernel sets when an enveloped voice ends (polled at the top of a write: no wait)
+  PgEnvTable* d_env_tab = nullptr; // header + entries (PgLaunch::env)
+  PgEnv* d_env = nullptr;          // its entries
+  int32_t* h_env_done = nullptr;
+  size_t env_cap = 0;
+  std::vector<int> env_voices;     // ids of the voices whose envelope is alive
+  uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
+  std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };
 
 // ---- graph internals used by the sharded handle (pg_host.hip) -------------------------------------------------
 int graph_quiesce(pg_graph* g);
+int pg_ahdsr_params_check(const pg_ahdsr_params* p);   // the reference's parameter errors (PG_OK / PG_ERR_PARAMETER): no graph, no device
 void graph_begin_write(pg_graph* g, uint64_t pos);
 void drain_control_messages_public(pg_graph* g);
 bool graph_is_empty(const pg_graph* g);

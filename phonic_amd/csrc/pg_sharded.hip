@@ -442,6 +442,22 @@ int pg_sharded_stop_all_voices(pg_sharded_graph* s) {
   for (pg_graph* g : s->shards) { int rc = pg_graph_stop_all_voices(g); if (rc) return rc; }
   return PG_OK;
 }
+int pg_sharded_set_voice_envelope(pg_sharded_graph* s, int voice_id, const pg_ahdsr_params* p) {
+  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }   // (before the id: parameter errors never depend on the graph)
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_envelope(s->shards[shard_of(pk)], local_of(pk), p);
+}
+int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_release_voice(s->shards[shard_of(pk)], local_of(pk), sample_time);
+}
+int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) {
+  if (!s || voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return -1;
+  const int32_t pk = s->voice_map.get((size_t)voice_id);
+  return pg_graph_voice_envelope_stage(s->shards[shard_of(pk)], local_of(pk));
+}
 int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id) {
   if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return 0;
   const int32_t pk = s->voice_map.get((size_t)voice_id);

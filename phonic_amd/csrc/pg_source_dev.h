@@ -932,13 +932,146 @@ DEVO int resampled_source_write(PgVoice* v, float* out, int frames, int pending_
   return total_written / C;
 }
 
+// ---- AhdsrEnvelope (src/utils/ahdsr.rs) around a voice, as SamplerVoice::process applies it (src/generator/sampler/voice.rs:469-486) ----
+// The envelope is an f32 recurrence with stage switches — `output += rate` per frame, not associative — so one lane walks it; the curve
+// scaling on top (two powf per frame) is independent per frame, so all lanes apply it: the split of the smoother ramps below.
+constexpr int AHDSR_TILE = 2048;          // frames per tile: raw outputs at dst[0 .. AHDSR_TILE), their stages (int) behind them
+constexpr float AHDSR_EPS = 1.1920929e-07f;  // f32::EPSILON
+constexpr float AHDSR_SILENCE = 0.001f;      // -60 dB (ahdsr.rs:376)
+
+// AhdsrEnvelope::run for n frames, the state machine only (ahdsr.rs:454-516): the raw `output` of every frame and the stage the frame left.
+// The linear stages are single IEEE operations in the reference's order (`output -= release_output * release_rate` is a product, rounded,
+// then a difference: never an fma).
+DEVO void ahdsr_sequence(PgEnvState& st, const PgEnvParams& p, float* dst, int n) {
+  int* const dst_stage = (int*)dst + AHDSR_TILE;
+  int stage = st.stage;
+  float out = st.output, tv = st.target_volume, hold = st.hold_samples_remaining;
+  const float rel_out = st.release_output, sus = p.sustain_level;
+  for (int i = 0; i < n; ++i) {
+    if (stage == PG_AHDSR_ATTACK) {
+      out = __fadd_rn(out, p.attack_rate);
+      if (out >= tv) {
+        out = tv;
+        tv = sus;
+        if (!(p.zero_times & PG_AHDSR_HOLD_ZERO)) { stage = PG_AHDSR_HOLD; hold = p.hold_samples; }
+        else stage = PG_AHDSR_DECAY;
+      }
+    } else if (stage == PG_AHDSR_HOLD) {
+      hold = __fsub_rn(hold, 1.0f);
+      if (hold <= 0.0f) stage = (p.zero_times & PG_AHDSR_DECAY_ZERO) ? PG_AHDSR_SUSTAIN : PG_AHDSR_DECAY;
+    } else if (stage == PG_AHDSR_DECAY) {
+      if (out > sus) {
+        out = __fsub_rn(out, p.decay_rate);
+        if (out <= sus) { out = sus; stage = PG_AHDSR_SUSTAIN; }
+      } else {  // attack target < sustain level
+        out = __fadd_rn(out, p.decay_rate);
+        if (out >= sus) { out = sus; stage = PG_AHDSR_SUSTAIN; }
+      }
+    } else if (stage == PG_AHDSR_RELEASE) {
+      out = __fsub_rn(out, __fmul_rn(rel_out, p.release_rate));
+      if (out <= AHDSR_SILENCE) { out = 0.0f; stage = PG_AHDSR_IDLE; }
+    }
+    dst[i] = out;
+    dst_stage[i] = stage;
+  }
+  st.stage = stage; st.output = out; st.target_volume = tv; st.hold_samples_remaining = hold;
+}
+// AhdsrEnvelope::note_off (ahdsr.rs:422-436)
+DEVO void ahdsr_note_off(PgEnvState& st, const PgEnvParams& p) {
+  if (!(p.zero_times & PG_AHDSR_RELEASE_ZERO)) {
+    st.target_volume = 0.0f;
+    st.release_output = st.output;
+    st.stage = st.release_output > AHDSR_EPS ? PG_AHDSR_RELEASE : PG_AHDSR_IDLE;
+  } else {
+    st.output = 0.0f; st.release_output = 0.0f; st.stage = PG_AHDSR_IDLE;
+  }
+}
+// AhdsrParameters::apply_scaling (ahdsr.rs:324-345)
+DEVO float ahdsr_apply_scaling(float value, float scaling) {
+  if (scaling == 0.0f || value == 0.0f) return value;
+  const float EULER_DIV_2 = 2.71828182845904523536f / 2.0f;   // std::f32::consts::E / 2.0
+  scaling = -scaling;
+  if (scaling > 0.0f) return powf(value, 1.0f + powf(scaling, EULER_DIV_2) * 16.0f);
+  return 1.0f - powf(1.0f - value, 1.0f + powf(-scaling, EULER_DIV_2) * 16.0f);
+}
+// What run() returns for a frame whose state machine left (stage, raw): the stage's curve scaling (ahdsr.rs:519-551). `tv` = target_volume
+// while the envelope is in that stage (it changes only where Attack ends and at note_off: constant over the Attack frames and over the Decay
+// frames of a tile).
+DEVO float ahdsr_scaled(int stage, float raw, float tv, const PgEnvParams& p) {
+  if (stage == PG_AHDSR_ATTACK && p.attack_scaling != 0.0f) {
+    const float progress = raw / fmaxf(tv, AHDSR_EPS);
+    return ahdsr_apply_scaling(progress, p.attack_scaling) * tv;
+  }
+  if (stage == PG_AHDSR_DECAY && p.decay_scaling != 0.0f) {
+    const float sus = p.sustain_level;
+    const float range = fmaxf(fabsf(tv - sus), AHDSR_EPS);
+    const float progress = tv > sus ? (tv - raw) / range : (raw - tv) / range;
+    const float sp = ahdsr_apply_scaling(progress, p.decay_scaling);
+    return tv > sus ? tv - sp * range : tv + sp * range;
+  }
+  if (stage == PG_AHDSR_RELEASE && p.release_scaling != 0.0f) {
+    const float initial = fmaxf(raw, AHDSR_EPS);
+    const float progress = 1.0f - raw / initial;
+    return initial * (1.0f - ahdsr_apply_scaling(progress, p.release_scaling));
+  }
+  return raw;
+}
+// The envelope over the `frames_w` stereo frames a voice wrote into `out` (voice.rs:469-486). A piece that begins in Sustain or Idle is one
+// multiplication by output() (:472-477) — the per-frame walk hands out the same value there, so how a call is cut into pieces does not change
+// the audio. Tiles of AHDSR_TILE frames: lane 0 lays out the raw outputs and stages in the source stage's scratch (free once the source has
+// written), all lanes scale and multiply. Returns with the voice marked finished once the stage is Idle: the sampler resets a voice in the
+// process call in which its envelope became Idle (:488-495), the mixer then drops it like any exhausted transient source.
+DEVO void ahdsr_apply(PgVoice* v, PgEnv* e, float* out, int frames_w, const SrcScratch& S) {
+  const int tid = pg_tid(), nt = blockDim.x;
+  float* const seq = S.sched_f;
+  static_assert(2 * AHDSR_TILE <= SRC_OUT_CAP + SRC_WIN_CAP + 2 * (SRC_WIN_CAP + 4), "raw outputs and stages of a tile fit the scratch in front of the control words");
+  const int* const seq_stage = (const int*)seq + AHDSR_TILE;
+  int base = 0;
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) { S.ctl[6] = e->state.stage; S.ctl[7] = (int)__float_as_uint(e->state.output); }
+    __syncthreads();
+    const int st0 = S.ctl[6];
+    if (base >= frames_w) break;
+    if (st0 == PG_AHDSR_SUSTAIN || st0 == PG_AHDSR_IDLE) {
+      const float gain = __uint_as_float((uint32_t)S.ctl[7]);
+      for (int i = 2 * base + tid; i < 2 * frames_w; i += nt) out[i] *= gain;   // scale_buffer
+      break;
+    }
+    const int n = frames_w - base < AHDSR_TILE ? frames_w - base : AHDSR_TILE;
+    if (tid == 0) {
+      PgEnvState st = e->state;
+      S.ctl[4] = (int)__float_as_uint(st.target_volume);   // target_volume of the tile's Attack frames ...
+      ahdsr_sequence(st, e->params, seq, n);
+      S.ctl[5] = (int)__float_as_uint(st.target_volume);   // ... and of its Decay frames
+      e->state = st;
+    }
+    __threadfence_block();
+    __syncthreads();
+    const PgEnvParams p = e->params;
+    const float tv_attack = __uint_as_float((uint32_t)S.ctl[4]), tv_decay = __uint_as_float((uint32_t)S.ctl[5]);
+    for (int f = tid; f < n; f += nt) {
+      const int stage = seq_stage[f];
+      const float val = ahdsr_scaled(stage, seq[f], stage == PG_AHDSR_ATTACK ? tv_attack : tv_decay, p);
+      out[2 * (base + f)] *= val; out[2 * (base + f) + 1] *= val;
+    }
+    base += n;
+  }
+  __syncthreads();
+  if (tid == 0 && S.ctl[6] == PG_AHDSR_IDLE) v->finished = 1;
+  __syncthreads();
+}
+
 // PreloadedFileSource::write [+ ResampledSource::write] + ChannelMappedSource::write (mapped.rs:61-99) +
 // AmplifiedSource::write (amplified.rs:93-104) + PannedSource::write (panned.rs:93-104).
 // Renders `frames` stereo output frames into `out` (LDS, 2*frames floats); returns stereo samples written.
 // ADAPTERS: 0 = the kernel variant never sees a ResampledSource-backed or host-fed voice (the staged kernels: the host keeps such units out);
 // 1 = host-fed voices only (the four-per-CU fast kernel: a graph with a ResampledSource takes the wide kernel instead); 2 = both.
-template <bool GLIDE, int ADAPTERS>
-DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const SrcScratch& S, float* acc, int* added, bool ask_ends = true) {
+// ENV: the kernel variant renders volume envelopes (pg_unit_kernel only: the host sends units with an enveloped voice there); `env` = the
+// voice's envelope or nullptr. An enveloped voice takes the separate passes (nothing fused into the resampler's output loop, nothing added
+// into the mixer's block on the way): the envelope multiplies what the panning step left.
+template <bool GLIDE, int ADAPTERS, bool ENV = false>
+DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const SrcScratch& S, float* acc, int* added, bool ask_ends = true, PgEnv* env = nullptr) {
   *added = 0;
   const int tid = pg_tid(), nt = blockDim.x;
   const int C = (int)v->channels;
@@ -959,7 +1092,8 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
     }
   } else {
     int post_on;
-    wf = file_source_write<GLIDE>(v, out, frames, pending_stop, S, acc, true, &post_on, ask_ends);
+    const bool enveloped = ENV && env != nullptr;
+    wf = file_source_write<GLIDE>(v, out, frames, pending_stop, S, enveloped ? nullptr : acc, !enveloped, &post_on, ask_ends);
     if (post_on) { *added = acc ? 1 : 0; return wf * 2; }  // (stereo samples: a fused mono voice has been mapped to both channels on the way)
   }
   __syncthreads();
@@ -1016,6 +1150,7 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
     }
   }
   __syncthreads();
+  if (ENV && env != nullptr) ahdsr_apply(v, env, out, written / 2, S);
   return written;
 }
 
@@ -1023,10 +1158,10 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
 // into `sig`. One call of process_sources = one chunk of the mixer, rendered as pieces: `chunk_first` names the chunk's first piece,
 // `chunk_end` the position at which the chunk ends. Returns bit 0: the source produced output in this piece; bit 1 (first piece only): it
 // has not started yet but will inside this chunk — `audible_input` of the chunk (mixed.rs:696-706) is decided at the first piece.
-template <bool GLIDE, int ADAPTERS = 2>
+template <bool GLIDE, int ADAPTERS = 2, bool ENV = false>
 DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp, int frames, uint64_t pos, const SrcScratch& S0,
                        const PgSchedEntry* sched, int sched_bank, bool have_word = false, uint32_t word = 0, uint64_t call_end = 0, bool chunk_first = true,
-                       uint64_t chunk_end = 0, bool in_lds = false) {
+                       uint64_t chunk_end = 0, bool in_lds = false, PgEnv* env = nullptr, int32_t* env_done = nullptr) {
   SrcScratch S = S0;
   const int tid = pg_tid(), nt = blockDim.x;
   static_assert(sizeof(PgVoice) / 4 <= 256, "one dword per lane");
@@ -1080,7 +1215,7 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
     // (a call that reaches the end of this piece without reaching a stop time or the end of the chunk goes on in the next piece)
     const bool ask_ends = pos + (uint64_t)frames >= chunk_end || samples_until_stop <= (uint64_t)(out_len - total_written);
     int added;
-    int written = voice_write<GLIDE, ADAPTERS>(lv, tmp, to_write / 2, pending_stop, S, sig + total_written, &added, ask_ends);
+    int written = voice_write<GLIDE, ADAPTERS, ENV>(lv, tmp, to_write / 2, pending_stop, S, sig + total_written, &added, ask_ends, env);
     if (!added) for (int i = tid; i < written; i += nt) sig[total_written + i] = sig[total_written + i] + tmp[i];  // add_buffers
     __syncthreads();
     total_written += written;
@@ -1090,10 +1225,15 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
     if (!ask_ends && written == to_write) {
       // the call filled this piece and goes on in the chunk's next one: the mixer looks at the source (is_exhausted, written == 0) when the
       // call returns, not here — a ResampledSource whose staging buffers happen to be empty at this frame refills them inside the same call
-    } else if (exhausted && !lv->persistent) {
-      if (tid == 0) { if (ADAPTERS == 2 && lv->active && lv->outer_on) lv->zombie_end = call_end; lv->active = 0; lv->chunk_skip = 1; }
-      break;
-    } else if (written == 0) { if (tid == 0) lv->chunk_skip = 1; break; }
+    } else {
+      // an enveloped voice that is finished — its envelope went Idle, or its file ran out — is finished for good (seeks leave a finished source
+      // alone): the host takes the unit off this kernel, also for a source the mixer keeps in its list (non_transient)
+      if (ENV && env != nullptr && env_done != nullptr && exhausted && tid == 0) { *(volatile int32_t*)env_done = 1; __threadfence_system(); }
+      if (exhausted && !lv->persistent) {
+        if (tid == 0) { if (ADAPTERS == 2 && lv->active && lv->outer_on) lv->zombie_end = call_end; lv->active = 0; lv->chunk_skip = 1; }
+        break;
+      } else if (written == 0) { if (tid == 0) lv->chunk_skip = 1; break; }
+    }
   }
   __syncthreads();
   {  // write the voice state back

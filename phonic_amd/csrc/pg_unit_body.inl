@@ -452,7 +452,7 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
   S.sched_rd = nullptr;
   FastCtx fc;
   fc.tmp = tmp; fc.tmp_floats = 2 * NA; fc.scratch = scratch; fc.ctl = ctl; fc.red = red; fc.diag = L.diag; fc.err = L.error_word;
-  fc.idx_log = FAST_ONLY ? nullptr : L.index_log;  // (a constant in the fast kernels: the logging stores are compiled out)
+  fc.idx_log = (FAST_ONLY || L.voices != nullptr) ? nullptr : L.index_log;  // (a constant in the fast kernels: the logging stores are compiled out; a graph's launches carry the envelope table in that word)
   if (L.mode != 2) PG_STAMP(L.diag, 0);
 
   // ---- two-kernel protocol: the lean fast kernel defers units it cannot run to the generic kernel ----
@@ -556,6 +556,11 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         else if (cmd.type == CMD_VOICE_STOP) { L.voices[cmd.target].has_stop = 1; L.voices[cmd.target].stop_time = cmd.value64; }
         else if (cmd.type == CMD_VOICE_SPEED) voice_set_speed(&L.voices[cmd.target], __longlong_as_double((long long)cmd.value64), cmd.value);
         else if (cmd.type == CMD_VOICE_SEEK) voice_seek(&L.voices[cmd.target], __longlong_as_double((long long)cmd.value64));
+        else if (cmd.type == CMD_VOICE_RELEASE) {  // SamplerVoice::stop (voice.rs:196-212): the envelope's release, or a plain stop without one
+          PgEnv* const e = (L.voices && L.env && (uint64_t)cmd.target < L.env->cap) ? (PgEnv*)(L.env + 1) + cmd.target : nullptr;   // (PgEnvTable::cap: entries the table holds)
+          if (e && e->on) { PgEnvState st = e->state; ahdsr_note_off(st, e->params); e->state = st; }
+          else { L.voices[cmd.target].has_stop = 1; L.voices[cmd.target].stop_time = cmd.value64; }
+        }
         ctl[2] = flush;
       }
       __syncthreads();
@@ -603,8 +608,12 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
       int later = 0;
       for (int vi = 0; vi < PG_UL(n_voices); ++vi) {
         PgVoice* gv = &L.voices[vi == 0 ? PG_UL(voice0) : L.voice_index[PG_UL(voice_off) + vi]];
-        const int r = voice_process<!FAST_ONLY, (FAST_ONLY && KMASK == (0x7ff & ~((1 << 5) | (1 << 7)))) ? 1 : 2>(gv, lv, sseg, tmp, seg, pos, S, L.sched, L.sched_bank, tables && vi == 0, voice_word, call_end_pos, seg_first, seg_chunk_end,
-                                                                                                                      resident && vi == 0);
+        // (volume envelopes: the exact kernel only — the host routes a unit that holds an enveloped voice here, static_defer)
+        PgEnvTable* const envs = (!FAST_ONLY && L.voices) ? L.env : nullptr;
+        PgEnv* env = (envs && (uint64_t)(gv - L.voices) < envs->cap) ? (PgEnv*)(envs + 1) + (gv - L.voices) : nullptr;
+        if (!FAST_ONLY && env && !env->on) env = nullptr;
+        const int r = voice_process<!FAST_ONLY, (FAST_ONLY && KMASK == (0x7ff & ~((1 << 5) | (1 << 7)))) ? 1 : 2, !FAST_ONLY>(gv, lv, sseg, tmp, seg, pos, S, L.sched, L.sched_bank, tables && vi == 0, voice_word, call_end_pos, seg_first, seg_chunk_end,
+                                                                                                                      resident && vi == 0, env, (!FAST_ONLY && env) ? envs->done + (gv - L.voices) : nullptr);
         audible_input |= (r & 1) != 0;
         later |= r & 2;
       }

@@ -213,6 +213,16 @@ class ShardedGraph:
     def remove_voice(self, voice):
         self._check(self._lib.pg_sharded_remove_voice(self._h, voice))
 
+    def set_voice_envelope(self, voice, params=None, **kw):
+        p = params if params is not None else _capi.ahdsr_params(**kw)
+        self._check(self._lib.pg_sharded_set_voice_envelope(self._h, voice, C.byref(p)))
+
+    def release_voice(self, voice, sample_time):
+        self._check(self._lib.pg_sharded_release_voice(self._h, voice, sample_time))
+
+    def voice_envelope_stage(self, voice):
+        return int(self._lib.pg_sharded_voice_envelope_stage(self._h, voice))
+
     def set_voice_speed(self, voice, speed, sample_time, glide=None):
         self._check(self._lib.pg_sharded_set_voice_speed(self._h, voice, float(speed), float(glide) if glide else 0.0, sample_time))
 
