@@ -291,6 +291,37 @@ int pg_graph_release_voice(pg_graph* g, int voice_id, uint64_t sample_time);
  * gone). Waits for the graph's stream: call it after pg_graph_write / a synchronize. */
 int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
 
+/* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
+ * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and
+ * RMS (AudioLevel, src/source/metered.rs), linear. The meter runs on the device (pg_meter_kernel: the sub-mixers' samples never leave it).
+ * AudioLevelState (metered.rs:75-143) per mixer: peak_hold (f32) and sum_square (f64) per channel, collected_frames, a clock with start_time 0,
+ * update_interval = (interval.as_secs_f64() * sample_rate as f64) as u64 frames, truncated (src/utils/time.rs:28-35). One RECORD is one write call
+ * of the wrapped mixer that returned samples: every sample enters peak_hold by a compare (a NaN never does) and sum_square as an f64 square; the
+ * frames are counted; then, with `time` the START of that call, `time.saturating_sub(start_time) >= update_interval` publishes peak = peak_hold,
+ * rms = sqrt(sum_square / collected_frames) as f32, sets start_time = time and zeroes the accumulators.
+ *   main mixer: one record per pg_graph_write* call whatever its length or the chunks and pieces it is rendered in, over the samples the call
+ *     delivers (behind the bus effects), time = the call's pos_in_frames; a call that returns 0 (mixed.rs:664-670) records nothing.
+ *   sub-mixer (nested ones too): one record per chunk of its parent — the call of SubMixerProcessor::process (submixer.rs:47-77) in which its
+ *     silence gate is decided, over the same buffer — time = the chunk's start (chunks: min(remaining, 4096) frames, cut at the parent's events,
+ *     mixed.rs:679-712). A sub-mixer with no source in its list, no effect, no sub-mixer and no pending event as the chunk begins returns 0 and
+ *     records nothing: its level stays FROZEN at what it last published (decided on the device, where the drop of an exhausted transient source
+ *     is known at the reference's time). A call the silence gate has closed (2 s below -60 dB) reads as zeros.
+ * The reference skips a record when its try_lock fails (metered.rs:196-204); nothing contends here, so no record is ever skipped.
+ * The published RMS is within one f32 rounding of the reference's sequential f64 sum (the kernel sums in a fixed parallel order), the peak equal. */
+typedef struct pg_audio_level { float peak[2]; float rms[2]; } pg_audio_level;   /* AudioLevel, linear; 16 bytes */
+/* PlayerConfig::metering_interval for all mixers of the graph, also those added later: interval_seconds >= 0 (the value Duration::as_secs_f64()
+ * returns) enables metering and resets every mixer to AudioLevelState::new (levels 0); < 0 is None: metering off, nothing is launched and a write
+ * is exactly what it is without this call. NaN / +inf: PG_ERR_PARAMETER (checked before the handle), a null handle too. Owner thread; waits for
+ * earlier writes like every graph-changing call. All memory (state, published levels, span tables) is reserved here and in the add_* calls:
+ * writes allocate nothing. */
+int pg_graph_set_metering(pg_graph* g, double interval_seconds);
+/* Player::audio_level (mixer 0) / MixerHandle::audio_level: the level the mixer last published. Any thread, any time: reads pinned host memory
+ * the kernel writes (guarded by a sequence word; the reader retries), never waits for the device, makes no HIP call. After pg_graph_synchronize
+ * (or a host-buffer pg_graph_write) it reflects every record of the writes issued so far. PG_ERR_STATE: metering is off; PG_ERR_NOT_FOUND: unknown
+ * or removed mixer; PG_ERR_PARAMETER: null handle or null `out`. With pg_graph_set_defer_bus the main mixer's record is taken at the end of
+ * pg_graph_process_bus_device*, with that call's pos_in_frames and samples, not in the write. */
+int pg_graph_mixer_audio_level(pg_graph* g, int mixer_id, pg_audio_level* out);
+
 /* Source::write(&mut output, &SourceTime{pos_in_frames}) of the main MixedSource
  * (src/source/mixed.rs:659-719): returns the samples written == n_samples, or 0 when the
  * graph is empty (or after a device failure: GuardedSource, src/source/guarded.rs:87-107).
@@ -419,6 +450,10 @@ int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id);
 int pg_sharded_set_voice_envelope(pg_sharded_graph* s, int voice_id, const pg_ahdsr_params* p);
 int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time);
 int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id);
+/* pg_graph_set_metering / pg_graph_mixer_audio_level on the one mixer: a sub-mixer's level comes from its shard; mixer 0's is measured on the root
+ * behind the bus chain, one record per pg_sharded_write* call (src/source/metered.rs:75-143) */
+int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds);
+int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_level* out);
 /* Source::write: host buffer (waits for the result) / buffer on the root device (asynchronous on the shards' streams, several calls may be
  * enqueued before pg_sharded_synchronize). A call of ANY length is ONE write of the one main mixer — messages processed once on every shard,
  * one call end — walked on the reference's chunk grid (min(remaining, 4096) frames from the call's start and from every main-mixer event of

@@ -78,6 +78,34 @@ class AhdsrParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("attack_s", "attack_scaling", "hold_s", "decay_s", "decay_scaling", "sustain_level", "release_s", "release_scaling")]
 
 
+class AudioLevel(C.Structure):
+    """pg_audio_level: AudioLevel (reference src/source/metered.rs), linear peak and RMS per channel."""
+    _fields_ = [("peak", C.c_float * 2), ("rms", C.c_float * 2)]
+
+
+def _db(x):
+    import math
+
+    return 20.0 * math.log10(x) if x > 0.0 else float("-inf")
+
+
+class Level:
+    """What Player::audio_level / MixerHandle::audio_level return: per-channel `peak` and `rms` (linear, exactly the f32 values the meter
+    published) plus `peak_db` / `rms_db` as AudioLevel::peak_db does: 20 log10, -inf at 0."""
+
+    def __init__(self, raw):
+        self.peak = (float(raw.peak[0]), float(raw.peak[1]))
+        self.rms = (float(raw.rms[0]), float(raw.rms[1]))
+        self.peak_db = tuple(_db(x) for x in self.peak)
+        self.rms_db = tuple(_db(x) for x in self.rms)
+
+    def __eq__(self, other):
+        return isinstance(other, Level) and self.peak == other.peak and self.rms == other.rms
+
+    def __repr__(self):
+        return f"Level(peak={self.peak}, rms={self.rms})"
+
+
 def ahdsr_params(**kw):
     """AhdsrParameters::default() (reference src/utils/ahdsr.rs:348-359) with overrides."""
     p = AhdsrParams(0.010, 0.0, 1.0, 0.5, 0.0, 0.75, 1.0, 0.0)
@@ -289,6 +317,13 @@ def load():
             fn = getattr(lib, prefix + name)
             fn.restype = C.c_int
             fn.argtypes = [vp] + args
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        fn = getattr(lib, prefix + "set_metering")
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_double]
+        fn = getattr(lib, prefix + "mixer_audio_level")
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int, P(AudioLevel)]
     lib.pg_graph_kernel_ms.restype = C.c_double
     lib.pg_graph_kernel_ms.argtypes = [vp, C.c_int, P(C.c_uint64)]
     lib.pg_graph_kernel_stats.restype = C.c_int

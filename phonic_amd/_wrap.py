@@ -185,6 +185,17 @@ class GraphHandle:
         """0 Idle .. 5 Release, -1: no envelope (waits for the graph's stream)."""
         return int(self._fn("graph_voice_envelope_stage")(self._h, voice))
 
+    def set_metering(self, interval_seconds):
+        """PlayerConfig::metering_interval for every mixer of the graph: seconds >= 0 switches the level meters on (all levels reset to 0),
+        None switches them off."""
+        self._check(self._fn("graph_set_metering")(self._h, -1.0 if interval_seconds is None else float(interval_seconds)))
+
+    def audio_level(self, mixer_id=0):
+        """Player::audio_level (mixer 0) / MixerHandle::audio_level: the level the mixer last published (a _capi.Level). Never waits for the device."""
+        raw = _capi.AudioLevel()
+        self._check(self._fn("graph_mixer_audio_level")(self._h, mixer_id, C.byref(raw)))
+        return _capi.Level(raw)
+
     def remove_voice(self, voice):
         """MixerMessage::RemoveSource: the source leaves its mixer at the start of the next write, at once (no fade)."""
         self._check(self._fn("graph_remove_voice")(self._h, voice))

@@ -170,6 +170,9 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
     vidx.push_back(g->voices[v].dev_index);
     g->order.push_back(slot);
   }
+  g->row_of_mixer = row_of_mixer;
+  g->meter_fragile = false;
+  for (size_t m = 1; m < g->mixers.size(); ++m) g->meter_fragile |= !g->mixers[m].removed && g->mixers[m].fx.empty() && g->mixers[m].children.empty();
   g->n_graph_units = (int)g->order.size();
   g->levels.back().cnt = g->n_graph_units - g->levels.back().off;  // the main mixer's sources belong to the last level
   int rc;
@@ -321,7 +324,7 @@ static int graph_reserve(pg_graph* g) {
     HIP_TRY(pg_malloc((void**)&g->d_partial, (nr * g->stride + 4) * sizeof(float)));
     g->partial_rows = nr;
   }
-  return PG_OK;
+  return graph_meter_reserve(g);   // (metering on: state, published levels and launch tables for the mixers and voices the graph holds now)
 }
 // blocking upload of whatever still waits in the staging blocks (introspection calls that read device state)
 static int graph_flush_blocking(pg_graph* g) {
@@ -393,6 +396,7 @@ pg_graph* pg_graph_create(uint32_t sample_rate, uint32_t channel_count, size_t m
   g->mixers[0].depth = 0;
   g->mixers[0].unit_slot = new_unit(g.get(), UNIT_BUS);
   if (g->mixers[0].unit_slot < 0) return nullptr;
+  if (!g->mixer_alive_tab.append(1)) return nullptr;
   if (graph_reserve(g.get())) return nullptr;
   return g.release();
 }
@@ -422,6 +426,7 @@ void pg_graph_destroy(pg_graph* g) {
   if (g->h_feedback) (void)pg_host_free(g->h_feedback);
   if (g->d_env_tab) (void)pg_free(g->d_env_tab);
   if (g->h_env_done) (void)pg_host_free(g->h_env_done);
+  graph_meter_release(g);
   for (auto& e : g->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_bus_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_gen_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -446,6 +451,7 @@ int pg_graph_add_mixer_to(pg_graph* g, int parent_mixer_id) {
   g->mixers.back().depth = g->mixers[parent_mixer_id].depth + 1;
   if (parent_mixer_id != 0) g->mixers[parent_mixer_id].children.push_back(id);
   g->mixers.back().events.reserve(64);
+  if (!g->mixer_alive_tab.append(1)) return -set_error(PG_ERR_STATE, "too many mixers");
   if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
   return id;
 }
@@ -536,6 +542,7 @@ int pg_graph_remove_mixer(pg_graph* g, int mixer_id) {
     for (int v : mx.voices) { g->voices[v].mixer = -1; g->voice_alive_tab.set((size_t)v, 0); g->retired_voices.push_back(v); }
     mx.children.clear(); mx.fx.clear(); mx.voices.clear(); mx.events.clear(); mx.messages.clear(); mx.bus_events.clear();
     mx.removed = true;
+    g->mixer_alive_tab.set((size_t)gone[i], 0);
   }
   g->topo_dirty = true;
   return PG_OK;
@@ -1572,6 +1579,68 @@ static void collect_piece_commands(pg_graph* g, std::vector<PgCmd>& cmds, uint64
   }
 }
 
+// ---- level metering of the sub-mixers (pg_k_meter.hip): one record per chunk of the parent, over the unit's output rows ----
+// The job of sub-mixer m over spans [span_first, +span_count) of the launch being put together. A mixer with effects, sub-mixers or pending
+// events writes whatever its sources do (mixed.rs:664-670); one with sources only lets the device decide (its list when the call began);
+// one with nothing records nothing.
+static void meter_push_job(pg_graph* g, size_t m, int span_first, int span_count) {
+  const HostMixer& mx = g->mixers[m];
+  if (mx.removed || m >= g->row_of_mixer.size() || g->row_of_mixer[m] < 0 || span_count <= 0) return;
+  const bool known = !mx.fx.empty() || !mx.children.empty() || !mx.events.empty();
+  if (!known && mx.voices.empty()) return;
+  PgMeterJob j;
+  memset(&j, 0, sizeof j);
+  j.base = g->d_unit_out + (size_t)g->row_of_mixer[m] * g->stride;
+  j.slot = (int32_t)m; j.unit = mx.unit_slot; j.span_first = span_first; j.span_count = span_count; j.flags = known ? PG_METER_JOB_WRITTEN : 0;
+  g->meter_jobs.push_back(j);
+}
+// A super-block launch sequence: k blocks of mf frames from `now`, whole chunks of CH frames (the last one may be shorter), one level.
+static void meter_collect_super(pg_graph* g, uint64_t now, uint64_t k, uint64_t mf) {
+  g->meter_jobs.clear(); g->meter_spans.clear();
+  const uint64_t CH = PG_MAX_FRAMES, per_chunk = CH % mf == 0 ? CH / mf : k;
+  const uint64_t chunk_stride = (uint64_t)g->unit_out_rows * g->stride;
+  for (uint64_t b = 0; b < k; ++b) {
+    PgMeterSpan sp;
+    sp.off = b * chunk_stride; sp.time = now + (b / per_chunk) * CH; sp.n_frames = (uint32_t)mf;
+    sp.flags = ((b + 1) % per_chunk == 0 || b + 1 == k) ? PG_METER_END_OF_RECORD : 0;
+    g->meter_spans.push_back(sp);
+  }
+  for (size_t m = 1; m < g->mixers.size(); ++m) meter_push_job(g, m, 0, (int)k);
+}
+// One chunk [now, now + chunk_n) rendered as pieces of mf frames (piece p in table p). The sub-mixers of the main mixer share one record;
+// a nested one is called once per segment of its ancestors' chunks (mixed.rs:679-712): a record per segment, cut inside the pieces.
+// Called before the pieces' commands are taken out of the queues: `pending events` is what the mixers hold as the chunk begins.
+static void meter_collect_chunk(pg_graph* g, uint64_t now, uint64_t chunk_n, uint64_t mf) {
+  g->meter_jobs.clear(); g->meter_spans.clear();
+  const uint64_t chunk_stride = (uint64_t)g->unit_out_rows * g->stride, n_pieces = (chunk_n + mf - 1) / mf;
+  auto add_record = [&](uint64_t s, uint64_t e) {   // frames [s, e) of the chunk
+    for (uint64_t p = s / mf; p < n_pieces && p * mf < e; ++p) {
+      const uint64_t a = std::max(s, p * mf), b = std::min(e, std::min((p + 1) * mf, chunk_n));
+      PgMeterSpan sp;
+      sp.off = p * chunk_stride + (a - p * mf) * 2; sp.time = now + s; sp.n_frames = (uint32_t)(b - a);
+      sp.flags = b == e ? PG_METER_END_OF_RECORD : 0;
+      g->meter_spans.push_back(sp);
+    }
+  };
+  add_record(0, chunk_n);
+  const int shared = (int)g->meter_spans.size();
+  for (size_t m = 1; m < g->mixers.size(); ++m) {
+    const HostMixer& mx = g->mixers[m];
+    if (mx.removed) continue;
+    std::vector<uint64_t> cuts;
+    for (int a = mx.parent; a != 0; a = g->mixers[a].parent)
+      for (const Event& e : g->mixers[a].events) { if (e.sample_time >= now + chunk_n) break; if (e.sample_time > now) cuts.push_back(e.sample_time - now); }
+    if (cuts.empty()) { meter_push_job(g, m, 0, shared); continue; }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    cuts.push_back(chunk_n);
+    const int first = (int)g->meter_spans.size();
+    uint64_t s = 0;
+    for (uint64_t c : cuts) { add_record(s, c); s = c; }
+    meter_push_job(g, m, first, (int)g->meter_spans.size() - first);
+  }
+}
+
 // Renders frames [pos, pos + n_samples / 2) of the write call into d_out. The call is walked in the reference's chunks — min(remaining,
 // PG_MAX_FRAMES) frames from the call's start and from every main-mixer event (mixed.rs:679-712) — whatever max_frames is: a chunk is rendered
 // as pieces of at most max_frames frames, every per-chunk decision taken once per chunk on the device (pg_dev.h: PG_MAX_FRAMES).
@@ -1655,6 +1724,8 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
     uint64_t k = 0;
     if (head.empty() && span >= mf && graph_super_ok(g)) {
       uint64_t kmax = std::min<uint64_t>(span / mf, g->max_blocks);
+      // (metering a sub-mixer whose records depend on its sources: the meter looks at them chunk by chunk)
+      if (g->metering && g->meter_fragile && CH % mf == 0) kmax = std::min<uint64_t>(kmax, CH / mf);
       if (cap_frames) kmax = std::min<uint64_t>(kmax, (cap_frames - std::min<uint64_t>(done, cap_frames)) / mf);
       uint64_t t_next = UINT64_MAX;
       for (const HostMixer& mx : g->mixers) if (!mx.events.empty()) t_next = std::min(t_next, mx.events.front().sample_time);
@@ -1703,6 +1774,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
                                    aud_words + slot, stream, (int)k, (size_t)g->unit_out_rows * g->stride, (g->write_done_event && done + k * mf == frames) ? g->write_done_event : nullptr));
         if (g->write_done_event && done + k * mf == frames) g->write_done_attached = true;
       }
+      if (g->metering) { meter_collect_super(g, now, k, mf); if (graph_meter_launch(g, stream)) return fail(); }   // (in front of ev_rows_free: the rows are still this sequence's)
       if (overlap) { HIP_TRY_FAIL(hipEventRecord(g->ev_rows_free, stream)); g->rows_free_fresh = true; }
       if (!g->defer_bus && launch_bus(g, d_out + done * 2, sp, slot, stream)) return fail();
       done += k * mf;
@@ -1730,6 +1802,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       break;
     }
     if (n_pieces > g->unit_out_blocks) { set_error(PG_ERR_STATE, "per-unit buffers were not reserved for a chunk's pieces"); return fail(); }
+    if (g->metering) meter_collect_chunk(g, now, chunk_n, mf);   // (launched behind the chunk's sum)
     std::vector<LaunchSpan> spans((size_t)n_pieces);
     const uint64_t round0 = g->launch_counter;
     g->launch_counter += n_pieces;
@@ -1788,6 +1861,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       HIP_TRY_FAIL(pg_launch_mix(g->d_unit_out + (size_t)n_full * chunk_stride + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, dst + n_full * mf * 2, r.n * 2,
                                  g->d_audible_tab + (size_t)n_full * g->unit_out_rows + top.off, g->unit_out_rows, aud_words + slot0 + (int)n_full, stream, 1, chunk_stride, last_chunk_of_call ? g->write_done_event : nullptr));
     }
+    if (g->metering && graph_meter_launch(g, stream)) return fail();
     if (!g->defer_bus && !g->mixers[0].fx.empty()) {
       // the bus unit's commands of the chunk's first piece (main-mixer effect events) ride on its bus launch
       const bool bus_timed = g->timing_period > 0 && ((spans[0].round + 1) % (uint64_t)g->timing_period) == 0;
@@ -1820,6 +1894,8 @@ extern "C" {
 size_t pg_graph_write_device(pg_graph* g, float* d_out, size_t n_samples, uint64_t pos_in_frames, void* hip_stream) {
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : g->stream;
   size_t w = graph_write_impl(g, d_out, n_samples, pos_in_frames, s);
+  // the main mixer's record: the samples this call delivers, behind the bus effects (with the bus chain deferred: pg_graph_process_bus_device)
+  if (w && g->metering && !g->defer_bus && graph_meter_main(g, d_out, w / 2, pos_in_frames, true, s)) { g->failed = true; return 0; }
   if (!hip_stream && w) { if (pg_stream_sync(g->stream) != hipSuccess) { g->failed = true; return 0; } g->cmds_since_sync = 0; }
   return w;
 }
@@ -1840,8 +1916,13 @@ size_t pg_graph_write(pg_graph* g, float* out, size_t n_samples, uint64_t pos_in
     if (w == 0) {  // nothing to do (from here on): silence for the rest of a call that has produced output, 0 for one that has not
       if (g->failed || off == 0) return 0;
       memset(out + off, 0, (n_samples - off) * sizeof(float));
+      if (g->metering && !g->defer_bus) {   // the rest of the call's record is silence
+        if (graph_meter_main(g, nullptr, (n_samples - off) / 2, pos_in_frames, true, g->stream) || pg_stream_sync(g->stream) != hipSuccess) { g->failed = true; return 0; }
+      }
       break;
     }
+    // the main mixer's record covers the whole call: a part per span of the staging, the last one carries the publish check
+    if (g->metering && !g->defer_bus && graph_meter_main(g, g->d_bus, w / 2, pos_in_frames, off + w >= n_samples, g->stream)) { g->failed = true; return 0; }
     // device feedback: how many main-mixer sources are still alive (transient sources are dropped when exhausted, :715)
     if (graph_enqueue_status(g, g->stream) != PG_OK || hipMemcpyAsync(g->h_pinned, g->d_bus, w * sizeof(float), hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
         pg_stream_sync(g->stream) != hipSuccess) {
@@ -1966,8 +2047,14 @@ __global__ void pg_float_to_words_kernel(const float* __restrict__ f, int* __res
 
 extern "C" {
 
+// With the bus chain deferred the main mixer's level record is taken here, over the processed bus, with this call's position.
+static int bus_meter_record(pg_graph* g, int rc, float* d_bus, size_t n_samples, uint64_t pos_in_frames, hipStream_t s) {
+  if (rc != PG_OK || !g->metering || !g->defer_bus || n_samples < 2) return rc;
+  return graph_meter_main(g, d_bus, n_samples / 2, pos_in_frames, true, s);
+}
 int pg_graph_process_bus_device(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_in_frames, void* hip_stream) {
-  return process_bus_impl(g, d_bus, n_samples, pos_in_frames, hip_stream ? (hipStream_t)hip_stream : g->stream, nullptr);
+  hipStream_t s = hip_stream ? (hipStream_t)hip_stream : g->stream;
+  return bus_meter_record(g, process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, nullptr), d_bus, n_samples, pos_in_frames, s);
 }
 int pg_graph_audible_words(pg_graph* g) { return g->audible_valid ? g->defer_words : 0; }
 uint64_t pg_graph_next_main_event(pg_graph* g, uint64_t pos_in_frames) {
@@ -1986,14 +2073,14 @@ int pg_graph_export_audible(pg_graph* g, float* d_dst, int n_words, void* hip_st
 }
 int pg_graph_process_bus_device_flags(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_in_frames, void* hip_stream, const float* d_flags, int n_words) {
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : g->stream;
-  if (!d_flags) return process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, nullptr);
+  if (!d_flags) return bus_meter_record(g, process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, nullptr), d_bus, n_samples, pos_in_frames, s);
   const size_t fr = n_samples / 2, per_chunk = (PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames;
   const size_t need = (fr / PG_MAX_FRAMES) * per_chunk + (fr % PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames;   // pieces of an event-free call (events add pieces: pg_graph_audible_words)
   if (n_words < 0 || (size_t)n_words > g->audible_slots || (size_t)n_words < need) return set_error(PG_ERR_PARAMETER, "the bus chain needs one word per block of max_frames (%zu)", need);
   (void)hipSetDevice(g->device);
   hipLaunchKernelGGL(pg_float_to_words_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, d_flags, g->d_audible, n_words);
   HIP_TRY(hipGetLastError());
-  return process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, g->d_audible);
+  return bus_meter_record(g, process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, g->d_audible), d_bus, n_samples, pos_in_frames, s);
 }
 
 }  // extern "C"

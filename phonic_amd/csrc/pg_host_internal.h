@@ -21,6 +21,7 @@
 #include "../../include/phonic_gpu.h"
 #include "pg_ctrl.h"
 #include "pg_dev.h"
+#include "pg_meter.h"
 #include "pg_dsp_dev.h"
 #include "pg_params.h"
 
@@ -177,6 +178,17 @@ int host_fx_from_init(int kind, const pg_effect_init* init, HostFx& h);
 int build_fx_device_state(HostFx& h, uint32_t sr, int device, bool standalone, PgFx& fx);
 // PgCmd::value64 of a parameter update (time-constant coefficients computed with the host's expf)
 uint64_t fx_param_aux(int kind, int param, float raw, uint32_t sr);
+
+// Launch tables of pg_meter_kernel (pg_k_meter.hip): pinned host memory in two halves, filled launch by launch
+struct MeterRing {
+  PgMeterJob* h_jobs = nullptr; PgMeterJob* d_jobs = nullptr;
+  PgMeterSpan* h_spans = nullptr; PgMeterSpan* d_spans = nullptr;
+  size_t half_jobs = 0, half_spans = 0, nj = 0, ns = 0;   // entries per half / used in the current half
+  int turn = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool in_flight[2] = {false, false};
+};
+#define PG_METER_PUB_CHUNKS 64   // chunks of 1024 published levels: never moved or freed before the graph dies (read from any thread)
 
 // ---- the graph --------------------------------------------------------------------------------------------
 struct Event {  // MixerEvent (src/source/mixed.rs:47-109) resolved to a device command
@@ -351,6 +363,20 @@ struct pg_graph {
   int32_t* h_env_done = nullptr;
   size_t env_cap = 0;
   std::vector<int> env_voices;     // ids of the voices whose envelope is alive
+  // level metering (pg_graph_set_metering, pg_k_meter.hip)
+  bool metering = false;           // owner thread's view; meter_on is what pg_graph_mixer_audio_level reads from any thread
+  std::atomic<int> meter_on{0};
+  uint64_t meter_interval = 0;     // AudioLevelState::update_interval in frames
+  bool meter_fragile = false;      // some sub-mixer has neither effects nor sub-mixers: whether it records depends on its sources (rebuild_topology)
+  PgMeterState* d_meter_state = nullptr; size_t meter_cap = 0;        // per mixer id
+  int32_t* d_meter_seen = nullptr; size_t meter_seen_cap = 0;         // per voice (device index)
+  std::atomic<PgMeterPub*> meter_pub[PG_METER_PUB_CHUNKS] = {};       // pinned, published levels by mixer id
+  PgMeterPub* meter_pub_dev[PG_METER_PUB_CHUNKS] = {};                // ... their device addresses
+  pgc::ChunkTable<int8_t> mixer_alive_tab;                            // mixer id -> 1 until it is removed (readable from any thread)
+  MeterRing meter_ring;
+  std::vector<PgMeterJob> meter_jobs;    // the launch being put together (capacity kept across writes)
+  std::vector<PgMeterSpan> meter_spans;
+  std::vector<int> row_of_mixer;         // sub-mixer id -> its row of the per-unit output table (rebuild_topology)
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };
@@ -366,3 +392,8 @@ int graph_enqueue_status(pg_graph* g, hipStream_t stream);
 void graph_collect_status(pg_graph* g);
 size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t pos, hipStream_t stream, bool begin = true, size_t cap_frames = 0);
 int process_bus_impl(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_in_frames, hipStream_t s, int* bus_audible);
+// level metering (pg_k_meter.hip)
+int graph_meter_reserve(pg_graph* g);    // mutating calls, graph quiescent: may allocate
+void graph_meter_release(pg_graph* g);
+int graph_meter_launch(pg_graph* g, hipStream_t stream);   // g->meter_jobs / g->meter_spans -> one pg_meter_kernel launch
+int graph_meter_main(pg_graph* g, const float* d_ptr, uint64_t frames, uint64_t time, bool end_of_record, hipStream_t stream);

@@ -458,6 +458,23 @@ int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) {
   const int32_t pk = s->voice_map.get((size_t)voice_id);
   return pg_graph_voice_envelope_stage(s->shards[shard_of(pk)], local_of(pk));
 }
+// PlayerConfig::metering_interval for the one mixer: every shard meters its sub-mixers, the root the main mixer (pg_graph_set_metering)
+int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds) {
+  if (std::isnan(interval_seconds) || (std::isinf(interval_seconds) && interval_seconds > 0)) return set_error(PG_ERR_PARAMETER, "Invalid metering interval: %g", interval_seconds);
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  for (pg_graph* g : s->shards) { const int rc = pg_graph_set_metering(g, interval_seconds); if (rc) return rc; }
+  return PG_OK;
+}
+// A sub-mixer's level comes from its shard, mixer 0's from the root. Any thread, no HIP call (pg_graph_mixer_audio_level).
+int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_level* out) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!out) return set_error(PG_ERR_PARAMETER, "`out` must not be null");
+  if (mixer_id == 0) return pg_graph_mixer_audio_level(s->shards[0], 0, out);
+  if (!s->shards[0]->meter_on.load(std::memory_order_acquire)) return set_error(PG_ERR_STATE, "metering is off (pg_sharded_set_metering)");
+  if (mixer_id < 0 || (size_t)mixer_id >= s->mixer_map.size()) return set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  const int32_t pk = s->mixer_map.get((size_t)mixer_id);
+  return pg_graph_mixer_audio_level(s->shards[shard_of(pk)], local_of(pk), out);
+}
 int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id) {
   if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return 0;
   const int32_t pk = s->voice_map.get((size_t)voice_id);
@@ -601,6 +618,8 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
       if (stage_off + n * 2 > 2 * s->stage_frames) stage_off = 0;   // (the staging is a ring of spans: reuse is ordered by the `summed` event and the shards' own streams)
       float* dst = contiguous ? d_out + (size_t)(done + off) * 2 : d_out;
       if (sharded_render_segment(s, dst, contiguous ? stage_off : 0, (size_t)n * 2, now + off)) { s->failed = true; return 0; }
+      // mixer 0's level: measured on the root behind the bus chain, one record per write of the one mixer (a part per span)
+      if (s->shards[0]->metering && graph_meter_main(s->shards[0], dst, n, pos, done + off + n == frames, s->shards[0]->stream)) { s->failed = true; return 0; }
       if (span_done && span_done((size_t)(done + off) * 2, (size_t)n * 2)) { s->failed = true; return 0; }
       stage_off += (size_t)n * 2;
       off += n;

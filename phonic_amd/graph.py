@@ -223,6 +223,15 @@ class ShardedGraph:
     def voice_envelope_stage(self, voice):
         return int(self._lib.pg_sharded_voice_envelope_stage(self._h, voice))
 
+    def set_metering(self, interval_seconds):
+        """PlayerConfig::metering_interval on every shard (None: off); mixer 0 is metered on the root behind the bus chain."""
+        self._check(self._lib.pg_sharded_set_metering(self._h, -1.0 if interval_seconds is None else float(interval_seconds)))
+
+    def audio_level(self, mixer_id=0):
+        raw = _capi.AudioLevel()
+        self._check(self._lib.pg_sharded_mixer_audio_level(self._h, mixer_id, C.byref(raw)))
+        return _capi.Level(raw)
+
     def set_voice_speed(self, voice, speed, sample_time, glide=None):
         self._check(self._lib.pg_sharded_set_voice_speed(self._h, voice, float(speed), float(glide) if glide else 0.0, sample_time))
 
