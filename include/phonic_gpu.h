@@ -291,6 +291,72 @@ int pg_graph_release_voice(pg_graph* g, int voice_id, uint64_t sample_time);
  * gone). Waits for the graph's stream: call it after pg_graph_write / a synchronize. */
 int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
 
+/* Granular playback voices: a sampler voice in granular mode — GrainPool<100> (src/generator/sampler/granular.rs) driven as
+ * SamplerVoice::process drives it (src/generator/sampler/voice.rs:406-432). Rendered on the device by pg_grain_kernel ("Granular
+ * voices"); each grain's per-frame stereo terms are the reference's bits, the f32 sum over the grains of a frame runs in ascending slot order.
+ * OUT OF SCOPE: the modulation matrix (every `*_mod` input of try_trigger_grain / advance_playhead is 0.0 — what a sampler without routings
+ * feeds); the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the mono down-mix and resample of
+ * create_granular_sample_buffer (sampler.rs:908-952: the caller hands over the mono f32 buffer at the graph's rate that function would have
+ * produced); changing granular parameters after the voice has started.
+ * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
+ * 2 Triangle, 3 Tukey, 4 Trapezoid, 5 Exponential, 6 RampUp, 7 RampDown (:61-70); size in ms, density in Hz, playback_direction 0 Forward,
+ * 1 Backward, 2 Random (:19-26); plus GrainPool::sample_loop_range (:357, voice.rs:355-360) as has_loop_range / loop_start / loop_end,
+ * normalised to [0, 1]. rng_state: the pool seeds its SmallRng from the OS (granular.rs:410) — here the state is an input, by the rule of
+ * pg_effect_init::lfo_rng_state above: Xoshiro256++, an all-zero state means SplitMix64(0x5EED0000) x 4. The draws are rand 0.9's:
+ * random::<f32>() = (next_u64 >> 40) * 2^-24, random::<f64>() = (next_u64 >> 11) * 2^-53, random::<bool>() = the top bit of next_u64 — these
+ * three definitions are taken from rand's documentation and are UNVERIFIED against the crate (its source is not part of this project).
+ * The window tables' cos / exp and the pitch variation's 2^x are the correctly rounded values, where a libm may be an ulp off. */
+typedef struct pg_granular_params {
+  int32_t overlap_mode, window;
+  float size, density, variation, spray, pan_spread;
+  int32_t playback_direction;
+  float position, step;
+  int32_t has_loop_range;
+  float loop_start, loop_end;
+  int32_t reserved;
+  uint64_t rng_state[4];
+} pg_granular_params;
+/* GranularParameters::default (granular.rs:268-283): Cloud, Triangle, 100 ms, 10 Hz, no variation / spray / pan spread, Forward, position 0.5,
+ * step 0; no loop range, rng_state 0 */
+void pg_granular_params_default(pg_granular_params* p);
+/* GranularParameters::validate (granular.rs:291-335): size 1..1000, density 1..100, spray / variation / pan_spread / position 0..1, step -4..4;
+ * also 0 <= loop_start, loop_end <= 1 (GrainPool::new's assertion, :393-398), enum fields in range, `p` not null. PG_OK or PG_ERR_PARAMETER;
+ * touches no graph and no device. */
+int pg_granular_params_check(const pg_granular_params* p);
+/* A sampler voice in granular mode on mixer `mixer_id`: `mono_pcm` = n_frames >= 1 mono f32 frames at the graph's rate (copied to the device).
+ * opt->volume / panning / speed become GrainPool::start(parameters, speed, volume, panning) (granular.rs:474-489); as in the reference's granular
+ * branch the output does NOT pass the amplified / panned / fader stages (voice.rs:412-427): volume and panning act through the grains only.
+ * opt->start_time works as for file voices; the other options are not used. Returns a voice id >= 0. On such a voice:
+ *  - pg_graph_set_voice_volume / _panning / _speed are GrainPool::set_volume / set_panning / set_speed (granular.rs:504-514) at the exact frame,
+ *    not smoothed: they reach the grains activated from that frame on (:824-831, :857); a glide is ignored (SamplerVoice::set_speed);
+ *  - pg_graph_stop_voice, and pg_graph_release_voice without an envelope, are GrainPool::stop() (:491-493): no new grains; the voice ends with
+ *    the chunk (the source's process call) in which the pool became exhausted (:442-444, voice.rs:488-495), which it writes in full;
+ *  - pg_graph_set_voice_envelope works as for any voice (before the first frame); then pg_graph_release_voice is the envelope's note_off and the
+ *    voice ends on Idle or on exhaustion, whichever comes first;
+ *  - pg_graph_seek_voice returns PG_ERR_STATE.
+ * A unit that holds a living granular voice is rendered by the exact kernel, which takes pg_grain_kernel's frames as the voice's source output. */
+int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt);
+/* Debug read-back of a granular voice's GrainPool (granular.rs:345-377) and its 100 Grain records (:961-985). Waits for the graph's stream.
+ * PG_ERR_NOT_FOUND: not a granular voice. */
+#define PG_GRAIN_POOL_SIZE 100
+typedef struct pg_grain_slot {
+  double position, increment, window_phase, window_increment;
+  uint64_t samples_remaining;
+  float volume, panning;
+  int32_t active, window_mode, has_loop_range, reserved;
+} pg_grain_slot;
+typedef struct pg_grain_state {
+  float trigger_phase, playhead;
+  int32_t playing_loop_range, trigger_new_grains;
+  int32_t primary_slot;      /* primary_grain_index, -1: None */
+  int32_t reserved;
+  double speed;
+  float volume, panning;
+  uint64_t rng_state[4];
+  pg_grain_slot slots[PG_GRAIN_POOL_SIZE];
+} pg_grain_state;
+int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out);
+
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and
  * RMS (AudioLevel, src/source/metered.rs), linear. The meter runs on the device (pg_meter_kernel: the sub-mixers' samples never leave it).
@@ -450,6 +516,10 @@ int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id);
 int pg_sharded_set_voice_envelope(pg_sharded_graph* s, int voice_id, const pg_ahdsr_params* p);
 int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time);
 int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id);
+/* pg_graph_add_granular_voice / _voice_grain_state (src/generator/sampler/granular.rs, src/generator/sampler/voice.rs:406-432) on the voice's shard;
+ * volume, panning, speed, stop, release, envelope and seek reach a granular voice through the calls above, as on the plain graph */
+int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt);
+int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out);
 /* pg_graph_set_metering / pg_graph_mixer_audio_level on the one mixer: a sub-mixer's level comes from its shard; mixer 0's is measured on the root
  * behind the bus chain, one record per pg_sharded_write* call (src/source/metered.rs:75-143) */
 int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds);

@@ -116,6 +116,79 @@ def ahdsr_params(**kw):
     return p
 
 
+class GranularParams(C.Structure):
+    """pg_granular_params: GranularParameters (reference src/generator/sampler/granular.rs:241-266) + the pool's normalised loop range + the
+    Xoshiro256++ state of its SmallRng."""
+    _fields_ = [("overlap_mode", C.c_int32), ("window", C.c_int32), ("size", C.c_float), ("density", C.c_float), ("variation", C.c_float), ("spray", C.c_float),
+                ("pan_spread", C.c_float), ("playback_direction", C.c_int32), ("position", C.c_float), ("step", C.c_float), ("has_loop_range", C.c_int32),
+                ("loop_start", C.c_float), ("loop_end", C.c_float), ("reserved", C.c_int32), ("rng_state", C.c_uint64 * 4)]
+
+
+GRAIN_POOL_SIZE = 100
+GRAIN_CLOUD, GRAIN_SEQUENTIAL = 0, 1
+GRAIN_FORWARD, GRAIN_BACKWARD, GRAIN_RANDOM = 0, 1, 2
+GRAIN_WINDOWS = ("Hann", "Blackman", "Triangle", "Tukey", "Trapezoid", "Exponential", "RampUp", "RampDown")
+
+
+def granular_params(loop_range=None, rng_state=None, **kw):
+    """GranularParameters::default() (granular.rs:268-283) with overrides; loop_range = (start, end) normalised; rng_state = four u64."""
+    p = GranularParams()
+    load().pg_granular_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in ("overlap_mode", "window", "size", "density", "variation", "spray", "pan_spread", "playback_direction", "position", "step"):
+            raise AttributeError(k)
+        setattr(p, k, int(v) if k in ("overlap_mode", "window", "playback_direction") else float(v))
+    if loop_range is not None:
+        p.has_loop_range, p.loop_start, p.loop_end = 1, float(loop_range[0]), float(loop_range[1])
+    if rng_state is not None:
+        for i in range(4):
+            p.rng_state[i] = int(rng_state[i])
+    return p
+
+
+class GrainSlot(C.Structure):
+    """pg_grain_slot: Grain (granular.rs:961-985)."""
+    _fields_ = [("position", C.c_double), ("increment", C.c_double), ("window_phase", C.c_double), ("window_increment", C.c_double), ("samples_remaining", C.c_uint64),
+                ("volume", C.c_float), ("panning", C.c_float), ("active", C.c_int32), ("window_mode", C.c_int32), ("has_loop_range", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GrainState(C.Structure):
+    """pg_grain_state: the GrainPool's scalars and its 100 grains."""
+    _fields_ = [("trigger_phase", C.c_float), ("playhead", C.c_float), ("playing_loop_range", C.c_int32), ("trigger_new_grains", C.c_int32), ("primary_slot", C.c_int32),
+                ("reserved", C.c_int32), ("speed", C.c_double), ("volume", C.c_float), ("panning", C.c_float), ("rng_state", C.c_uint64 * 4), ("slots", GrainSlot * GRAIN_POOL_SIZE)]
+
+
+def grain_state_dict(st):
+    """A GrainState as numpy arrays / scalars (the layout tests/granular_model.py's GrainPool.state() uses)."""
+    import numpy as np
+
+    slots = st.slots
+    col = lambda name, dt: np.array([getattr(slots[i], name) for i in range(GRAIN_POOL_SIZE)], dtype=dt)
+    return {
+        "trigger_phase": np.float32(st.trigger_phase), "playhead": np.float32(st.playhead), "playing_loop_range": int(st.playing_loop_range),
+        "trigger_new_grains": int(st.trigger_new_grains), "primary": int(st.primary_slot), "speed": float(st.speed), "volume": np.float32(st.volume),
+        "panning": np.float32(st.panning), "rng": tuple(int(x) for x in st.rng_state),
+        "active": col("active", np.int32), "samples_remaining": col("samples_remaining", np.int64), "position": col("position", np.float64),
+        "increment": col("increment", np.float64), "window_phase": col("window_phase", np.float64), "window_increment": col("window_increment", np.float64),
+        "volume_g": col("volume", np.float32), "panning_g": col("panning", np.float32), "window_mode": col("window_mode", np.int32),
+        "has_loop": col("has_loop_range", np.int32),
+    }
+
+
+def mono_downmix(pcm, channels):
+    """The down-mix of Sampler::create_granular_sample_buffer (sampler.rs:940-943) for a buffer that is already at the graph's rate: per frame, the f32
+    sum of the channels in order, divided by the channel count."""
+    import numpy as np
+
+    pcm = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1, channels)
+    if channels == 1:
+        return pcm.reshape(-1).copy()
+    acc = np.zeros(pcm.shape[0], dtype=np.float32)
+    for c in range(channels):
+        acc = (acc + pcm[:, c]).astype(np.float32)
+    return (acc / np.float32(channels)).astype(np.float32)
+
+
 def make_init(params=None, reverb_seeds=None, lfo_seed=None):
     """Build a pg_effect_init. params: dict {fourcc-str: raw value}; reverb_seeds: (fpd_l, fpd_r, [16 phases]); lfo_seed: the four u64 of the
     Delay LFO's Xoshiro256++ state (Random / Smooth Random shapes)."""
@@ -324,6 +397,17 @@ def load():
         fn = getattr(lib, prefix + "mixer_audio_level")
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int, P(AudioLevel)]
+    lib.pg_granular_params_default.restype = None
+    lib.pg_granular_params_default.argtypes = [P(GranularParams)]
+    lib.pg_granular_params_check.restype = C.c_int
+    lib.pg_granular_params_check.argtypes = [P(GranularParams)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        fn = getattr(lib, prefix + "add_granular_voice")
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int, P(C.c_float), C.c_size_t, P(GranularParams), P(VoiceOptions)]
+        fn = getattr(lib, prefix + "voice_grain_state")
+        fn.restype = C.c_int
+        fn.argtypes = [vp, C.c_int, P(GrainState)]
     lib.pg_graph_kernel_ms.restype = C.c_double
     lib.pg_graph_kernel_ms.argtypes = [vp, C.c_int, P(C.c_uint64)]
     lib.pg_graph_kernel_stats.restype = C.c_int

@@ -140,6 +140,21 @@ class GraphHandle:
             self._fn("graph_add_voice")(self._h, mixer_id, _f32p(pcm), pcm.size // src_channels, src_channels, src_rate, C.byref(o))
         )
 
+    def add_granular_voice(self, mixer_id, pcm, params=None, channels=1, **opts):
+        """A sampler voice in granular mode (GrainPool, src/generator/sampler/granular.rs): `pcm` at the graph's rate, mono — or `channels`
+        interleaved channels, mixed down as Sampler::create_granular_sample_buffer does. `params`: a _capi.GranularParams (see
+        _capi.granular_params); opts: volume, panning, speed, start_time."""
+        mono = _capi.mono_downmix(pcm, channels)
+        p = params if params is not None else _capi.granular_params()
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._fn("graph_add_granular_voice")(self._h, mixer_id, _f32p(mono), mono.size, C.byref(p), C.byref(o)))
+
+    def voice_grain_state(self, voice):
+        """The voice's GrainPool and its 100 grains as a dict (debug read-back: waits for the graph's stream)."""
+        st = _capi.GrainState()
+        self._check(self._fn("graph_voice_grain_state")(self._h, voice, C.byref(st)))
+        return _capi.grain_state_dict(st)
+
     def stop_all_voices(self):
         """Player::stop_all_sources (src/player.rs:1012-1045)."""
         self._check(self._fn("graph_stop_all_voices")(self._h))

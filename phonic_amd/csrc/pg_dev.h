@@ -240,11 +240,60 @@ struct PgEnv {
 };
 // The side table in device memory: this header, then one PgEnv per voice, indexed like PgLaunch::voices. `done`: one word per voice in mapped
 // host memory that the exact kernel sets when an enveloped voice has ended — the host then takes the voice's unit off the exact kernel again.
+struct PgGrainVoice;
 struct PgEnvTable {
   int32_t* done;
   uint64_t cap;         // entries behind the header: the kernel takes no entry at or beyond it
+  // granular voices (pg_graph_add_granular_voice): the per-voice side table travels behind the same word of PgLaunch. grain_of_voice[v] (v < cap):
+  // index of voice v's record in `grains`, -1 for every other voice; nullptr: the graph never had a granular voice.
+  const int32_t* grain_of_voice;
+  PgGrainVoice* grains;
+  uint32_t n_grains;    // records `grains` holds: no record at or beyond it is taken
+  uint32_t pad_grains[3];
 };
-static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 16, "the entries follow the header, 16-byte aligned");
+static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 48, "the entries follow the header, 16-byte aligned");
+
+// ---- granular voices: GrainPool<100> of a sampler voice (src/generator/sampler/granular.rs), see pg_grain_dev.h / pg_k_grain.hip ----
+#define PG_GRAIN_POOL 100      // Sampler's GrainPool<100>: concurrent grains of one voice
+#define PG_GRAIN_LUT_N 2048    // GRAIN_WINDOW_LUT: GrainWindow<2048> (granular.rs:221)
+#define PG_GRAIN_WINDOWS 8     // GrainWindowMode::COUNT
+struct PgGrain {               // Grain (granular.rs:961-985)
+  double position, increment, window_phase, window_increment;
+  double loop_start, loop_end;         // loop_range: Some((start, end)) when has_loop
+  uint64_t samples_remaining;
+  float volume, panning;
+  int32_t active, window_mode, has_loop, pad;
+};
+struct PgGrainPool {           // the mutable scalars of GrainPool (granular.rs:345-377)
+  uint64_t rng[4];             // SmallRng = Xoshiro256++
+  double speed;
+  float trigger_phase, playhead, volume, panning;
+  int32_t playing_loop_range, trigger_new_grains, primary /* primary_grain_index, -1: None */, pad;
+};
+struct PgGrainParams {         // GranularParameters (granular.rs:241-266) + GrainPool::sample_loop_range; fixed once the voice exists
+  int32_t overlap_mode, window;
+  float size, density, variation, spray, pan_spread;
+  int32_t direction;
+  float position, step;
+  int32_t has_loop;
+  float loop_start, loop_end;
+  int32_t pad;
+};
+struct PgGrainVoice {
+  PgGrainParams params;
+  PgGrainPool pool;
+  const float* pcm;            // GrainPool::sample_buffer: mono f32 at the graph's rate
+  uint64_t n_frames;
+  float* staged;               // PG_MAX_FRAMES interleaved stereo frames: what pg_grain_kernel rendered of the main mixer's current chunk ...
+  uint64_t stage_pos;          // ... whose frame 0 is this position
+  uint64_t start_time;         // the voice's start time: no frame in front of it is rendered
+  uint64_t stop_time;          // StopSource: GrainPool::stop() in front of the first frame at or behind it (UINT64_MAX: none)
+  uint64_t exhausted_at;       // position of the frame behind which GrainPool::is_exhausted() first held (UINT64_MAX: not yet)
+  int32_t voice;               // device index of the voice (PgLaunch::voices)
+  int32_t has_env;             // the voice has a volume envelope: CMD_VOICE_RELEASE is its note_off, not a stop
+  PgGrain grains[PG_GRAIN_POOL];
+};
+static_assert(sizeof(PgGrain) == 80 && sizeof(PgGrainPool) == 72 && sizeof(PgGrainParams) == 56 && sizeof(PgGrainVoice) % 8 == 0, "host and device agree on the layout");
 
 // Parameter indices per effect kind = order of `Effect::parameters()` in the reference.
 enum { P_GAIN_GAIN = 0, P_GAIN_DCFM };

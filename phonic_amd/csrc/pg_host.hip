@@ -115,7 +115,8 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
       if (m != 0 && k == PG_FX_GAIN && (int)g->fx[f]->init_raw[1] != 0) g->wide = true;  // DC filter: blocked scan, compiled into the wide variants only
     }
     // a living voice with a volume envelope: the exact kernel renders it (pg_graph_set_voice_envelope); the mixer's other units keep their kernels
-    if (m != 0) for (int v : mx.voices) if (g->voices[v].env_live) u.static_defer = 1;
+    // (a living granular voice too: the exact kernel's source stage takes what pg_grain_kernel rendered)
+    if (m != 0) for (int v : mx.voices) if (g->voices[v].env_live || g->voices[v].gran_live) u.static_defer = 1;
     // staged pipeline: a sub-mixer whose chain is [Gain (no DC filter) | Panning]* -> Reverb
     u.staged = 0;
     if (m != 0 && !u.static_defer && !mx.fx.empty() && g->fx[mx.fx.back()]->kind == PG_FX_REVERB) {
@@ -164,7 +165,7 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
     int slot = g->source_unit_of_voice[v];
     PgUnit& u = topo[slot];
     u.voice_off = (int)vidx.size(); u.n_voices = 1; u.n_fx = 0; u.fx_off = 0;
-    u.static_defer = g->voices[v].env_live ? 1 : 0;
+    u.static_defer = (g->voices[v].env_live || g->voices[v].gran_live) ? 1 : 0;
     if (g->voices[v].outer) g->any_outer = true;
     u.voice0 = g->voices[v].dev_index;
     vidx.push_back(g->voices[v].dev_index);
@@ -235,24 +236,90 @@ static int graph_env_reserve(pg_graph* g, size_t n) {
   PgEnvTable* nt = nullptr;
   int32_t* nh = nullptr;
   int32_t* ndd = nullptr;
+  int32_t* ngv = nullptr;   // PgEnvTable::grain_of_voice: -1 for every voice that is not granular
   HIP_TRY(pg_malloc((void**)&nt, sizeof(PgEnvTable) + cap * sizeof(PgEnv)));
   PgEnv* const nd = (PgEnv*)(nt + 1);
   if (pg_memset(nt, 0, sizeof(PgEnvTable) + cap * sizeof(PgEnv)) != hipSuccess || pg_host_malloc((void**)&nh, cap * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { (void)pg_free(nt); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
   memset(nh, 0, cap * sizeof(int32_t));
-  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
+  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess || pg_malloc((void**)&ngv, cap * sizeof(int32_t)) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
+  auto undo = [&]() { (void)pg_free(nt); (void)pg_host_free(nh); (void)pg_free(ngv); };
+  if (pg_memset(ngv, 0xff, cap * sizeof(int32_t)) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
   PgEnvTable head;
+  memset(&head, 0, sizeof head);
   head.done = ndd; head.cap = cap;
-  if (pg_memcpy(nt, &head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table upload failed"); }
+  head.grain_of_voice = ngv; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
+  if (pg_memcpy(nt, &head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table upload failed"); }
   PgEnvTable* const old_tab = g->d_env_tab;
   int32_t* const old_done = g->h_env_done;
+  int32_t* const old_gv = g->d_grain_of_voice;
   if (g->d_env) {
-    if (pg_memcpy(nd, g->d_env, g->env_cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table copy failed"); }
+    if (pg_memcpy(nd, g->d_env, g->env_cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess ||
+        pg_memcpy(ngv, old_gv, g->env_cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table copy failed"); }
     memcpy(nh, g->h_env_done, g->env_cap * sizeof(int32_t));
   }
   // (the new table is complete: swap first, then let go of the old one — a failure above leaves the graph on its old table)
-  g->d_env_tab = nt; g->d_env = nd; g->h_env_done = nh; g->env_cap = cap;
+  g->d_env_tab = nt; g->d_env = nd; g->h_env_done = nh; g->env_cap = cap; g->d_grain_of_voice = ngv;
   if (old_tab) (void)pg_free(old_tab);
   if (old_done) (void)pg_host_free(old_done);
+  if (old_gv) (void)pg_free(old_gv);
+  return PG_OK;
+}
+// Room for `n` granular records, their `ended` words and their launch list; the window tables with the first one. The graph is quiescent.
+static int graph_gran_reserve(pg_graph* g, size_t n) {
+  if (!g->d_grain_lut) {
+    std::vector<float> lut((size_t)PG_GRAIN_WINDOWS * PG_GRAIN_LUT_N);
+    pg_grain_build_lut(lut.data());
+    HIP_TRY(pg_malloc((void**)&g->d_grain_lut, lut.size() * sizeof(float)));
+    HIP_TRY(pg_memcpy(g->d_grain_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  int rc;
+  if ((rc = g->d_gran_live.reserve(std::max<size_t>(next_pow2(n), 16)))) return rc;
+  if (n <= g->gran_cap) return PG_OK;
+  const size_t cap = std::max<size_t>(next_pow2(n), 16);
+  PgGrainVoice* nd = nullptr;
+  int32_t* nh = nullptr;
+  int32_t* ndd = nullptr;
+  HIP_TRY(pg_malloc((void**)&nd, cap * sizeof(PgGrainVoice)));
+  if (pg_host_malloc((void**)&nh, cap * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { (void)pg_free(nd); return set_error(PG_ERR_DEVICE, "granular table allocation failed"); }
+  memset(nh, 0, cap * sizeof(int32_t));
+  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess ||
+      (g->gran_n && pg_memcpy(nd, g->d_gran, g->gran_n * sizeof(PgGrainVoice), hipMemcpyDeviceToDevice) != hipSuccess)) { (void)pg_free(nd); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "granular table allocation failed"); }
+  if (g->gran_n) memcpy(nh, g->h_gran_ended, g->gran_n * sizeof(int32_t));
+  if (g->d_gran) (void)pg_free(g->d_gran);
+  if (g->h_gran_ended) (void)pg_host_free(g->h_gran_ended);
+  g->d_gran = nd; g->h_gran_ended = nh; g->d_gran_ended = ndd; g->gran_cap = cap;
+  return PG_OK;
+}
+// The granular fields of the envelope table's header, as the graph holds them now (the graph is quiescent).
+static int graph_gran_publish(pg_graph* g) {
+  PgEnvTable head;
+  memset(&head, 0, sizeof head);
+  HIP_TRY(pg_memcpy(&head, g->d_env_tab, sizeof head, hipMemcpyDeviceToHost));
+  head.grain_of_voice = g->d_grain_of_voice; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
+  HIP_TRY(pg_memcpy(g->d_env_tab, &head, sizeof head, hipMemcpyHostToDevice));
+  return PG_OK;
+}
+// Granular voices pg_grain_kernel has reported as ended (or that left the graph): they leave its launch list, and their units go back to the
+// time-parallel kernels with the next topology upload. Reads mapped host words: no wait.
+static void graph_poll_granular(pg_graph* g) {
+  for (size_t i = 0; i < g->gran_voices.size();) {
+    HostVoice& hv = g->voices[g->gran_voices[i]];
+    if (hv.mixer < 0 || *(volatile int32_t*)(g->h_gran_ended + hv.gran) != 0) {
+      hv.gran_live = false;
+      g->gran_voices.erase(g->gran_voices.begin() + i);
+      g->topo_dirty = true; g->gran_live_dirty = true;
+    } else ++i;
+  }
+}
+// pg_grain_kernel for frames [t0, t0 + n) of the chunk that began at chunk_t0, in front of the unit kernels that take its frames.
+static int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
+  if (g->gran_voices.empty()) return PG_OK;
+  PgGrainLaunch L;
+  memset(&L, 0, sizeof L);
+  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gran_voices.size(); L.live = g->d_gran_live.d;
+  L.voices = g->d_voices.d; L.cmds = d_cmds; L.n_cmds = n_cmds; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->d_gran_ended;
+  L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
+  HIP_TRY(pg_launch_grain(L, stream));
   return PG_OK;
 }
 // Enveloped voices the exact kernel has reported as ended (or that left the graph): their units go back to the time-parallel kernels with the
@@ -426,6 +493,11 @@ void pg_graph_destroy(pg_graph* g) {
   if (g->h_feedback) (void)pg_host_free(g->h_feedback);
   if (g->d_env_tab) (void)pg_free(g->d_env_tab);
   if (g->h_env_done) (void)pg_host_free(g->h_env_done);
+  if (g->d_grain_of_voice) (void)pg_free(g->d_grain_of_voice);
+  if (g->d_gran) (void)pg_free(g->d_gran);
+  if (g->d_grain_lut) (void)pg_free(g->d_grain_lut);
+  if (g->h_gran_ended) (void)pg_host_free(g->h_gran_ended);
+  g->d_gran_live.release();
   graph_meter_release(g);
   for (auto& e : g->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_bus_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -827,6 +899,7 @@ static int fx_kind_of(pg_graph* g, int effect_id) {  // -1: unknown or removed
 static bool voice_alive(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) != 0; }
 // Seek and speed exist on FilePlaybackHandle only (src/player/handles/file.rs): a host-fed source (the host's own `dyn Source` behind a ring) has
 // neither a position to seek to nor a resampler to re-target — the device would rewind the ring's read position over stale frames.
+static bool voice_is_granular(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 3; }
 static bool voice_is_host_fed(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 2; }
 
 int pg_graph_schedule_param(pg_graph* g, int effect_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
@@ -868,6 +941,7 @@ int pg_graph_set_voice_speed(pg_graph* g, int voice_id, double speed, float glid
 int pg_graph_seek_voice(pg_graph* g, int voice_id, double position_seconds, uint64_t sample_time) {
   if (!(position_seconds >= 0.0)) return set_error(PG_ERR_PARAMETER, "seek position must be >= 0");
   if (voice_is_host_fed(g, voice_id)) return set_error(PG_ERR_PARAMETER, "Source with id %d is host-fed: it takes volume, panning and stop only", voice_id);
+  if (voice_is_granular(g, voice_id)) return set_error(PG_ERR_STATE, "Source with id %d is a granular voice: its grains have positions of their own, there is nothing to seek", voice_id);
   return voice_message(g, voice_id, pgc::CT_VOICE_SEEK, 0.0f, position_seconds, sample_time);
 }
 int pg_graph_stop_voice(pg_graph* g, int voice_id, uint64_t sample_time) {  // MixerMessage::StopSource (mixed.rs:389-400): not an event
@@ -927,6 +1001,10 @@ int pg_graph_set_voice_envelope(pg_graph* g, int voice_id, const pg_ahdsr_params
   (void)hipSetDevice(g->device);
   HIP_TRY(pg_memcpy(g->d_env + hv.dev_index, &e, sizeof e, hipMemcpyHostToDevice));
   g->h_env_done[hv.dev_index] = 0;
+  if (hv.gran >= 0) {  // pg_grain_kernel: a release is the envelope's note_off from here on, not GrainPool::stop
+    const int32_t one = 1;
+    HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, has_env), &one, sizeof one, hipMemcpyHostToDevice));
+  }
   if (!hv.env_live) g->env_voices.push_back(voice_id);
   hv.env = true; hv.env_live = true;
   g->topo_dirty = true;
@@ -940,6 +1018,136 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id) {
   PgEnv e;
   if (pg_memcpy(&e, g->d_env + g->voices[voice_id].dev_index, sizeof e, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return e.on ? (int)e.state.stage : -1;
+}
+// ---- granular voices (src/generator/sampler/granular.rs; pg_k_grain.hip) ----
+void pg_granular_params_default(pg_granular_params* p) {  // GranularParameters::default (granular.rs:268-283)
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->overlap_mode = 0; p->window = 2; p->size = 100.0f; p->density = 10.0f; p->playback_direction = 0; p->position = 0.5f;
+}
+int pg_granular_params_check(const pg_granular_params* p) {  // GranularParameters::validate (granular.rs:291-335); a NaN fails every range
+  if (!p) return set_error(PG_ERR_PARAMETER, "granular parameters must not be null");
+  if (p->overlap_mode < 0 || p->overlap_mode > 1) return set_error(PG_ERR_PARAMETER, "Invalid grain overlap mode: %d", p->overlap_mode);
+  if (p->window < 0 || p->window >= PG_GRAIN_WINDOWS) return set_error(PG_ERR_PARAMETER, "Invalid grain window mode: %d", p->window);
+  if (p->playback_direction < 0 || p->playback_direction > 2) return set_error(PG_ERR_PARAMETER, "Invalid grain playback direction: %d", p->playback_direction);
+  if (!(p->size >= 1.0f && p->size <= 1000.0f)) return set_error(PG_ERR_PARAMETER, "Grain size must be between 1 and 1000 ms");
+  if (!(p->density >= 1.0f && p->density <= 100.0f)) return set_error(PG_ERR_PARAMETER, "Grain density must be between 1.0 and 100.0 Hz");
+  if (!(p->spray >= 0.0f && p->spray <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain spray must be between 0.0 and 1.0");
+  if (!(p->variation >= 0.0f && p->variation <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain variation must be between 0.0 and 1.0");
+  if (!(p->pan_spread >= 0.0f && p->pan_spread <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain pan spread must be between 0.0 and 1.0");
+  if (!(p->position >= 0.0f && p->position <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Position must be between 0.0 and 1.0");
+  if (!(p->step >= -4.0f && p->step <= 4.0f)) return set_error(PG_ERR_PARAMETER, "Step must be between -4.0 and 4.0");
+  if (p->has_loop_range && !(p->loop_start >= 0.0f && p->loop_start <= 1.0f && p->loop_end >= 0.0f && p->loop_end <= 1.0f))
+    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)p->loop_start, (double)p->loop_end);
+  return PG_OK;
+}
+int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!mono_pcm || n_frames < 1) return -set_error(PG_ERR_PARAMETER, "Need a valid, non empty sample buffer");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  drain_control_messages(g);
+  pg_voice_options def;
+  if (!opt) { pg_voice_options_default(&def); opt = &def; }
+  if (!(opt->speed > 0.0)) return -set_error(PG_ERR_PARAMETER, "speed must be > 0");
+  if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  // the voice as the mixer sees it: a stereo source at the graph's rate whose frames pg_grain_kernel renders; AmplifiedSource / PannedSource /
+  // fader are neutral — the granular branch of SamplerVoice::process does not pass them (voice.rs:412-427)
+  PgVoice v;
+  memset(&v, 0, sizeof v);
+  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
+  v.fader_state = 0; v.fader_current = 1.0f; v.fader_target = 1.0f; v.fader_inertia = 1.0f;
+  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};
+  v.volume = make_smooth(exp_spec, 1.0f, g->sample_rate);
+  v.panning = make_smooth(exp_spec, 0.0f, g->sample_rate);
+  v.start_time = opt->start_time;
+  v.active = 1;
+  v.persistent = opt->non_transient != 0;
+  v.current_speed = 1.0; v.target_speed = 1.0;
+  v.sched_class = -1;
+  void* d_pcm = nullptr;
+  void* d_stage = nullptr;
+  auto release = [&]() { if (d_pcm) (void)pg_free(d_pcm); if (d_stage) (void)pg_free(d_stage); };
+  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
+  if (pg_malloc(&d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      pg_malloc(&d_stage, stage_bytes) != hipSuccess || pg_memset(d_stage, 0, stage_bytes) != hipSuccess) {
+    release();
+    return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice allocation failed"));
+  }
+  if (graph_gran_reserve(g, g->gran_n + 1)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  int dev_index = -1;
+  int rc = g->d_voices.push(v, &dev_index);
+  if (rc) { release(); return -graph_fail(g, rc); }
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + 1, (size_t)dev_index + 1))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  // GrainPool::new + start(parameters, speed, volume, panning) (granular.rs:384-429, :474-489)
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  memset(r.get(), 0, sizeof(PgGrainVoice));
+  PgGrainParams& q = r->params;
+  q.overlap_mode = p->overlap_mode; q.window = p->window; q.size = p->size; q.density = p->density; q.variation = p->variation; q.spray = p->spray;
+  q.pan_spread = p->pan_spread; q.direction = p->playback_direction; q.position = p->position; q.step = p->step;
+  q.has_loop = p->has_loop_range ? 1 : 0; q.loop_start = p->has_loop_range ? p->loop_start : 0.0f; q.loop_end = p->has_loop_range ? p->loop_end : 0.0f;
+  PgGrainPool& pool = r->pool;
+  if ((p->rng_state[0] | p->rng_state[1] | p->rng_state[2] | p->rng_state[3]) != 0) memcpy(pool.rng, p->rng_state, sizeof pool.rng);
+  else { uint64_t z = 0x5EED0000ull; for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; pool.rng[i] = x ^ (x >> 31); } }
+  pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
+  pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
+  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1;
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
+  r->pcm = (const float*)d_pcm; r->n_frames = n_frames; r->staged = (float*)d_stage; r->stage_pos = 0;
+  r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
+  const int rec = (int)g->gran_n;
+  const int32_t rec32 = rec;
+  (void)hipSetDevice(g->device);
+  if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
+      pg_memcpy(g->d_grain_of_voice + dev_index, &rec32, sizeof rec32, hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
+  g->h_gran_ended[rec] = 0;
+  g->gran_n += 1;
+  if (graph_gran_publish(g)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  const int id = (int)g->voices.size();
+  HostVoice hv;
+  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_pcm; hv.d_stage = d_stage;
+  hv.transient = opt->non_transient == 0; hv.gran = rec; hv.gran_live = true;
+  g->voices.push_back(hv);
+  g->gran_voices.push_back(id); g->gran_live_dirty = true;
+  g->source_unit_of_voice.push_back(-1);
+  // AddSource: sort by start time, insert BEFORE equal start times (mixed.rs:324-329)
+  HostMixer& mx = g->mixers[mixer_id];
+  size_t pos = 0;
+  while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
+  mx.voices.insert(mx.voices.begin() + pos, id);
+  if (mixer_id == 0) {
+    int slot = new_unit(g, UNIT_SOURCE);
+    if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
+    g->source_unit_of_voice[id] = slot;
+    g->main_active_voices += 1;
+    g->ever_had_main_voice = true;
+  }
+  if (!g->voice_alive_tab.append(3)) return -set_error(PG_ERR_STATE, "too many voices");   // (3: alive and granular — no seek)
+  g->topo_dirty = true;
+  if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  return id;
+}
+int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_stream_sync(g->stream));
+  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  HIP_TRY(pg_memcpy(r.get(), g->d_gran + g->voices[voice_id].gran, sizeof(PgGrainVoice), hipMemcpyDeviceToHost));
+  memset(out, 0, sizeof *out);
+  const PgGrainPool& pool = r->pool;
+  out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
+  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
+  memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) {
+    const PgGrain& s = r->grains[i];
+    pg_grain_slot& o = out->slots[i];
+    o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
+    o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
+  }
+  return PG_OK;
 }
 int pg_graph_remove_voice(pg_graph* g, int voice_id) {  // MixerMessage::RemoveSource (mixed.rs:149-151,400-402)
   const int rc = voice_message(g, voice_id, pgc::CT_VOICE_REMOVE, 0.0f, 0.0, 0);
@@ -1662,7 +1870,14 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
   g->last_stream = stream;
   if (begin) { graph_begin_write(g, pos); g->call_end = pos + n_samples / 2; }
   if (!g->env_voices.empty()) graph_poll_envelopes(g);
+  if (!g->gran_voices.empty()) graph_poll_granular(g);
   if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return 0; } }
+  if (g->gran_live_dirty) {  // the records pg_grain_kernel renders from here on
+    std::vector<int32_t> live;
+    for (int id : g->gran_voices) live.push_back(g->voices[id].gran);
+    if (g->d_gran_live.upload_async(live, stream)) { g->failed = true; return 0; }
+    g->gran_live_dirty = false;
+  }
   if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return 0; } }
   if (g->overlap_stream != stream) { g->rows_free_fresh = false; g->overlap_stream = stream; }
   g->write_done_attached = false;
@@ -1819,7 +2034,8 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       if (!cmds.empty()) {
         // (a round that will run its decision-scan kernel takes a short list there as the kernel's argument: no copy kernel on the stream)
         sp.n_cmds = (int)cmds.size();
-        const bool by_scan = cmds.size() <= PG_CMD_PACK && level_concurrent(g, 0, sp, stream);
+        // (pg_grain_kernel reads the list in front of the scan: with living granular voices it travels by copy)
+        const bool by_scan = cmds.size() <= PG_CMD_PACK && g->gran_voices.empty() && level_concurrent(g, 0, sp, stream);
         if (stage_commands(g, cmds, stream, &sp.d_cmds, by_scan ? &sp.h_cmds : nullptr)) return fail();
         // Which commands can leave the steady state behind them? A parameter command may start a smoother of an effect (the device knows how
         // long: the next rounds' scans tell), a speed command a glide, markers belong to split chunks. Source volume / panning / stop / seek
@@ -1836,6 +2052,11 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       // nothing deferred, and units leave the steady state only through those host-visible events -> the generic launch is skipped.
       // (Graphs with nested sub-mixers always launch it: the parents are rendered there.)
       sp.generic_idle = steady_now && cmds.empty() && g->last_change_round < round0;
+    }
+    // granular voices: their frames of every piece of the chunk, staged in front of the unit kernels that take them
+    if (!g->gran_voices.empty()) for (uint64_t p = 0; p < n_pieces; ++p) {
+      const LaunchSpan& sp = spans[(size_t)p];
+      if (launch_grains(g, sp.t0, sp.n, now, sp.d_cmds, sp.n_cmds, stream)) return fail();
     }
     for (size_t li = 0; li < g->levels.size(); ++li) {
       for (uint64_t p = 0; p < n_pieces; ++p) {

@@ -38,6 +38,25 @@ hipError_t pg_launch_defer_scan(const PgLaunch& L, hipStream_t stream, hipEvent_
 hipError_t pg_launch_stages(const PgLaunch& L, hipStream_t stream, int single_launch, int lean, int wide, int adapt, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, hipEvent_t tail_done = nullptr);
 hipError_t pg_launch_mix(const float* unit_out, uint32_t stride, int n_units, float* partial, float* bus, uint32_t n_samples, const int32_t* audible_tab,
                          size_t audible_stride, int* audible_out, hipStream_t stream, int n_chunks = 1, size_t chunk_stride = 0, hipEvent_t done = nullptr);
+// ---- granular voices (pg_k_grain.hip): one pg_grain_kernel launch renders frames [t0, t0 + n) of every living granular voice ----
+struct PgGrainLaunch {
+  PgGrainVoice* recs;          // the graph's granular records ...
+  uint32_t n_recs;             // ... and how many there are: no record at or beyond it is taken
+  uint32_t n_live;             // workgroups of the launch: live[b] = the record workgroup b renders
+  const int32_t* live;
+  const PgVoice* voices;
+  const PgCmd* cmds;           // the piece's command list (PgLaunch::cmds): the kernel picks the voice commands of its voice
+  int32_t n_cmds;
+  uint32_t sample_rate;
+  const float* lut;            // [PG_GRAIN_WINDOWS][PG_GRAIN_LUT_N]
+  int32_t* ended;              // mapped host memory, one word per record: set when the kernel finds the record's voice ended
+  uint64_t t0;                 // position of the launch's first frame
+  uint32_t n;                  // frames of the launch
+  uint32_t pad;
+  uint64_t chunk_t0;           // position of frame 0 of the voices' staging buffers: the start of the main mixer's chunk this piece belongs to
+};
+hipError_t pg_launch_grain(const PgGrainLaunch& L, hipStream_t stream);
+void pg_grain_build_lut(float* out);   // GRAIN_WINDOW_LUT, host side
 
 // ---- errors ---------------------------------------------------------------------------------------------
 int set_error(int code, const char* fmt, ...);  // records the thread's last error message (pg_last_error_message) and returns `code`
@@ -211,6 +230,8 @@ struct HostVoice {
   uint64_t added_at_write = 0;     // pg_graph::write_count when the voice was added (an envelope is attached before the voice renders a frame)
   bool env = false;                // an envelope was attached (pg_graph_set_voice_envelope): its state sits in pg_graph::d_env[dev_index]
   bool env_live = false;           // ... and the voice has not ended yet: its unit is rendered by the exact kernel (PgUnit::static_defer)
+  int gran = -1;                   // granular voice (pg_graph_add_granular_voice): its record in pg_graph::d_gran; d_pcm = the mono buffer, d_stage = the staging buffer
+  bool gran_live = false;          // ... and pg_grain_kernel has not reported the voice ended: it renders the voice, the exact kernel its unit
 };
 struct HostMixer {
   int unit_slot = -1;              // sub-mixer unit; for the main mixer: the bus unit
@@ -377,6 +398,18 @@ struct pg_graph {
   std::vector<PgMeterJob> meter_jobs;    // the launch being put together (capacity kept across writes)
   std::vector<PgMeterSpan> meter_spans;
   std::vector<int> row_of_mixer;         // sub-mixer id -> its row of the per-unit output table (rebuild_topology)
+  // granular voices (pg_graph_add_granular_voice): records in device memory (grown by doubling, the graph quiescent), reached by the kernels
+  // through the envelope table's header; the window tables, built with the first granular voice; one `ended` word per record in mapped host
+  // memory (polled at the top of a write); the records pg_grain_kernel still renders, uploaded when the set changes
+  PgGrainVoice* d_gran = nullptr;
+  size_t gran_n = 0, gran_cap = 0;
+  int32_t* d_grain_of_voice = nullptr;   // env_cap entries
+  float* d_grain_lut = nullptr;
+  int32_t* h_gran_ended = nullptr;       // gran_cap words, mapped
+  int32_t* d_gran_ended = nullptr;       // ... as the device sees them
+  std::vector<int> gran_voices;          // ids of the living granular voices
+  DeviceTable<int32_t> d_gran_live;      // their records
+  bool gran_live_dirty = false;
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };

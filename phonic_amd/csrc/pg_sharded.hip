@@ -352,6 +352,26 @@ int pg_sharded_add_stream_voice(pg_sharded_graph* s, int mixer_id, uint32_t chan
   if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
   return id;
 }
+// granular voices (pg_graph_add_granular_voice): placed like any other source; the shard that owns the voice runs its pg_grain_kernel
+int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }   // (before the id: parameter errors never depend on the graph)
+  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  int32_t pk;
+  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
+  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
+  const int local = pg_graph_add_granular_voice(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), mono_pcm, n_frames, p, opt);
+  if (local < 0) return local;
+  if (mixer_id == 0) s->load[shard] += 1;
+  const int id = (int)s->voice_map.size();
+  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
+  return id;
+}
+int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  const int32_t pk = s->voice_map.get((size_t)voice_id);
+  return pg_graph_voice_grain_state(s->shards[shard_of(pk)], local_of(pk), out);
+}
 int pg_sharded_feed_voice(pg_sharded_graph* s, int voice_id, const float* frames, size_t n_frames) {
   if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
   const int32_t pk = s->voice_map.get((size_t)voice_id);

@@ -1071,9 +1071,26 @@ DEVO void ahdsr_apply(PgVoice* v, PgEnv* e, float* out, int frames_w, const SrcS
 // voice's envelope or nullptr. An enveloped voice takes the separate passes (nothing fused into the resampler's output loop, nothing added
 // into the mixer's block on the way): the envelope multiplies what the panning step left.
 template <bool GLIDE, int ADAPTERS, bool ENV = false>
-DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const SrcScratch& S, float* acc, int* added, bool ask_ends = true, PgEnv* env = nullptr) {
+DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const SrcScratch& S, float* acc, int* added, bool ask_ends = true, PgEnv* env = nullptr,
+                     const PgGrainVoice* gr = nullptr, uint64_t src_time = 0) {
   *added = 0;
   const int tid = pg_tid(), nt = blockDim.x;
+  if (ENV && gr != nullptr) {
+    // A granular voice (SamplerVoice::process's grain branch, voice.rs:412-427): pg_grain_kernel rendered the chunk's frames into the voice's
+    // staging buffer in front of this launch — the source output is a copy; no amplified / panned / fader stage, the envelope on top as for
+    // any voice (:469-486). GrainPool::stop() is pg_grain_kernel's business (a Stop message queued here changes nothing). The voice is finished
+    // with the call in which the pool became exhausted (:488-495): a call that ends in this piece asks.
+    if (v->finished) return 0;
+    const uint64_t off = src_time - gr->stage_pos;
+    const bool staged_ok = src_time >= gr->stage_pos && off + (uint64_t)frames <= (uint64_t)PG_MAX_FRAMES;
+    const float* const src = gr->staged + off * 2;
+    for (int i = tid; i < 2 * frames; i += nt) out[i] = staged_ok ? src[i] : 0.0f;
+    __syncthreads();
+    if (env != nullptr) ahdsr_apply(v, env, out, frames, S);
+    if (tid == 0 && ask_ends && gr->exhausted_at < src_time + (uint64_t)frames) v->finished = 1;
+    __syncthreads();
+    return frames * 2;
+  }
   const int C = (int)v->channels;
   int wf;
   if (ADAPTERS >= 1 && (v->stream_on || (ADAPTERS == 2 && v->outer_on))) {
@@ -1161,7 +1178,7 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
 template <bool GLIDE, int ADAPTERS = 2, bool ENV = false>
 DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp, int frames, uint64_t pos, const SrcScratch& S0,
                        const PgSchedEntry* sched, int sched_bank, bool have_word = false, uint32_t word = 0, uint64_t call_end = 0, bool chunk_first = true,
-                       uint64_t chunk_end = 0, bool in_lds = false, PgEnv* env = nullptr, int32_t* env_done = nullptr) {
+                       uint64_t chunk_end = 0, bool in_lds = false, PgEnv* env = nullptr, int32_t* env_done = nullptr, const PgGrainVoice* gr = nullptr) {
   SrcScratch S = S0;
   const int tid = pg_tid(), nt = blockDim.x;
   static_assert(sizeof(PgVoice) / 4 <= 256, "one dword per lane");
@@ -1215,7 +1232,7 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
     // (a call that reaches the end of this piece without reaching a stop time or the end of the chunk goes on in the next piece)
     const bool ask_ends = pos + (uint64_t)frames >= chunk_end || samples_until_stop <= (uint64_t)(out_len - total_written);
     int added;
-    int written = voice_write<GLIDE, ADAPTERS, ENV>(lv, tmp, to_write / 2, pending_stop, S, sig + total_written, &added, ask_ends, env);
+    int written = voice_write<GLIDE, ADAPTERS, ENV>(lv, tmp, to_write / 2, pending_stop, S, sig + total_written, &added, ask_ends, env, gr, source_time);
     if (!added) for (int i = tid; i < written; i += nt) sig[total_written + i] = sig[total_written + i] + tmp[i];  // add_buffers
     __syncthreads();
     total_written += written;

@@ -612,8 +612,14 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         PgEnvTable* const envs = (!FAST_ONLY && L.voices) ? L.env : nullptr;
         PgEnv* env = (envs && (uint64_t)(gv - L.voices) < envs->cap) ? (PgEnv*)(envs + 1) + (gv - L.voices) : nullptr;
         if (!FAST_ONLY && env && !env->on) env = nullptr;
+        // (granular voices: their record sits behind the same table; its frames of this piece were staged by pg_grain_kernel)
+        const PgGrainVoice* gr = nullptr;
+        if (!FAST_ONLY && envs && envs->grain_of_voice && (uint64_t)(gv - L.voices) < envs->cap) {
+          const int gi = envs->grain_of_voice[gv - L.voices];
+          if (gi >= 0 && (uint32_t)gi < envs->n_grains) gr = envs->grains + gi;
+        }
         const int r = voice_process<!FAST_ONLY, (FAST_ONLY && KMASK == (0x7ff & ~((1 << 5) | (1 << 7)))) ? 1 : 2, !FAST_ONLY>(gv, lv, sseg, tmp, seg, pos, S, L.sched, L.sched_bank, tables && vi == 0, voice_word, call_end_pos, seg_first, seg_chunk_end,
-                                                                                                                      resident && vi == 0, env, (!FAST_ONLY && env) ? envs->done + (gv - L.voices) : nullptr);
+                                                                                                                      resident && vi == 0, env, (!FAST_ONLY && env) ? envs->done + (gv - L.voices) : nullptr, gr);
         audible_input |= (r & 1) != 0;
         later |= r & 2;
       }

@@ -174,6 +174,17 @@ class ShardedGraph:
         o = _capi.default_voice_options(**opts)
         return self._id(self._lib.pg_sharded_add_voice(self._h, mixer_id, pcm.ctypes.data_as(C.POINTER(C.c_float)), pcm.size // src_channels, src_channels, src_rate, C.byref(o)))
 
+    def add_granular_voice(self, mixer_id, pcm, params=None, channels=1, **opts):
+        mono = _capi.mono_downmix(pcm, channels)
+        p = params if params is not None else _capi.granular_params()
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._lib.pg_sharded_add_granular_voice(self._h, mixer_id, mono.ctypes.data_as(C.POINTER(C.c_float)), mono.size, C.byref(p), C.byref(o)))
+
+    def voice_grain_state(self, voice):
+        st = _capi.GrainState()
+        self._check(self._lib.pg_sharded_voice_grain_state(self._h, voice, C.byref(st)))
+        return _capi.grain_state_dict(st)
+
     def add_stream_voice(self, mixer_id, channels, rate, capacity_frames, **opts):
         o = _capi.default_voice_options(**opts)
         v = self._id(self._lib.pg_sharded_add_stream_voice(self._h, mixer_id, channels, rate, capacity_frames, C.byref(o)))
