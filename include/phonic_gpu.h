@@ -294,8 +294,9 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
 /* Granular playback voices: a sampler voice in granular mode — GrainPool<100> (src/generator/sampler/granular.rs) driven as
  * SamplerVoice::process drives it (src/generator/sampler/voice.rs:406-432). Rendered on the device by pg_grain_kernel ("Granular
  * voices"); each grain's per-frame stereo terms are the reference's bits, the f32 sum over the grains of a frame runs in ascending slot order.
- * OUT OF SCOPE: the modulation matrix (every `*_mod` input of try_trigger_grain / advance_playhead is 0.0 — what a sampler without routings
- * feeds); the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the mono down-mix and resample of
+ * The voice's modulation matrix is pg_graph_set_voice_modulation_matrix below; without one every `*_mod` input of try_trigger_grain /
+ * advance_playhead is 0.0 — what a sampler without routings feeds.
+ * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the mono down-mix and resample of
  * create_granular_sample_buffer (sampler.rs:908-952: the caller hands over the mono f32 buffer at the graph's rate that function would have
  * produced); changing granular parameters after the voice has started.
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
@@ -356,6 +357,70 @@ typedef struct pg_grain_state {
   pg_grain_slot slots[PG_GRAIN_POOL_SIZE];
 } pg_grain_state;
 int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out);
+
+/* The modulation matrix of a granular voice: the ModulationMatrix every granular sampler voice owns (src/generator/sampler/voice.rs:341-373,
+ * src/modulation/matrix.rs, src/generator/sampler/modulation.rs), run in front of the grain engine (voice.rs:412-427) — on the device as phase 0
+ * of pg_grain_kernel ("Granular voices", Modulation). Sources in the matrix's slot order (sampler.rs:362-416): 0 LFO 1 (`LFO1`,
+ * 1 Hz Sine), 1 LFO 2 (`LFO2`, 2 Hz Triangle), 2 velocity (`VELM`), 3 keytracking (`KEYM`). Targets in Sampler::modulation_config's order
+ * (sampler.rs:417-425): 0 GRAIN_SIZE, 1 GRAIN_DENSITY, 2 GRAIN_VARIATION, 3 GRAIN_SPRAY, 4 GRAIN_PAN_SPREAD, 5 GRAIN_POSITION, 6 GRAIN_STEP.
+ * Per target and frame the sum starts at 0.0 and takes the slots in that order, each only if it routes to the target (matrix.rs:194-303), in
+ * f32: an LFO adds v * amount to a bipolar target and ((v + 1) / 2) * amount to a unipolar one; velocity (the note's volume) and keytracking
+ * (note / 127) add ((v - 0.5) * 2) * amount to a bipolar target and v * amount to a unipolar one. The sums enter the pool as granular.rs writes
+ * them: density * (1 + mod) clamped to 1..100 (:798-799), spray + mod clamped to 0..1 (:565), position + mod when mod != 0, in front of the
+ * loop fold (:455-471), variation + mod clamped to 0..1 (:827), size * (1 + mod) clamped to 1..1000 (:848-849), pan spread + mod clamped to
+ * 0..1 (:855), step * (1 + mod) (:609-613). The LFOs are src/utils/dsp/lfo.rs with all seven shapes; their generators follow the rule of
+ * pg_granular_params::rng_state above (Xoshiro256++ state as an input, all-zero = SplitMix64(0x5EED0000) x 4, random::<f32>() as defined there
+ * and as UNVERIFIED against the crate). The matrix advances on the frames the voice renders only: not in front of its start time, not after it
+ * has ended. A release touches no modulation source (note_off reaches envelope slots, and the sampler has none, sampler/modulation.rs:101-103).
+ * In the reference the timed calls below reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
+ * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the Sampler's note, voice-allocation and stealing layer;
+ * playback-position status events (pg_modulation_state::last[5] is the value they would use, voice.rs:435-446); changing the granular
+ * parameters themselves after the voice has started. */
+#define PG_MOD_SOURCES 4
+#define PG_MOD_TARGETS 7
+typedef struct pg_mod_lfo   { float rate_hz; int32_t waveform; uint64_t rng_state[4]; } pg_mod_lfo;   /* waveform: LfoWaveform 0..6 (lfo.rs:35-47): Sine, Triangle, RampUp, RampDown, Square, Random, SmoothRandom */
+typedef struct pg_mod_route { float amount; int32_t bipolar; } pg_mod_route;                          /* ModulationProcessorTarget (processor.rs); amount 0: no route */
+typedef struct pg_modulation_params {
+  pg_mod_lfo lfo[2];
+  float velocity;      /* SamplerVoice::start's per-note `volume`, 0..1 — NOT the effective volume handed to GrainPool::start */
+  int32_t note;        /* 0..127 */
+  pg_mod_route routes[PG_MOD_SOURCES][PG_MOD_TARGETS];
+} pg_modulation_params;
+/* Sampler::modulation_config's defaults (sampler.rs:369-390): 1 Hz Sine, 2 Hz Triangle; velocity 1.0, note 60, no routes, rng states 0 */
+void pg_modulation_params_default(pg_modulation_params* p);
+/* ModulationState::set_modulation's errors (src/modulation/state.rs:195-201) for every route: an amount outside [-1, 1] or NaN; a waveform outside
+ * 0..6; a NaN rate (other rates are clamped to 0.01..=20.0 like the reference's raw parameter update, sampler.rs:870-874, :369-384); a velocity
+ * outside [0, 1]; a note outside 0..127; a null `p`. PG_OK or PG_ERR_PARAMETER; touches no graph and no device. */
+int pg_modulation_params_check(const pg_modulation_params* p);
+/* SamplerVoice::enable_granular_playback's create_matrix (voice.rs:341-373, src/modulation/state.rs:91-156: each Lfo::new draws its three random
+ * values at the default rate and waveform), then the rates, waveforms and routes of `p` (Lfo::set_rate / set_waveform change nothing else,
+ * lfo.rs:102-119; a route with |amount| < 0.001 is not added, matrix.rs:60-83), then SamplerVoiceModulationState::start(note, velocity) =
+ * ModulationMatrix::note_on (matrix.rs:394-408): both LFOs reset (lfo.rs:89-99: phase 0; Random and SmoothRandom draw again). Granular voices
+ * only (PG_ERR_NOT_FOUND otherwise); only before the voice has rendered a frame (PG_ERR_STATE afterwards). A granular voice without this call has
+ * no matrix and nothing about it changes. */
+int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_modulation_params* p);
+/* GeneratorPlaybackHandle::set_modulation / clear_modulation (player/handles/generator.rs:337-430, sampler.rs:694-720; ModulationMatrixSlot::
+ * update_target, matrix.rs:60-83: |amount| < 0.001 removes the route) and set_parameter(ML1R | ML2R) / (ML1W | ML2W) (sampler.rs:1148-1186; the
+ * rate is clamped to 0.01..=20.0). Scheduled like pg_graph_set_voice_volume: events of the voice's mixer that cut its chunk and act in front of
+ * frame `sample_time` (0: the next write's first frame); any thread. clear is set with amount 0. PG_ERR_PARAMETER: an index out of range, an
+ * amount outside [-1, 1] or NaN, a NaN rate; PG_ERR_NOT_FOUND: no such voice; PG_ERR_STATE: the voice has no matrix. */
+int pg_graph_set_voice_modulation(pg_graph* g, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time);
+int pg_graph_clear_voice_modulation(pg_graph* g, int voice_id, int source, int target, uint64_t sample_time);
+int pg_graph_set_voice_lfo_rate(pg_graph* g, int voice_id, int lfo, float rate_hz, uint64_t sample_time);
+int pg_graph_set_voice_lfo_waveform(pg_graph* g, int voice_id, int lfo, int waveform, uint64_t sample_time);
+/* Debug read-back of the matrix: per LFO the fields of Lfo (lfo.rs:52-60), the two static sources, the 4 x 7 routes as the matrix holds them (a
+ * removed route reads amount 0, bipolar 0) and last[7], the seven sums of the last rendered frame (what voice.rs:435-446 reads with
+ * output_at(.., output_size - 1)), all 0 before the first frame. Waits for the graph's stream. PG_ERR_NOT_FOUND: not a granular voice;
+ * PG_ERR_STATE: no matrix. */
+typedef struct pg_mod_lfo_state { float phase, phase_inc, sample_hold, jitter_current, jitter_target; int32_t waveform; uint64_t rng_state[4]; } pg_mod_lfo_state;
+typedef struct pg_modulation_state {
+  pg_mod_lfo_state lfo[2];
+  float velocity, note_pitch;
+  pg_mod_route routes[PG_MOD_SOURCES][PG_MOD_TARGETS];
+  float last[PG_MOD_TARGETS];
+  int32_t reserved;
+} pg_modulation_state;
+int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_state* out);
 
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and
@@ -520,6 +585,14 @@ int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id);
  * volume, panning, speed, stop, release, envelope and seek reach a granular voice through the calls above, as on the plain graph */
 int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt);
 int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out);
+/* pg_graph_set_voice_modulation_matrix / _set_voice_modulation / _clear_voice_modulation / _set_voice_lfo_rate / _set_voice_lfo_waveform /
+ * _voice_modulation_state (src/modulation/matrix.rs, src/generator/sampler/modulation.rs) on the voice's shard */
+int pg_sharded_set_voice_modulation_matrix(pg_sharded_graph* s, int voice_id, const pg_modulation_params* p);
+int pg_sharded_set_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time);
+int pg_sharded_clear_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, uint64_t sample_time);
+int pg_sharded_set_voice_lfo_rate(pg_sharded_graph* s, int voice_id, int lfo, float rate_hz, uint64_t sample_time);
+int pg_sharded_set_voice_lfo_waveform(pg_sharded_graph* s, int voice_id, int lfo, int waveform, uint64_t sample_time);
+int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modulation_state* out);
 /* pg_graph_set_metering / pg_graph_mixer_audio_level on the one mixer: a sub-mixer's level comes from its shard; mixer 0's is measured on the root
  * behind the bus chain, one record per pg_sharded_write* call (src/source/metered.rs:75-143) */
 int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds);

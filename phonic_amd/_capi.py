@@ -175,6 +175,76 @@ def grain_state_dict(st):
     }
 
 
+MOD_SOURCES, MOD_TARGETS = 4, 7
+MOD_SOURCE_NAMES = ("LFO1", "LFO2", "VELM", "KEYM")                                         # the matrix's slot order (sampler.rs:362-416)
+MOD_TARGET_NAMES = ("size", "density", "variation", "spray", "pan_spread", "position", "step")   # Sampler::modulation_config's order (sampler.rs:417-425)
+LFO_WAVEFORMS = ("Sine", "Triangle", "RampUp", "RampDown", "Square", "Random", "SmoothRandom")   # LfoWaveform (utils/dsp/lfo.rs:35-47)
+
+
+class ModLfo(C.Structure):
+    """pg_mod_lfo: rate, waveform and the Xoshiro256++ state of one of the matrix's LFOs."""
+    _fields_ = [("rate_hz", C.c_float), ("waveform", C.c_int32), ("rng_state", C.c_uint64 * 4)]
+
+
+class ModRoute(C.Structure):
+    """pg_mod_route: ModulationProcessorTarget's amount and polarity; amount 0 = no route."""
+    _fields_ = [("amount", C.c_float), ("bipolar", C.c_int32)]
+
+
+class ModulationParams(C.Structure):
+    """pg_modulation_params: the ModulationMatrix of a granular sampler voice as the note starts (src/generator/sampler/modulation.rs)."""
+    _fields_ = [("lfo", ModLfo * 2), ("velocity", C.c_float), ("note", C.c_int32), ("routes", (ModRoute * MOD_TARGETS) * MOD_SOURCES)]
+
+
+class ModLfoState(C.Structure):
+    _fields_ = [("phase", C.c_float), ("phase_inc", C.c_float), ("sample_hold", C.c_float), ("jitter_current", C.c_float), ("jitter_target", C.c_float),
+                ("waveform", C.c_int32), ("rng_state", C.c_uint64 * 4)]
+
+
+class ModulationState(C.Structure):
+    """pg_modulation_state: debug read-back of the matrix."""
+    _fields_ = [("lfo", ModLfoState * 2), ("velocity", C.c_float), ("note_pitch", C.c_float), ("routes", (ModRoute * MOD_TARGETS) * MOD_SOURCES),
+                ("last", C.c_float * MOD_TARGETS), ("reserved", C.c_int32)]
+
+
+def modulation_params(rates=None, waveforms=None, rng_states=None, velocity=None, note=None, routes=()):
+    """pg_modulation_params_default() with overrides: rates / waveforms / rng_states per LFO (None: keep), routes = (source, target, amount, bipolar)."""
+    p = ModulationParams()
+    load().pg_modulation_params_default(C.byref(p))
+    for l in range(2):
+        if rates is not None and rates[l] is not None:
+            p.lfo[l].rate_hz = float(rates[l])
+        if waveforms is not None and waveforms[l] is not None:
+            p.lfo[l].waveform = int(waveforms[l])
+        if rng_states is not None and rng_states[l] is not None:
+            for i in range(4):
+                p.lfo[l].rng_state[i] = int(rng_states[l][i])
+    if velocity is not None:
+        p.velocity = float(velocity)
+    if note is not None:
+        p.note = int(note)
+    for (s, t, amount, bipolar) in routes:
+        p.routes[s][t].amount, p.routes[s][t].bipolar = float(amount), 1 if bipolar else 0
+    return p
+
+
+def modulation_state_dict(st):
+    """A ModulationState as numpy scalars / arrays (the layout tests/modulation_model.py's Matrix.state() uses)."""
+    import numpy as np
+
+    d = {"velocity": np.float32(st.velocity), "note_pitch": np.float32(st.note_pitch),
+         "amount": np.array([[st.routes[s][t].amount for t in range(MOD_TARGETS)] for s in range(MOD_SOURCES)], dtype=np.float32),
+         "bipolar": np.array([[st.routes[s][t].bipolar for t in range(MOD_TARGETS)] for s in range(MOD_SOURCES)], dtype=np.int32),
+         "last": np.array(list(st.last), dtype=np.float32)}
+    for l in range(2):
+        o = st.lfo[l]
+        for k in ("phase", "phase_inc", "sample_hold", "jitter_current", "jitter_target"):
+            d[f"lfo{l}_{k}"] = np.float32(getattr(o, k))
+        d[f"lfo{l}_waveform"] = int(o.waveform)
+        d[f"lfo{l}_rng"] = tuple(int(x) for x in o.rng_state)
+    return d
+
+
 def mono_downmix(pcm, channels):
     """The down-mix of Sampler::create_granular_sample_buffer (sampler.rs:940-943) for a buffer that is already at the graph's rate: per frame, the f32
     sum of the channels in order, divided by the channel count."""
@@ -408,6 +478,20 @@ def load():
         fn = getattr(lib, prefix + "voice_grain_state")
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int, P(GrainState)]
+    lib.pg_modulation_params_default.restype = None
+    lib.pg_modulation_params_default.argtypes = [P(ModulationParams)]
+    lib.pg_modulation_params_check.restype = C.c_int
+    lib.pg_modulation_params_check.argtypes = [P(ModulationParams)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        for name, args in (("set_voice_modulation_matrix", [C.c_int, P(ModulationParams)]),
+                           ("set_voice_modulation", [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64]),
+                           ("clear_voice_modulation", [C.c_int, C.c_int, C.c_int, C.c_uint64]),
+                           ("set_voice_lfo_rate", [C.c_int, C.c_int, C.c_float, C.c_uint64]),
+                           ("set_voice_lfo_waveform", [C.c_int, C.c_int, C.c_int, C.c_uint64]),
+                           ("voice_modulation_state", [C.c_int, P(ModulationState)])):
+            fn = getattr(lib, prefix + name)
+            fn.restype = C.c_int
+            fn.argtypes = [vp] + args
     lib.pg_graph_kernel_ms.restype = C.c_double
     lib.pg_graph_kernel_ms.argtypes = [vp, C.c_int, P(C.c_uint64)]
     lib.pg_graph_kernel_stats.restype = C.c_int

@@ -155,6 +155,31 @@ class GraphHandle:
         self._check(self._fn("graph_voice_grain_state")(self._h, voice, C.byref(st)))
         return _capi.grain_state_dict(st)
 
+    def set_voice_modulation_matrix(self, voice, params=None, **kw):
+        """The ModulationMatrix of a granular voice (two LFOs, velocity, keytracking -> the seven granular targets) + note_on; before the voice
+        renders. `params`: a _capi.ModulationParams, or the keywords of _capi.modulation_params."""
+        p = params if params is not None else _capi.modulation_params(**kw)
+        self._check(self._fn("graph_set_voice_modulation_matrix")(self._h, voice, C.byref(p)))
+
+    def set_voice_modulation(self, voice, source, target, amount, bipolar, sample_time):
+        """GeneratorPlaybackHandle::set_modulation for this voice, in front of frame sample_time (|amount| < 0.001 removes the route)."""
+        self._check(self._fn("graph_set_voice_modulation")(self._h, voice, source, target, float(amount), 1 if bipolar else 0, sample_time))
+
+    def clear_voice_modulation(self, voice, source, target, sample_time):
+        self._check(self._fn("graph_clear_voice_modulation")(self._h, voice, source, target, sample_time))
+
+    def set_voice_lfo_rate(self, voice, lfo, rate_hz, sample_time):
+        self._check(self._fn("graph_set_voice_lfo_rate")(self._h, voice, lfo, float(rate_hz), sample_time))
+
+    def set_voice_lfo_waveform(self, voice, lfo, waveform, sample_time):
+        self._check(self._fn("graph_set_voice_lfo_waveform")(self._h, voice, lfo, int(waveform), sample_time))
+
+    def voice_modulation_state(self, voice):
+        """The matrix as a dict (debug read-back: waits for the graph's stream)."""
+        st = _capi.ModulationState()
+        self._check(self._fn("graph_voice_modulation_state")(self._h, voice, C.byref(st)))
+        return _capi.modulation_state_dict(st)
+
     def stop_all_voices(self):
         """Player::stop_all_sources (src/player.rs:1012-1045)."""
         self._check(self._fn("graph_stop_all_voices")(self._h))

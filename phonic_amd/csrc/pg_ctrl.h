@@ -27,6 +27,10 @@ enum CtrlType : int32_t {
   CT_STOP_ALL = 7,      // Player::stop_all_sources: stop every source + RemoveAllPendingEvents
   CT_VOICE_REMOVE = 8,  // id = voice id                                                         (RemoveSource)
   CT_VOICE_RELEASE = 9, // id = voice id: the envelope's note_off at sample_time, an event           (SamplerVoice::stop)
+  // the modulation matrix of a granular voice, events (GeneratorPlaybackHandle::set_modulation / set_parameter, player/handles/generator.rs:337-430)
+  CT_VOICE_MOD_ROUTE = 10,    // param = source | target << 8 | bipolar << 16, value = amount (0: remove the route)
+  CT_VOICE_LFO_RATE = 11,     // param = lfo, value = rate in Hz, clamped
+  CT_VOICE_LFO_WAVEFORM = 12, // param = lfo | waveform << 8
 };
 
 struct CtrlMsg {

@@ -3,6 +3,7 @@
 // ring layout and index arithmetic (reference src/utils/dsp/delay.rs) so state is comparable with the
 // CPU oracle after every block.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define PG_USIZE_MAX 0xFFFFFFFFFFFFFFFFull
@@ -279,6 +280,26 @@ struct PgGrainParams {         // GranularParameters (granular.rs:241-266) + Gra
   float loop_start, loop_end;
   int32_t pad;
 };
+// The ModulationMatrix of a granular sampler voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs): two LFO slots, the velocity
+// and the keytracking slot, routed to the seven granular targets of Sampler::modulation_config (sampler.rs:392-427).
+#define PG_GMOD_SOURCES 4      // slot order: LFO 1, LFO 2, velocity, keytracking
+#define PG_GMOD_TARGETS 7      // GRAIN_SIZE, _DENSITY, _VARIATION, _SPRAY, _PAN_SPREAD, _POSITION, _STEP
+struct PgModLfo {              // Lfo (src/utils/dsp/lfo.rs:52-60), all seven shapes, with its generator (SmallRng = Xoshiro256++)
+  float phase, phase_inc;
+  int32_t waveform;            // LfoWaveform 0..6
+  float sample_hold, jitter_current, jitter_target;
+  int32_t pad[2];
+  uint64_t rng[4];
+};
+struct PgGrainMod {
+  int32_t on, pad;
+  float velocity, note_pitch;  // VelocityModulationProcessor::velocity, KeytrackingModulationProcessor::note_pitch (processor.rs:236-244, :292-298)
+  PgModLfo lfo[2];
+  float amount[PG_GMOD_SOURCES][PG_GMOD_TARGETS];     // the slot's target for the parameter (matrix.rs:60-83): 0.0 = none (a route's |amount| is >= 0.001)
+  int32_t bipolar[PG_GMOD_SOURCES][PG_GMOD_TARGETS];
+  float last[PG_GMOD_TARGETS]; // the seven sums of the last rendered frame (voice.rs:435-446 reads the position's)
+  int32_t pad_last;
+};
 struct PgGrainVoice {
   PgGrainParams params;
   PgGrainPool pool;
@@ -292,8 +313,10 @@ struct PgGrainVoice {
   int32_t voice;               // device index of the voice (PgLaunch::voices)
   int32_t has_env;             // the voice has a volume envelope: CMD_VOICE_RELEASE is its note_off, not a stop
   PgGrain grains[PG_GRAIN_POOL];
+  PgGrainMod mod;              // the voice's ModulationMatrix (pg_graph_set_voice_modulation_matrix); mod.on == 0: none, every `*_mod` is left out
 };
 static_assert(sizeof(PgGrain) == 80 && sizeof(PgGrainPool) == 72 && sizeof(PgGrainParams) == 56 && sizeof(PgGrainVoice) % 8 == 0, "host and device agree on the layout");
+static_assert(sizeof(PgModLfo) == 64 && sizeof(PgGrainMod) == 400 && offsetof(PgGrainVoice, mod) % 8 == 0, "host and device agree on the layout");
 
 // Parameter indices per effect kind = order of `Effect::parameters()` in the reference.
 enum { P_GAIN_GAIN = 0, P_GAIN_DCFM };
@@ -372,6 +395,10 @@ enum PgCmdType {
   CMD_CHUNK_END = 9,
   CMD_CALL_END = 10,
   CMD_VOICE_RELEASE = 11,  // target = voice index: AhdsrEnvelope::note_off at `frame`; a voice without an envelope stops (stop_time = value64), voice.rs:196-212
+  // the modulation matrix of a granular voice (target = voice index; pg_grain_kernel applies them in front of `frame`, the unit kernels ignore them):
+  CMD_VOICE_MOD_ROUTE = 12,     // value = amount (0.0: remove the route), value64 = source | target << 8 | bipolar << 16   (ModulationMatrixSlot::update_target)
+  CMD_VOICE_LFO_RATE = 13,      // value = phase_inc = (rate as f64 / sample_rate as f64) as f32, value64 = lfo                (Lfo::set_rate)
+  CMD_VOICE_LFO_WAVEFORM = 14,  // value64 = lfo | waveform << 8                                                               (Lfo::set_waveform)
 };
 #define PG_MAX_CALLS 64  // calls of one sub-mixer per launch round (bits of PgUnit::call_audible); the host bounds the round accordingly
 struct PgCmd {

@@ -12,9 +12,11 @@
 // Everything is compiled with contraction off, f32 where the reference has f32 and f64 where it has f64: each grain's per-frame terms are the
 // reference's bits; only the order of the f32 sum over the grains of a frame is this implementation's (ascending slot index).
 //
-// Out of scope (include/phonic_gpu.h says so too): the modulation matrix — every `*_mod` argument of try_trigger_grain / advance_playhead is
-// 0.0, what a sampler without routings feeds; `x + 0.0` and `x * (1.0 + 0.0)` leave every finite x as it is, so those operations are left out;
-// parameter changes after the voice has started; playback-position status events.
+// The modulation matrix (pg_graph_set_voice_modulation_matrix): a voice that has one hands the frame's seven sums (GrainModFrame, formed by
+// phase 0 of pg_grain_kernel) to grain_sched_frame<true>, which applies them as the reference writes them, `x + 0.0` and `x * (1.0 + 0.0)` of
+// a matrix without routes included. A voice without one takes grain_sched_frame<false>: every `*_mod` argument of try_trigger_grain /
+// advance_playhead is 0.0 there, and since `x + 0.0` and `x * (1.0 + 0.0)` leave every finite x as it is those operations are left out.
+// Out of scope (include/phonic_gpu.h says so too): parameter changes after the voice has started; playback-position status events.
 //
 // Random draws are rand 0.9's on SmallRng = Xoshiro256++ as rand's documentation describes them (unverified against the crate's source, which
 // this project does not hold): random::<f32>() = (next_u64 >> 40) * 2^-24 (rng_random_f32), random::<f64>() = (next_u64 >> 11) * 2^-53,
@@ -90,8 +92,61 @@ struct GrainActivation {
   int32_t has_loop;
 };
 
-DEV float grain_playback_position(const GrainSched& S) {  // granular.rs:446-472, position_mod == 0
+// The seven sums of the matrix for one frame, in the targets' order (SamplerVoiceModulationState::output, sampler/modulation.rs:237-247).
+// `p` points at the frame's GRAIN_SIZE sum, the other targets follow PG_GRAIN_TILE floats apart (pg_grain_kernel's s_mod[target][frame]); each is
+// read where the reference uses it.
+struct GrainModFrame {
+  const float* p;
+  DEV float size() const { return p[0]; }
+  DEV float density() const { return p[PG_GRAIN_TILE]; }
+  DEV float variation() const { return p[2 * PG_GRAIN_TILE]; }
+  DEV float spray() const { return p[3 * PG_GRAIN_TILE]; }
+  DEV float pan_spread() const { return p[4 * PG_GRAIN_TILE]; }
+  DEV float position() const { return p[5 * PG_GRAIN_TILE]; }
+  DEV float speed() const { return p[6 * PG_GRAIN_TILE]; }
+};
+
+// One LFO frame with all seven shapes: Lfo::process (lfo.rs:172-231) with advance_phase / advance_phase_random (:233-252).
+DEV float mod_lfo_run(PgModLfo& m) {
+  PgLfo l = {m.phase, m.phase_inc, m.waveform};
+  float v;
+  if (m.waveform < 5) v = lfo_run(l);
+  else {
+    if (m.waveform == 5) v = m.sample_hold;
+    else {
+      const float p = 1.57079632679489661923f - l.phase * F32_PI;   // FRAC_PI_2 - phase * PI
+      const float t = (1.0f - sine_approx(p)) * 0.5f;
+      v = m.jitter_current + t * (m.jitter_target - m.jitter_current);
+    }
+    l.phase += l.phase_inc;
+    if (l.phase >= 1.0f) {
+      l.phase -= 1.0f;
+      m.sample_hold = lfo_random_bipolar(m.rng);
+      m.jitter_current = m.jitter_target;
+      m.jitter_target = lfo_random_bipolar(m.rng);
+    }
+  }
+  m.phase = l.phase;
+  return v;
+}
+// Lfo::reset (lfo.rs:89-99): the phase restarts; the random shapes draw again
+DEV void mod_lfo_reset(PgModLfo& m) {
+  m.phase = 0.0f;
+  if (m.waveform >= 5) {
+    m.sample_hold = lfo_random_bipolar(m.rng);
+    m.jitter_current = m.jitter_target;
+    m.jitter_target = lfo_random_bipolar(m.rng);
+  }
+}
+// One slot's contribution to a target's sum (ModulationMatrix::output, matrix.rs:201-231): LFOs are bipolar sources, velocity and keytracking
+// unipolar ones.
+DEV float mod_bipolar_source(float v, int bipolar) { return bipolar ? v : (v + 1.0f) / 2.0f; }
+DEV float mod_unipolar_source(float v, int bipolar) { return bipolar ? (v - 0.5f) * 2.0f : v; }
+
+template <bool MOD>
+DEV float grain_playback_position(const GrainSched& S, float position_mod) {  // granular.rs:446-472
   float base = S.p.step == 0.0f ? S.p.position : S.pool.playhead;
+  if (MOD) { if (position_mod != 0.0f) base += position_mod; }
   if (S.pool.playing_loop_range && S.p.has_loop) base = (float)grain_fold_into_loop_range((double)base, (double)S.p.loop_start, (double)S.p.loop_end);
   const float r = fmodf(base, 1.0f);   // f32::rem_euclid(1.0)
   return r < 0.0f ? r + 1.0f : r;
@@ -99,8 +154,9 @@ DEV float grain_playback_position(const GrainSched& S) {  // granular.rs:446-472
 
 // One frame of the scheduler, in front of the frame's grains: try_trigger_grain, then advance_playhead when step != 0 (granular.rs:693-711).
 // `end`: see GrainSched. Returns the activation (slot == -1: none).
-template <typename EndArray>
-DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& act) {
+// MOD: the voice has a modulation matrix and `m` holds the frame's sums; without one `m` is not looked at.
+template <bool MOD, typename EndArray>
+DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& act, const GrainModFrame& m) {
   act.slot = -1;
   PgGrainPool& P = S.pool;
   const PgGrainParams& p = S.p;
@@ -112,7 +168,7 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
   }
   if (trigger && !P.trigger_new_grains) trigger = false;
   if (trigger && !sequential) {  // update_trigger_phase
-    float density = p.density;   // * (1.0 + density_mod)
+    float density = MOD ? p.density * (1.0f + m.density()) : p.density;
     density = density < 1.0f ? 1.0f : (density > 100.0f ? 100.0f : density);
     P.trigger_phase += density / (float)S.sample_rate;
     if (P.trigger_phase >= 1.0f) P.trigger_phase -= 1.0f; else trigger = false;
@@ -120,18 +176,18 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
   if (trigger) {
     // spray: +/- 1 s at 1.0 (:562-571) — drawn whether or not a slot is free
     const double file_duration = (double)S.n_frames / (double)S.sample_rate;
-    float spray = p.spray;
+    float spray = MOD ? p.spray + m.spray() : p.spray;
     spray = spray < 0.0f ? 0.0f : (spray > 1.0f ? 1.0f : spray);
     const double spray_seconds = (double)spray * 2.0 * (grain_random_f64(P.rng) - 0.5);
     const double spray_variation = spray_seconds / file_duration;
-    double grain_position = (double)grain_playback_position(S) + spray_variation;
+    double grain_position = (double)grain_playback_position<MOD>(S, MOD ? m.position() : 0.0f) + spray_variation;
     if (P.playing_loop_range && p.has_loop) grain_position = grain_fold_into_loop_range(grain_position, (double)p.loop_start, (double)p.loop_end);
     grain_position = grain_rem_euclid(grain_position, 1.0);
     // activate_new_grain: the first inactive slot (:821)
     int index = -1;
     for (int s = 0; s < PG_GRAIN_POOL; ++s) if (end[s] <= f) { index = s; break; }
     if (index >= 0) {
-      float variation = p.variation;
+      float variation = MOD ? p.variation + m.variation() : p.variation;
       variation = variation < 0.0f ? 0.0f : (variation > 1.0f ? 1.0f : variation);
       const float volume_scale = 1.0f - (variation * rng_random_f32(P.rng));
       const float volume = P.volume * volume_scale;
@@ -140,12 +196,12 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
       const float min_scale = 1.0f - (0.75f * variation);
       const float max_scale = 1.0f + (2.0f * variation);
       const float size_scale = min_scale + (max_scale - min_scale) * rng_random_f32(P.rng);
-      float grain_size_ms = p.size;   // * (1.0 + size_mod)
+      float grain_size_ms = MOD ? p.size * (1.0f + m.size()) : p.size;
       grain_size_ms = grain_size_ms < 1.0f ? 1.0f : (grain_size_ms > 1000.0f ? 1000.0f : grain_size_ms);
       const float size_f = grain_size_ms * size_scale * (float)S.sample_rate / 1000.0f;
       uint64_t grain_size = size_f > 0.0f ? (uint64_t)size_f : 0;   // `as usize` saturates
       if (grain_size < 2) grain_size = 2;
-      float pan_spread = p.pan_spread;
+      float pan_spread = MOD ? p.pan_spread + m.pan_spread() : p.pan_spread;
       pan_spread = pan_spread < 0.0f ? 0.0f : (pan_spread > 1.0f ? 1.0f : pan_spread);
       const float panning_spread = pan_spread * (rng_random_f32(P.rng) * 2.0f - 1.0f);
       float panning = P.panning + panning_spread;
@@ -168,8 +224,9 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
       if (sequential) { P.primary = index; S.prim_phase = 0.0; S.prim_inc = act.window_increment; }
     }
   }
-  if (p.step != 0.0f) {  // advance_playhead (:607-640): step * (1.0 + speed_mod) / len
-    P.playhead += p.step / (float)S.n_frames;
+  if (p.step != 0.0f) {  // advance_playhead (:607-640)
+    const float modulated_step = MOD ? p.step * (1.0f + m.speed()) : p.step;
+    P.playhead += modulated_step / (float)S.n_frames;
     if (p.has_loop) {
       if (P.playing_loop_range) P.playhead = (float)grain_fold_into_loop_range((double)P.playhead, (double)p.loop_start, (double)p.loop_end);
       else if (P.playhead >= p.loop_start && P.playhead < p.loop_end) P.playing_loop_range = 1;

@@ -6,6 +6,7 @@
 // here on the host and handed to the kernels as per-launch command lists — and the parameter descriptor
 // logic (pg_params.h). All per-sample work happens in pg_kernels.hip.
 #include "pg_host_internal.h"
+#include "pg_grain_dev.h"   // mod_lfo_reset: the note_on of a voice's modulation matrix runs on the host
 
 // ---- errors ---------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -899,7 +900,8 @@ static int fx_kind_of(pg_graph* g, int effect_id) {  // -1: unknown or removed
 static bool voice_alive(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) != 0; }
 // Seek and speed exist on FilePlaybackHandle only (src/player/handles/file.rs): a host-fed source (the host's own `dyn Source` behind a ring) has
 // neither a position to seek to nor a resampler to re-target — the device would rewind the ring's read position over stale frames.
-static bool voice_is_granular(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 3; }
+static bool voice_is_granular(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) >= 3; }
+static bool voice_has_matrix(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 4; }   // (4: granular with a modulation matrix)
 static bool voice_is_host_fed(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 2; }
 
 int pg_graph_schedule_param(pg_graph* g, int effect_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
@@ -1020,6 +1022,11 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id) {
   return e.on ? (int)e.state.stage : -1;
 }
 // ---- granular voices (src/generator/sampler/granular.rs; pg_k_grain.hip) ----
+// The Xoshiro256++ state an all-zero `rng_state` stands for (pg_granular_params, pg_mod_lfo): SplitMix64 of the fixed seed, four times
+static void rng_default_state(uint64_t out[4]) {
+  uint64_t z = 0x5EED0000ull;
+  for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; out[i] = x ^ (x >> 31); }
+}
 void pg_granular_params_default(pg_granular_params* p) {  // GranularParameters::default (granular.rs:268-283)
   if (!p) return;
   memset(p, 0, sizeof *p);
@@ -1089,7 +1096,7 @@ int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm
   q.has_loop = p->has_loop_range ? 1 : 0; q.loop_start = p->has_loop_range ? p->loop_start : 0.0f; q.loop_end = p->has_loop_range ? p->loop_end : 0.0f;
   PgGrainPool& pool = r->pool;
   if ((p->rng_state[0] | p->rng_state[1] | p->rng_state[2] | p->rng_state[3]) != 0) memcpy(pool.rng, p->rng_state, sizeof pool.rng);
-  else { uint64_t z = 0x5EED0000ull; for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; pool.rng[i] = x ^ (x >> 31); } }
+  else rng_default_state(pool.rng);
   pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
   pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
   pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1;
@@ -1149,6 +1156,127 @@ int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
   }
   return PG_OK;
 }
+// ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
+static_assert(PG_MOD_SOURCES == PG_GMOD_SOURCES && PG_MOD_TARGETS == PG_GMOD_TARGETS, "the header's and the device's matrix agree");
+static float mod_clamp_rate(float rate_hz) { return rate_hz < 0.01f ? 0.01f : (rate_hz > 20.0f ? 20.0f : rate_hz); }   // FloatParameter::clamp_value of ML1R / ML2R (sampler.rs:369-384)
+void pg_modulation_params_default(pg_modulation_params* p) {  // Sampler::modulation_config (sampler.rs:369-427), a note at full velocity
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->lfo[0].rate_hz = 1.0f; p->lfo[0].waveform = 0;
+  p->lfo[1].rate_hz = 2.0f; p->lfo[1].waveform = 1;
+  p->velocity = 1.0f; p->note = 60;
+}
+static int mod_check_route(int source, int target, float amount) {  // ModulationState::set_modulation (state.rs:174-201)
+  if (source < 0 || source >= PG_MOD_SOURCES) return set_error(PG_ERR_PARAMETER, "Unknown modulation source '%d'", source);
+  if (target < 0 || target >= PG_MOD_TARGETS) return set_error(PG_ERR_PARAMETER, "Unknown modulation target '%d'", target);
+  if (!(amount >= -1.0f && amount <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Modulation amount must be in range -1..-1.0 but is %g", (double)amount);
+  return PG_OK;
+}
+int pg_modulation_params_check(const pg_modulation_params* p) {
+  if (!p) return set_error(PG_ERR_PARAMETER, "modulation parameters must not be null");
+  for (int l = 0; l < 2; ++l) {
+    if (p->lfo[l].rate_hz != p->lfo[l].rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", l + 1);
+    if (p->lfo[l].waveform < 0 || p->lfo[l].waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", l + 1, p->lfo[l].waveform);
+  }
+  if (!(p->velocity >= 0.0f && p->velocity <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Velocity must be in range [0.0, 1.0]");
+  if (p->note < 0 || p->note > 127) return set_error(PG_ERR_PARAMETER, "MIDI note must be in range [0, 127]");
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { const int rc = mod_check_route(s, t, p->routes[s][t].amount); if (rc) return rc; }
+  return PG_OK;
+}
+int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_modulation_params* p) {
+  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  drain_control_messages(g);
+  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  HostVoice& hv = g->voices[voice_id];
+  if (hv.gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  // the matrix is created with the voice and note_on belongs to its start (voice.rs:341-373, :181-184): not for a voice that has rendered frames
+  // (see pg_graph_set_voice_envelope)
+  uint64_t end_since_add = 0;
+  for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) { end_since_add = w.second; break; }
+  if (end_since_add > hv.start_time) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: the modulation matrix is attached before the voice starts", voice_id);
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
+  PgGrainMod m;
+  memset(&m, 0, sizeof m);
+  m.on = 1;
+  for (int l = 0; l < 2; ++l) {
+    PgModLfo& o = m.lfo[l];
+    const pg_mod_lfo& in = p->lfo[l];
+    if ((in.rng_state[0] | in.rng_state[1] | in.rng_state[2] | in.rng_state[3]) != 0) memcpy(o.rng, in.rng_state, sizeof o.rng);
+    else rng_default_state(o.rng);
+    // create_matrix: Lfo::new(sample_rate, default rate, default waveform) (state.rs:96-113, lfo.rs:70-86)
+    o.phase = 0.0f;
+    o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
+    // the parameter updates in front of the note: set_rate / set_waveform (lfo.rs:102-119)
+    o.phase_inc = (float)((double)mod_clamp_rate(in.rate_hz) / (double)g->sample_rate);
+    o.waveform = in.waveform;
+  }
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {  // update_target on an empty slot (matrix.rs:75-82)
+    const pg_mod_route& r = p->routes[s][t];
+    if (fabsf(r.amount) >= 0.001f) { m.amount[s][t] = r.amount; m.bipolar[s][t] = r.bipolar ? 1 : 0; }
+  }
+  // SamplerVoiceModulationState::start(note, velocity) = ModulationMatrix::note_on (matrix.rs:394-408)
+  for (int l = 0; l < 2; ++l) mod_lfo_reset(m.lfo[l]);
+  m.velocity = p->velocity;
+  m.note_pitch = (float)p->note / 127.0f;
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, mod), &m, sizeof m, hipMemcpyHostToDevice));
+  hv.mod = true;
+  g->voice_alive_tab.set((size_t)voice_id, 4);
+  return PG_OK;
+}
+// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
+static int mod_message(pg_graph* g, int voice_id, int type, int packed, float value, uint64_t sample_time) {
+  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  if (!voice_has_matrix(g, voice_id)) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = type; m.id = voice_id; m.param = packed; m.value = value; m.sample_time = sample_time;
+  return ctrl_push(g, m);
+}
+int pg_graph_set_voice_modulation(pg_graph* g, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
+  { const int rc = mod_check_route(source, target, amount); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  const bool keep = fabsf(amount) >= 0.001f;   // update_target's threshold (matrix.rs:61): below it the route is removed, or not added
+  return mod_message(g, voice_id, pgc::CT_VOICE_MOD_ROUTE, source | (target << 8) | ((keep && bipolar) ? 1 << 16 : 0), keep ? amount : 0.0f, sample_time);
+}
+int pg_graph_clear_voice_modulation(pg_graph* g, int voice_id, int source, int target, uint64_t sample_time) {  // set_modulation(.., 0.0, false) (state.rs:223-231)
+  return pg_graph_set_voice_modulation(g, voice_id, source, target, 0.0f, 0, sample_time);
+}
+int pg_graph_set_voice_lfo_rate(pg_graph* g, int voice_id, int lfo, float rate_hz, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (rate_hz != rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", lfo + 1);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return mod_message(g, voice_id, pgc::CT_VOICE_LFO_RATE, lfo, mod_clamp_rate(rate_hz), sample_time);
+}
+int pg_graph_set_voice_lfo_waveform(pg_graph* g, int voice_id, int lfo, int waveform, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (waveform < 0 || waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", lfo + 1, waveform);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return mod_message(g, voice_id, pgc::CT_VOICE_LFO_WAVEFORM, lfo | (waveform << 8), 0.0f, sample_time);
+}
+int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_state* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  if (!g->voices[voice_id].mod) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_stream_sync(g->stream));
+  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
+  PgGrainMod m;
+  HIP_TRY(pg_memcpy(&m, (const char*)(g->d_gran + g->voices[voice_id].gran) + offsetof(PgGrainVoice, mod), sizeof m, hipMemcpyDeviceToHost));
+  memset(out, 0, sizeof *out);
+  for (int l = 0; l < 2; ++l) {
+    const PgModLfo& s = m.lfo[l];
+    pg_mod_lfo_state& o = out->lfo[l];
+    o.phase = s.phase; o.phase_inc = s.phase_inc; o.sample_hold = s.sample_hold; o.jitter_current = s.jitter_current; o.jitter_target = s.jitter_target; o.waveform = s.waveform;
+    memcpy(o.rng_state, s.rng, sizeof o.rng_state);
+  }
+  out->velocity = m.velocity; out->note_pitch = m.note_pitch;
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
+  for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
+  return PG_OK;
+}
 int pg_graph_remove_voice(pg_graph* g, int voice_id) {  // MixerMessage::RemoveSource (mixed.rs:149-151,400-402)
   const int rc = voice_message(g, voice_id, pgc::CT_VOICE_REMOVE, 0.0f, 0.0, 0);
   // the id is dead for every later call from here on (a second remove, a volume change: PG_ERR_NOT_FOUND as the header says), not only once the
@@ -1206,7 +1334,8 @@ static void drain_control_messages(pg_graph* g) {
           mx.messages.erase(std::remove_if(mx.messages.begin(), mx.messages.end(), [&](const PgCmd& x) { return x.param == m.id; }), mx.messages.end());
           // events already queued for the source stay the mixer's events: when they come due they find no source (mixed.rs:810-845) but still
           // split the block there — like the events of a removed effect
-          for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK || e.cmd.type == CMD_VOICE_RELEASE) && e.cmd.param == m.id) {
+          for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK || e.cmd.type == CMD_VOICE_RELEASE ||
+                                         e.cmd.type == CMD_VOICE_MOD_ROUTE || e.cmd.type == CMD_VOICE_LFO_RATE || e.cmd.type == CMD_VOICE_LFO_WAVEFORM) && e.cmd.param == m.id) {
             e.cmd.type = CMD_NOP; e.cmd.target = 0;
             if (hv.mixer == 0) e.cmd.param = -1;
           }
@@ -1224,6 +1353,9 @@ static void drain_control_messages(pg_graph* g) {
         else if (m.type == pgc::CT_VOICE_PAN) { c.type = CMD_VOICE_PAN; c.value = m.value; }
         else if (m.type == pgc::CT_VOICE_SPEED) { c.type = CMD_VOICE_SPEED; c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }
         else if (m.type == pgc::CT_VOICE_RELEASE) { c.type = CMD_VOICE_RELEASE; c.value64 = m.sample_time; }
+        else if (m.type == pgc::CT_VOICE_MOD_ROUTE) { c.type = CMD_VOICE_MOD_ROUTE; c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }
+        else if (m.type == pgc::CT_VOICE_LFO_RATE) { c.type = CMD_VOICE_LFO_RATE; c.value = (float)((double)m.value / (double)g->sample_rate); c.value64 = (uint64_t)(uint32_t)m.param; }   // Lfo::set_rate (lfo.rs:102-104)
+        else if (m.type == pgc::CT_VOICE_LFO_WAVEFORM) { c.type = CMD_VOICE_LFO_WAVEFORM; c.value64 = (uint64_t)(uint32_t)m.param; }
         else { c.type = CMD_VOICE_SEEK; memcpy(&c.value64, &m.dvalue, 8); }
         push_event(g, hv.mixer, m.sample_time, c);
       } break;
@@ -2043,7 +2175,8 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
         // deferred for those alone is back on its kernel in the next block, so the host need not wait for the device to say so — offline
         // calls keep their super-block launches between such commands (notes that stop and start: bench.py --workload dyn --churn).
         bool may_ramp = false;
-        for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK || c.type == CMD_VOICE_RELEASE);
+        for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK || c.type == CMD_VOICE_RELEASE ||
+                                                         c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM);   // (the matrix's commands reach pg_grain_kernel only)
         // (the round AFTER this one is the first whose scan sees what the commands left behind: this round's own count of state-deferred units
         // was taken in front of them)
         if (may_ramp) g->last_change_round = sp.round + 1;

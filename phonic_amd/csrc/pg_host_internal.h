@@ -232,6 +232,7 @@ struct HostVoice {
   bool env_live = false;           // ... and the voice has not ended yet: its unit is rendered by the exact kernel (PgUnit::static_defer)
   int gran = -1;                   // granular voice (pg_graph_add_granular_voice): its record in pg_graph::d_gran; d_pcm = the mono buffer, d_stage = the staging buffer
   bool gran_live = false;          // ... and pg_grain_kernel has not reported the voice ended: it renders the voice, the exact kernel its unit
+  bool mod = false;                // ... with a modulation matrix (pg_graph_set_voice_modulation_matrix): PgGrainVoice::mod of its record
 };
 struct HostMixer {
   int unit_slot = -1;              // sub-mixer unit; for the main mixer: the bus unit

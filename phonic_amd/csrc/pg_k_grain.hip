@@ -5,6 +5,9 @@
 // read from the launch's command list and applied at their frames.
 //
 // Per tile of PG_GRAIN_TILE frames (pg_grain_dev.h has the arithmetic):
+//   0  voices with a modulation matrix only (pg_graph_set_voice_modulation_matrix): one lane per LFO walks its f32 phase recurrence, wraps and
+//      draws over the tile's rendered frames and leaves the raw values in LDS; then one lane per (target, frame) forms the target's sum in slot
+//      order from the 4 x 7 routing table as of its frame. Phase 1 reads seven floats per frame, nothing else of the matrix is in its walk;
 //   1  lane 0 walks the scheduler frame by frame and leaves the activations, one slot per frame at most, in LDS;
 //   2  lane s walks slot s: takes its activations at their frames, steps Grain::process's f64 recurrences and leaves, per frame, the f32 read
 //      position and the window table's index and fraction in LDS (12 bytes per slot and frame: 38 KB for 100 slots x 32 frames); the slot's
@@ -22,8 +25,12 @@ using namespace pgd;
 #define GRAIN_CMD_CAP 64
 
 __device__ __forceinline__ bool grain_cmd_matches(const PgCmd& c, int voice) {
-  return c.target == voice && (c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_SPEED || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_RELEASE);
+  return c.target == voice && (c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_SPEED || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_RELEASE ||
+                               c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM);
 }
+// A route command's source and target, -1 when either is out of range (the host checks them: nothing out of range indexes the table)
+__device__ __forceinline__ int grain_route_source(const PgCmd& c) { const uint32_t s = (uint32_t)(c.value64 & 0xff); return s < PG_GMOD_SOURCES ? (int)s : -1; }
+__device__ __forceinline__ int grain_route_target(const PgCmd& c) { const uint32_t t = (uint32_t)((c.value64 >> 8) & 0xff); return t < PG_GMOD_TARGETS ? (int)t : -1; }
 
 __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   __shared__ float s_lut[PG_GRAIN_LUT_N];
@@ -38,6 +45,14 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   __shared__ int s_wcnt[2];
   __shared__ int s_cmd[GRAIN_CMD_CAP];
   __shared__ int s_ncmd;
+  // phase 0 (voices with a modulation matrix): the LFOs' raw values and the targets' sums of the tile, the routing table and the LFO records
+  __shared__ float s_lfo[2][GT];
+  __shared__ float s_mod[PG_GMOD_TARGETS][GT];
+  __shared__ float s_ramt[PG_GMOD_SOURCES][PG_GMOD_TARGETS];
+  __shared__ int s_rbip[PG_GMOD_SOURCES][PG_GMOD_TARGETS];
+  __shared__ PgModLfo s_lfo_state[2];
+  __shared__ float s_mstatic[2];   // velocity, note_pitch
+  __shared__ int s_lfo_cursor[2];  // the LFO lanes' places in the command list
 
   const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (blockIdx.x >= L.n_live) return;
@@ -87,6 +102,19 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   }
   const uint64_t start_time = V->start_time;
   const int has_env = V->has_env;
+  const bool has_mod = V->mod.on != 0;   // (the same for every lane of the workgroup)
+  int route_cursor = 0;
+  if (has_mod) {
+    if (tid < PG_GMOD_SOURCES * PG_GMOD_TARGETS) { (&s_ramt[0][0])[tid] = (&V->mod.amount[0][0])[tid]; (&s_rbip[0][0])[tid] = (&V->mod.bipolar[0][0])[tid]; }
+    if (tid == 64 || tid == 128) { s_lfo_state[(tid >> 6) - 1] = V->mod.lfo[(tid >> 6) - 1]; s_lfo_cursor[(tid >> 6) - 1] = 0; }
+    if (tid == 192) { s_mstatic[0] = V->mod.velocity; s_mstatic[1] = V->mod.note_pitch; }
+  }
+  // the voice's next command at or behind `cursor` in the launch's list (-1: none): a lane's own walk
+  auto peek_cmd = [&](int& cursor) -> int {
+    if (!cmd_overflow) return cursor < n_cmd ? s_cmd[cursor] : -1;
+    while (cursor < L.n_cmds && !grain_cmd_matches(L.cmds[cursor], voice)) ++cursor;
+    return cursor < L.n_cmds ? cursor : -1;
+  };
   __syncthreads();
 
   for (uint32_t base = 0; base < L.n; base += GT) {
@@ -97,6 +125,66 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
       s_vol[tid] = g.volume; s_pan[tid] = g.panning; s_touched[tid] = 0;
     }
     __syncthreads();
+    // ---- phase 0: the modulation matrix ----
+    if (has_mod) {
+      int otid = tid;
+      asm volatile("" : "+v"(otid));   // (opaque: the lane's LDS addresses below are formed here, not in front of the tile loop to be kept in registers through phases 1-3)
+      if (otid == 64 || otid == 128) {  // one lane per LFO, in waves of their own
+        const int l = (otid >> 6) - 1;
+        PgModLfo m = s_lfo_state[l];
+        int lfo_cursor = s_lfo_cursor[l];
+        for (int f = 0; f < tn; ++f) {
+          const uint32_t lf = base + (uint32_t)f;
+          for (;;) {  // Lfo::set_rate / set_waveform in front of this frame (matrix.rs:417-429)
+            const int ci = peek_cmd(lfo_cursor);
+            if (ci < 0) break;
+            const PgCmd c = L.cmds[ci];
+            if (c.frame > lf) break;
+            ++lfo_cursor;
+            if (c.type == CMD_VOICE_LFO_RATE && (int)(c.value64 & 0xff) == l) m.phase_inc = c.value;
+            else if (c.type == CMD_VOICE_LFO_WAVEFORM && (int)(c.value64 & 0xff) == l) { const uint32_t w = (uint32_t)((c.value64 >> 8) & 0xff); if (w < 7) m.waveform = (int32_t)w; }
+          }
+          if (tile_t + (uint64_t)f >= start_time) s_lfo[l][f] = mod_lfo_run(m);
+        }
+        s_lfo_state[l] = m; s_lfo_cursor[l] = lfo_cursor;
+      }
+      // the sums, in segments cut at the tile's route commands: every frame takes exactly the routes set in front of it. The walk over the
+      // command list is the same in every lane; lane 0 changes the table between two segments.
+      const int mk = otid / GT, mf = otid % GT;   // lane (target, frame)
+      for (int seg0 = 0;;) {
+        for (;;) {  // ModulationMatrixSlot::update_target (matrix.rs:60-83) in front of frame seg0; the other commands are not this walk's
+          const int ci = peek_cmd(route_cursor);
+          if (ci < 0 || L.cmds[ci].frame > base + (uint32_t)seg0) break;
+          ++route_cursor;
+          if (tid == 0 && L.cmds[ci].type == CMD_VOICE_MOD_ROUTE) {
+            const PgCmd c = L.cmds[ci];
+            const int sr = grain_route_source(c), tg = grain_route_target(c);
+            if (sr >= 0 && tg >= 0) { s_ramt[sr][tg] = c.value; s_rbip[sr][tg] = c.value != 0.0f && ((c.value64 >> 16) & 1) ? 1 : 0; }
+          }
+        }
+        int seg1 = tn;
+        for (int cur = route_cursor;;) {  // the next route command inside the tile ends the segment
+          const int ci = peek_cmd(cur);
+          if (ci < 0 || L.cmds[ci].frame >= base + (uint32_t)tn) break;
+          if (L.cmds[ci].type == CMD_VOICE_MOD_ROUTE) { seg1 = (int)(L.cmds[ci].frame - base); break; }
+          ++cur;
+        }
+        __syncthreads();   // (the LFO lanes' values and lane 0's table)
+        if (mk < PG_GMOD_TARGETS && mf >= seg0 && mf < seg1 && tile_t + (uint64_t)mf >= start_time) {
+          // ModulationMatrix::output (matrix.rs:194-303): LFO 1, LFO 2, velocity, keytracking — each only if it routes to the target
+          float total = 0.0f;
+          if (s_ramt[0][mk] != 0.0f) total += mod_bipolar_source(s_lfo[0][mf], s_rbip[0][mk]) * s_ramt[0][mk];
+          if (s_ramt[1][mk] != 0.0f) total += mod_bipolar_source(s_lfo[1][mf], s_rbip[1][mk]) * s_ramt[1][mk];
+          if (s_ramt[2][mk] != 0.0f) total += mod_unipolar_source(s_mstatic[0], s_rbip[2][mk]) * s_ramt[2][mk];
+          if (s_ramt[3][mk] != 0.0f) total += mod_unipolar_source(s_mstatic[1], s_rbip[3][mk]) * s_ramt[3][mk];
+          s_mod[mk][mf] = total;
+          if (mf == tn - 1) V->mod.last[mk] = total;
+        }
+        __syncthreads();   // (phase 1, or lane 0's next change of the table, begins behind it)
+        if (seg1 >= tn) break;
+        seg0 = seg1;
+      }
+    }
     // ---- phase 1: the scheduler ----
     if (tid == 0) {
       int max_end = -1;
@@ -115,12 +203,15 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
           else if (c.type == CMD_VOICE_PAN) S.pool.panning = c.value;
           else if (c.type == CMD_VOICE_SPEED) S.pool.speed = __longlong_as_double((long long)c.value64);   // (the glide is ignored: SamplerVoice::set_speed hands the pool the speed alone)
           else if (c.type == CMD_VOICE_STOP) stop_time = c.value64;
-          else if (!has_env) S.pool.trigger_new_grains = 0;   // CMD_VOICE_RELEASE without an envelope: SamplerVoice::stop -> GrainPool::stop
+          else if (c.type == CMD_VOICE_RELEASE && !has_env) S.pool.trigger_new_grains = 0;   // without an envelope: SamplerVoice::stop -> GrainPool::stop
+          // (the modulation matrix's commands were taken in phase 0)
         }
         if (t < start_time) { s_act[f].slot = -1; continue; }
         if (t >= stop_time) S.pool.trigger_new_grains = 0;
         GrainActivation a;
-        grain_sched_frame(S, s_end, f, a);
+        const GrainModFrame m = {&s_mod[0][f]};
+        if (has_mod) grain_sched_frame<true>(S, s_end, f, a, m);
+        else grain_sched_frame<false>(S, s_end, f, a, m);
         if (a.slot >= 0) { s_act[f] = a; s_touched[a.slot] = 1; }
         else s_act[f].slot = -1;
         if (!S.pool.trigger_new_grains && exhausted_at == UINT64_MAX) {
@@ -180,6 +271,10 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   }
   if (tid < PG_GRAIN_POOL) V->grains[tid] = g;
   if (tid == 0) { V->pool = S.pool; V->stop_time = stop_time; V->exhausted_at = exhausted_at; V->stage_pos = L.chunk_t0; }
+  if (has_mod) {  // (the last tile's barriers are behind every lane)
+    if (tid < PG_GMOD_SOURCES * PG_GMOD_TARGETS) { (&V->mod.amount[0][0])[tid] = (&s_ramt[0][0])[tid]; (&V->mod.bipolar[0][0])[tid] = (&s_rbip[0][0])[tid]; }
+    if (tid == 64 || tid == 128) V->mod.lfo[(tid >> 6) - 1] = s_lfo_state[(tid >> 6) - 1];
+  }
 }
 
 hipError_t pg_launch_grain(const PgGrainLaunch& L, hipStream_t stream) {

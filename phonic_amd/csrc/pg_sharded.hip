@@ -473,6 +473,36 @@ int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_
   SHARDED_VOICE(s, voice_id, pk);
   return pg_graph_release_voice(s->shards[shard_of(pk)], local_of(pk), sample_time);
 }
+// the modulation matrix of a granular voice (pg_graph_set_voice_modulation_matrix and its timed calls): on the voice's shard
+int pg_sharded_set_voice_modulation_matrix(pg_sharded_graph* s, int voice_id, const pg_modulation_params* p) {
+  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }   // (before the id: parameter errors never depend on the graph)
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_modulation_matrix(s->shards[shard_of(pk)], local_of(pk), p);
+}
+int pg_sharded_set_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
+  if (!s) return pg_graph_set_voice_modulation(nullptr, 0, source, target, amount, bipolar, 0);   // (the parameter error, or the null handle's)
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_modulation(s->shards[shard_of(pk)], local_of(pk), source, target, amount, bipolar, sample_time);
+}
+int pg_sharded_clear_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, uint64_t sample_time) {
+  return pg_sharded_set_voice_modulation(s, voice_id, source, target, 0.0f, 0, sample_time);
+}
+int pg_sharded_set_voice_lfo_rate(pg_sharded_graph* s, int voice_id, int lfo, float rate_hz, uint64_t sample_time) {
+  if (!s) return pg_graph_set_voice_lfo_rate(nullptr, 0, lfo, rate_hz, 0);   // (the parameter error, or the null handle's)
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_lfo_rate(s->shards[shard_of(pk)], local_of(pk), lfo, rate_hz, sample_time);
+}
+int pg_sharded_set_voice_lfo_waveform(pg_sharded_graph* s, int voice_id, int lfo, int waveform, uint64_t sample_time) {
+  if (!s) return pg_graph_set_voice_lfo_waveform(nullptr, 0, lfo, waveform, 0);
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_lfo_waveform(s->shards[shard_of(pk)], local_of(pk), lfo, waveform, sample_time);
+}
+int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modulation_state* out) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_voice_modulation_state(s->shards[shard_of(pk)], local_of(pk), out);
+}
 int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) {
   if (!s || voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return -1;
   const int32_t pk = s->voice_map.get((size_t)voice_id);
