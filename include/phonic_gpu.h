@@ -296,9 +296,11 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
  * voices"); each grain's per-frame stereo terms are the reference's bits, the f32 sum over the grains of a frame runs in ascending slot order.
  * The voice's modulation matrix is pg_graph_set_voice_modulation_matrix below; without one every `*_mod` input of try_trigger_grain /
  * advance_playhead is 0.0 — what a sampler without routings feeds.
+ * The granular parameters and the loop range change while the voice plays: pg_graph_set_voice_granular_parameter / _grain_loop_range below.
  * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the mono down-mix and resample of
  * create_granular_sample_buffer (sampler.rs:908-952: the caller hands over the mono f32 buffer at the graph's rate that function would have
- * produced); changing granular parameters after the voice has started.
+ * produced); the Sampler's base transpose, finetune, volume and panning parameters (pg_graph_set_voice_speed / _volume / _panning carry their
+ * effect); AHDSR parameter changes on a running envelope.
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
  * 2 Triangle, 3 Tukey, 4 Trapezoid, 5 Exponential, 6 RampUp, 7 RampDown (:61-70); size in ms, density in Hz, playback_direction 0 Forward,
  * 1 Backward, 2 Random (:19-26); plus GrainPool::sample_loop_range (:357, voice.rs:355-360) as has_loop_range / loop_start / loop_end,
@@ -350,13 +352,43 @@ typedef struct pg_grain_state {
   float trigger_phase, playhead;
   int32_t playing_loop_range, trigger_new_grains;
   int32_t primary_slot;      /* primary_grain_index, -1: None */
-  int32_t reserved;
+  int32_t overlap_mode;      /* the pool's own copy (granular.rs:346): Cloud from GrainPool::new (:399) until the first rendered frame takes the parameters' (:535-538) */
   double speed;
   float volume, panning;
   uint64_t rng_state[4];
   pg_grain_slot slots[PG_GRAIN_POOL_SIZE];
 } pg_grain_state;
 int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out);
+
+/* The granular parameters while the voice plays: Sampler::GRAIN_* (src/generator/sampler.rs:219-296), ordinary automatable parameters in the
+ * reference — GeneratorPlaybackHandle::set_parameter(id, value, sample_time) -> Sampler::set_granular_parameter (:299-360, :1132-1147) — and the
+ * sampler's loop range (SamplerMessage::SetLoopRange, sampler.rs:1246-1270 -> GrainPool::set_loop_range, granular.rs:516-518).
+ * pg_granular_param_count / pg_granular_param: the ten descriptors in Sampler::granular_parameters() order — GOVM Overlap Mode, GWND Window,
+ * GSIZ Grain Size, GDEN Density, GVAR Variation, GSPY Spray, GPAN Pan Spread, GDIR Direction, GPOS Position, GSTP Step — as the record
+ * pg_effect_kind_param returns; they touch no graph and no device. (GWND's descriptor default is Hann; GranularParameters::default() is Triangle.)
+ * pg_graph_set_voice_granular_parameter: `fourcc` is one of the ten ids. A raw float value is clamped to the descriptor's range
+ * (Sampler::parameter_update_value, sampler.rs:862-883); a normalized one is clamped to 0..1 and denormalized, min + scaling.scale(n) * (max - min)
+ * (src/parameter/float.rs:137-141; GSIZ and GDEN scale with Exponential(2.0)). A normalized enum value is (n * (count - 1)).round()
+ * (src/parameter/enum.rs:154); a raw enum value is the variant's index, as for pg_graph_schedule_param — one out of range is ignored (PG_OK).
+ * pg_graph_set_voice_grain_loop_range: GrainPool::sample_loop_range becomes (loop_start, loop_end), normalised to [0, 1] as in
+ * pg_granular_params, or None (has_loop_range 0); it accepts what pg_granular_params_check accepts. Only sample_loop_range changes:
+ * playing_loop_range, the playhead and the living grains keep what they have.
+ * Both are scheduled like pg_graph_set_voice_modulation: events of the voice's mixer that cut its chunk and act in front of frame `sample_time`
+ * (0: the next write's first frame), several at one frame in the order of the calls; any thread. What a change means for the grains is the
+ * reference's: a grain keeps the window and the loop range it was activated with (granular.rs:823, :1038-1047); the pool follows a new overlap
+ * mode at the next frame and forgets its primary grain (:535-538); the crossfade point is the current window's (:547); `position` places the
+ * grains only while step == 0 (:448-452) and the playhead keeps its value while it does. A command in front of the voice's start time changes the
+ * parameters, and a new position then is the playhead's too: GrainPool::start reads it at note-on (:487). A voice whose pool has run dry takes no
+ * parameters any more. In the reference these calls reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
+ * PG_ERR_PARAMETER: an unknown fourcc, a NaN value, loop points outside [0, 1] or NaN, a null handle — checked in that order, before anything
+ * touches a device; PG_ERR_NOT_FOUND: no such voice, or not a granular voice.
+ * pg_graph_voice_granular_params: the parameters and the loop range as the device holds them (rng_state reads 0). Waits for the graph's stream.
+ * PG_ERR_NOT_FOUND: not a granular voice. */
+int pg_granular_param_count(void);
+int pg_granular_param(int index, pg_param_desc* out);
+int pg_graph_set_voice_granular_parameter(pg_graph* g, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
+int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time);
+int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out);
 
 /* The modulation matrix of a granular voice: the ModulationMatrix every granular sampler voice owns (src/generator/sampler/voice.rs:341-373,
  * src/modulation/matrix.rs, src/generator/sampler/modulation.rs), run in front of the grain engine (voice.rs:412-427) — on the device as phase 0
@@ -374,8 +406,8 @@ int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out);
  * has ended. A release touches no modulation source (note_off reaches envelope slots, and the sampler has none, sampler/modulation.rs:101-103).
  * In the reference the timed calls below reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
  * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the Sampler's note, voice-allocation and stealing layer;
- * playback-position status events (pg_modulation_state::last[5] is the value they would use, voice.rs:435-446); changing the granular
- * parameters themselves after the voice has started. */
+ * playback-position status events (pg_modulation_state::last[5] is the value they would use, voice.rs:435-446). (The granular parameters
+ * themselves change through pg_graph_set_voice_granular_parameter above; a route's sum applies to the parameter's value as of its frame.) */
 #define PG_MOD_SOURCES 4
 #define PG_MOD_TARGETS 7
 typedef struct pg_mod_lfo   { float rate_hz; int32_t waveform; uint64_t rng_state[4]; } pg_mod_lfo;   /* waveform: LfoWaveform 0..6 (lfo.rs:35-47): Sine, Triangle, RampUp, RampDown, Square, Random, SmoothRandom */
@@ -585,6 +617,10 @@ int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id);
  * volume, panning, speed, stop, release, envelope and seek reach a granular voice through the calls above, as on the plain graph */
 int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt);
 int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out);
+/* pg_graph_set_voice_granular_parameter / _set_voice_grain_loop_range / _voice_granular_params on the voice's shard */
+int pg_sharded_set_voice_granular_parameter(pg_sharded_graph* s, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
+int pg_sharded_set_voice_grain_loop_range(pg_sharded_graph* s, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time);
+int pg_sharded_voice_granular_params(pg_sharded_graph* s, int voice_id, pg_granular_params* out);
 /* pg_graph_set_voice_modulation_matrix / _set_voice_modulation / _clear_voice_modulation / _set_voice_lfo_rate / _set_voice_lfo_waveform /
  * _voice_modulation_state (src/modulation/matrix.rs, src/generator/sampler/modulation.rs) on the voice's shard */
 int pg_sharded_set_voice_modulation_matrix(pg_sharded_graph* s, int voice_id, const pg_modulation_params* p);

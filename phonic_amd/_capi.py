@@ -155,7 +155,7 @@ class GrainSlot(C.Structure):
 class GrainState(C.Structure):
     """pg_grain_state: the GrainPool's scalars and its 100 grains."""
     _fields_ = [("trigger_phase", C.c_float), ("playhead", C.c_float), ("playing_loop_range", C.c_int32), ("trigger_new_grains", C.c_int32), ("primary_slot", C.c_int32),
-                ("reserved", C.c_int32), ("speed", C.c_double), ("volume", C.c_float), ("panning", C.c_float), ("rng_state", C.c_uint64 * 4), ("slots", GrainSlot * GRAIN_POOL_SIZE)]
+                ("overlap_mode", C.c_int32), ("speed", C.c_double), ("volume", C.c_float), ("panning", C.c_float), ("rng_state", C.c_uint64 * 4), ("slots", GrainSlot * GRAIN_POOL_SIZE)]
 
 
 def grain_state_dict(st):
@@ -171,8 +171,33 @@ def grain_state_dict(st):
         "active": col("active", np.int32), "samples_remaining": col("samples_remaining", np.int64), "position": col("position", np.float64),
         "increment": col("increment", np.float64), "window_phase": col("window_phase", np.float64), "window_increment": col("window_increment", np.float64),
         "volume_g": col("volume", np.float32), "panning_g": col("panning", np.float32), "window_mode": col("window_mode", np.int32),
-        "has_loop": col("has_loop_range", np.int32),
+        "has_loop": col("has_loop_range", np.int32), "overlap_mode": int(st.overlap_mode),
     }
+
+
+GRANULAR_PARAM_IDS = ("GOVM", "GWND", "GSIZ", "GDEN", "GVAR", "GSPY", "GPAN", "GDIR", "GPOS", "GSTP")   # Sampler::granular_parameters() (sampler.rs:283-296)
+
+
+def granular_param_descs():
+    """The ten descriptors of pg_granular_param as dicts, in Sampler::granular_parameters() order. No device."""
+    lib = load()
+    out = []
+    for i in range(lib.pg_granular_param_count()):
+        d = ParamDesc()
+        if lib.pg_granular_param(i, C.byref(d)) != 0:
+            raise RuntimeError((lib.pg_last_error_message() or b"").decode())
+        out.append({"id": d.fourcc.to_bytes(4, "big").decode(), "name": d.name.decode(), "type": int(d.type), "min": float(d.min), "max": float(d.max),
+                    "default": float(d.default_value), "scaling": int(d.scaling), "scaling_arg0": float(d.scaling_arg0), "n_values": int(d.n_values)})
+    return out
+
+
+def granular_params_dict(p):
+    """A GranularParams read back with pg_graph_voice_granular_params as numpy scalars (the layout tests/granular_params_model.py's params_state() uses)."""
+    import numpy as np
+
+    return {"overlap_mode": int(p.overlap_mode), "window": int(p.window), "size": np.float32(p.size), "density": np.float32(p.density), "variation": np.float32(p.variation),
+            "spray": np.float32(p.spray), "pan_spread": np.float32(p.pan_spread), "playback_direction": int(p.playback_direction), "position": np.float32(p.position),
+            "step": np.float32(p.step), "has_loop_range": int(p.has_loop_range), "loop_start": np.float32(p.loop_start), "loop_end": np.float32(p.loop_end)}
 
 
 MOD_SOURCES, MOD_TARGETS = 4, 7
@@ -478,6 +503,17 @@ def load():
         fn = getattr(lib, prefix + "voice_grain_state")
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int, P(GrainState)]
+    lib.pg_granular_param_count.restype = C.c_int
+    lib.pg_granular_param_count.argtypes = []
+    lib.pg_granular_param.restype = C.c_int
+    lib.pg_granular_param.argtypes = [C.c_int, P(ParamDesc)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        for name, args in (("set_voice_granular_parameter", [C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64]),
+                           ("set_voice_grain_loop_range", [C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64]),
+                           ("voice_granular_params", [C.c_int, P(GranularParams)])):
+            fn = getattr(lib, prefix + name)
+            fn.restype = C.c_int
+            fn.argtypes = [vp] + args
     lib.pg_modulation_params_default.restype = None
     lib.pg_modulation_params_default.argtypes = [P(ModulationParams)]
     lib.pg_modulation_params_check.restype = C.c_int

@@ -31,6 +31,9 @@ enum CtrlType : int32_t {
   CT_VOICE_MOD_ROUTE = 10,    // param = source | target << 8 | bipolar << 16, value = amount (0: remove the route)
   CT_VOICE_LFO_RATE = 11,     // param = lfo, value = rate in Hz, clamped
   CT_VOICE_LFO_WAVEFORM = 12, // param = lfo | waveform << 8
+  // the granular parameters and loop range of a granular voice, events (GeneratorPlaybackHandle::set_parameter(GOVM .. GSTP), SamplerMessage::SetLoopRange)
+  CT_VOICE_GRAIN_PARAM = 13,  // param = index in Sampler::granular_parameters() order, value = resolved raw value
+  CT_VOICE_GRAIN_LOOP = 14,   // param = has_loop_range, value = loop_start, value2 = loop_end
 };
 
 struct CtrlMsg {

@@ -269,9 +269,10 @@ struct PgGrainPool {           // the mutable scalars of GrainPool (granular.rs:
   uint64_t rng[4];             // SmallRng = Xoshiro256++
   double speed;
   float trigger_phase, playhead, volume, panning;
-  int32_t playing_loop_range, trigger_new_grains, primary /* primary_grain_index, -1: None */, pad;
+  int32_t playing_loop_range, trigger_new_grains, primary /* primary_grain_index, -1: None */;
+  int32_t overlap_mode;        // the pool's own copy (granular.rs:346): Cloud from GrainPool::new until the first frame's try_trigger_grain takes the parameters' (:535-538)
 };
-struct PgGrainParams {         // GranularParameters (granular.rs:241-266) + GrainPool::sample_loop_range; fixed once the voice exists
+struct PgGrainParams {         // GranularParameters (granular.rs:241-266) + GrainPool::sample_loop_range; CMD_VOICE_GRAIN_PARAM / _LOOP change them while the voice plays
   int32_t overlap_mode, window;
   float size, density, variation, spray, pan_spread;
   int32_t direction;
@@ -399,7 +400,13 @@ enum PgCmdType {
   CMD_VOICE_MOD_ROUTE = 12,     // value = amount (0.0: remove the route), value64 = source | target << 8 | bipolar << 16   (ModulationMatrixSlot::update_target)
   CMD_VOICE_LFO_RATE = 13,      // value = phase_inc = (rate as f64 / sample_rate as f64) as f32, value64 = lfo                (Lfo::set_rate)
   CMD_VOICE_LFO_WAVEFORM = 14,  // value64 = lfo | waveform << 8                                                               (Lfo::set_waveform)
+  // the granular parameters and loop range of a granular voice (target = voice index; pg_grain_kernel applies them in front of `frame`, the unit
+  // kernels ignore them):
+  CMD_VOICE_GRAIN_PARAM = 15,   // value = the raw value (an enum's index as a float), value64 = index in Sampler::granular_parameters() order   (Sampler::set_granular_parameter)
+  CMD_VOICE_GRAIN_LOOP = 16,    // value = loop_start, value64 = has_loop | f32 bits of loop_end << 32                          (GrainPool::set_loop_range)
 };
+// CMD_VOICE_GRAIN_PARAM's index: Sampler::granular_parameters() (sampler.rs:283-296)
+enum { PG_GP_OVERLAP_MODE = 0, PG_GP_WINDOW, PG_GP_SIZE, PG_GP_DENSITY, PG_GP_VARIATION, PG_GP_SPRAY, PG_GP_PAN_SPREAD, PG_GP_DIRECTION, PG_GP_POSITION, PG_GP_STEP, PG_GP_COUNT };
 #define PG_MAX_CALLS 64  // calls of one sub-mixer per launch round (bits of PgUnit::call_audible); the host bounds the round accordingly
 struct PgCmd {
   int32_t type, unit, target, param;

@@ -325,6 +325,16 @@ int pg_effect_kind_param(int kind, int index, pg_param_desc* out) {
   out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
   return PG_OK;
 }
+// Sampler::granular_parameters() (sampler.rs:283-296): the same record, no device
+int pg_granular_param_count(void) { return PG_GP_COUNT; }
+int pg_granular_param(int index, pg_param_desc* out) {
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (index < 0 || index >= PG_GP_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
+  const ParamSpec& p = GRANULAR_PARAMS[index];
+  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
+  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  return PG_OK;
+}
 void pg_voice_options_default(pg_voice_options* o) {  // FilePlaybackOptions::default()  file.rs:94-112
   memset(o, 0, sizeof *o);
   o->volume = 1.0f; o->panning = 0.0f; o->speed = 1.0;

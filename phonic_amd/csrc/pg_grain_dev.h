@@ -16,7 +16,10 @@
 // phase 0 of pg_grain_kernel) to grain_sched_frame<true>, which applies them as the reference writes them, `x + 0.0` and `x * (1.0 + 0.0)` of
 // a matrix without routes included. A voice without one takes grain_sched_frame<false>: every `*_mod` argument of try_trigger_grain /
 // advance_playhead is 0.0 there, and since `x + 0.0` and `x * (1.0 + 0.0)` leave every finite x as it is those operations are left out.
-// Out of scope (include/phonic_gpu.h says so too): parameter changes after the voice has started; playback-position status events.
+// The granular parameters and the loop range change while the voice plays (pg_graph_set_voice_granular_parameter / _grain_loop_range): the
+// scheduler lane applies the commands to GrainSched::p in front of their frames; what a change makes live is in grain_sched_frame (the pool's own
+// overlap_mode, the crossfade point of the current window) and in the activation (the grain keeps the window and loop range it was born with).
+// Out of scope (include/phonic_gpu.h says so too): playback-position status events.
 //
 // Random draws are rand 0.9's on SmallRng = Xoshiro256++ as rand's documentation describes them (unverified against the crate's source, which
 // this project does not hold): random::<f32>() = (next_u64 >> 40) * 2^-24 (rng_random_f32), random::<f64>() = (next_u64 >> 11) * 2^-53,
@@ -89,7 +92,8 @@ struct GrainActivation {
   uint64_t samples_remaining;
   float volume, panning;
   int32_t slot;           // -1: no activation at this frame
-  int32_t has_loop;
+  int16_t has_loop;
+  int16_t window;         // parameters.window as the grain is activated (:823): the grain's own for its whole life
 };
 
 // The seven sums of the matrix for one frame, in the targets' order (SamplerVoiceModulationState::output, sampler/modulation.rs:237-247).
@@ -160,9 +164,9 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
   act.slot = -1;
   PgGrainPool& P = S.pool;
   const PgGrainParams& p = S.p;
-  const bool sequential = p.overlap_mode == 1;
+  if (P.overlap_mode != p.overlap_mode) { P.overlap_mode = p.overlap_mode; P.primary = -1; }   // detect mode changes (:535-538)
+  const bool sequential = P.overlap_mode == 1;   // (the pool's copy: :541, :794, :596)
   bool trigger = true;
-  // (the pool's overlap_mode follows the parameters' at the first frame and primary_grain_index starts as None: nothing to do, :535-538)
   if (sequential && P.primary >= 0 && end[P.primary] > f) {
     if (S.prim_phase < (double)grain_crossfade_point(p.window)) trigger = false;   // block the new grain until the primary reaches its crossfade point
   }
@@ -215,9 +219,11 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
       act.volume = volume < 0.0f ? 0.0f : (volume > 100.0f ? 100.0f : volume);
       act.panning = panning;
       act.samples_remaining = grain_size;
-      act.has_loop = (P.playing_loop_range && p.has_loop) ? 1 : 0;
-      act.loop_start = act.has_loop ? (double)p.loop_start : 0.0;
-      act.loop_end = act.has_loop ? (double)p.loop_end : 0.0;
+      const bool has_loop = P.playing_loop_range && p.has_loop;
+      act.has_loop = has_loop ? 1 : 0;
+      act.window = (int16_t)(p.window & (PG_GRAIN_WINDOWS - 1));
+      act.loop_start = has_loop ? (double)p.loop_start : 0.0;
+      act.loop_end = has_loop ? (double)p.loop_end : 0.0;
       act.increment = (varied_speed / (double)S.n_frames) * (reverse ? -1.0 : 1.0);
       act.window_increment = 1.0 / (double)grain_size;
       end[index] = f + (int)(grain_size < 0x3fffffffull ? grain_size : 0x3fffffffull);
@@ -239,8 +245,8 @@ DEV void grain_sched_frame(GrainSched& S, EndArray end, int f, GrainActivation& 
   if (sequential && P.primary >= 0 && end[P.primary] > f) S.prim_phase += S.prim_inc;
 }
 
-DEV void grain_take_activation(PgGrain& g, const GrainActivation& a, int window) {
-  g.active = 1; g.window_mode = window;
+DEV void grain_take_activation(PgGrain& g, const GrainActivation& a) {
+  g.active = 1; g.window_mode = a.window;
   g.position = a.position; g.volume = a.volume; g.panning = a.panning;
   g.samples_remaining = a.samples_remaining;
   g.has_loop = a.has_loop; g.loop_start = a.loop_start; g.loop_end = a.loop_end;
@@ -266,12 +272,16 @@ DEV void grain_step(PgGrain& g, float& position, uint32_t& index, float& fractio
   if (g.samples_remaining == 0) g.active = 0;
 }
 
-// The two stereo terms of one grain at one frame (granular.rs:717-724): `lut` is the voice's window row, `pcm` its buffer of `len` >= 1 frames.
+// GrainWindow::sample's f32 part (:207-215): `lut` is the row of the grain's window_mode.
 template <typename Lut>
-DEV void grain_term(Lut lut, const float* pcm, uint64_t len, float position, uint32_t index, float fraction, float volume, float panning, float& left, float& right) {
-  left = 0.0f; right = 0.0f;
+DEV float grain_window_value(Lut lut, uint32_t index, float fraction) {
   const uint32_t next_index = (index + 1) & (PG_GRAIN_LUT_N - 1);
-  const float envelope_value = index < PG_GRAIN_LUT_N - 1 ? lut[index] * (1.0f - fraction) + lut[next_index] * fraction : lut[PG_GRAIN_LUT_N - 1];
+  return index < PG_GRAIN_LUT_N - 1 ? lut[index] * (1.0f - fraction) + lut[next_index] * fraction : lut[PG_GRAIN_LUT_N - 1];
+}
+// The two stereo terms of one grain at one frame (granular.rs:717-724): `envelope_value` is the grain's window at the frame, `pcm` the voice's buffer
+// of `len` >= 1 frames.
+DEV void grain_term(float envelope_value, const float* pcm, uint64_t len, float position, float volume, float panning, float& left, float& right) {
+  left = 0.0f; right = 0.0f;
   const float envelope = envelope_value * volume;
   if (!(envelope > GRAIN_ENVELOPE_THRESHOLD)) return;
   // sample_at_position (:901-933)

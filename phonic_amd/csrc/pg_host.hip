@@ -1099,7 +1099,7 @@ int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm
   else rng_default_state(pool.rng);
   pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
   pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
-  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1;
+  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
   for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
   r->pcm = (const float*)d_pcm; r->n_frames = n_frames; r->staged = (float*)d_stage; r->stage_pos = 0;
   r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
@@ -1146,7 +1146,7 @@ int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
   memset(out, 0, sizeof *out);
   const PgGrainPool& pool = r->pool;
   out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
-  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
+  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->overlap_mode = pool.overlap_mode; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
   memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
   for (int i = 0; i < PG_GRAIN_POOL; ++i) {
     const PgGrain& s = r->grains[i];
@@ -1154,6 +1154,49 @@ int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
     o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
     o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
   }
+  return PG_OK;
+}
+// ---- the granular parameters and the loop range while the voice plays (Sampler::set_granular_parameter, sampler.rs:299-360, :1132-1147;
+// SamplerMessage::SetLoopRange -> GrainPool::set_loop_range, sampler.rs:1246-1270, granular.rs:516-518) ----
+// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
+static int grain_message(pg_graph* g, int voice_id, int type, int param, float value, float value2, uint64_t sample_time) {
+  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  if (!voice_is_granular(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = type; m.id = voice_id; m.param = param; m.value = value; m.value2 = value2; m.sample_time = sample_time;
+  return ctrl_push(g, m);
+}
+int pg_graph_set_voice_granular_parameter(pg_graph* g, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  const int pi = find_granular_param(fourcc);
+  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown granular playback parameter 0x%08x", fourcc);
+  if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  float raw;
+  if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) {  // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
+    if (!voice_alive(g, voice_id) || !voice_is_granular(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+    return PG_OK;
+  }
+  return grain_message(g, voice_id, pgc::CT_VOICE_GRAIN_PARAM, pi, raw, 0.0f, sample_time);
+}
+int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time) {
+  if (has_loop_range && !(loop_start >= 0.0f && loop_start <= 1.0f && loop_end >= 0.0f && loop_end <= 1.0f))
+    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)loop_start, (double)loop_end);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return grain_message(g, voice_id, pgc::CT_VOICE_GRAIN_LOOP, has_loop_range ? 1 : 0, has_loop_range ? loop_start : 0.0f, has_loop_range ? loop_end : 0.0f, sample_time);
+}
+int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_stream_sync(g->stream));
+  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
+  PgGrainParams q;
+  HIP_TRY(pg_memcpy(&q, (const char*)(g->d_gran + g->voices[voice_id].gran) + offsetof(PgGrainVoice, params), sizeof q, hipMemcpyDeviceToHost));
+  memset(out, 0, sizeof *out);
+  out->overlap_mode = q.overlap_mode; out->window = q.window; out->size = q.size; out->density = q.density; out->variation = q.variation; out->spray = q.spray;
+  out->pan_spread = q.pan_spread; out->playback_direction = q.direction; out->position = q.position; out->step = q.step;
+  out->has_loop_range = q.has_loop; out->loop_start = q.loop_start; out->loop_end = q.loop_end;
   return PG_OK;
 }
 // ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
@@ -1335,7 +1378,8 @@ static void drain_control_messages(pg_graph* g) {
           // events already queued for the source stay the mixer's events: when they come due they find no source (mixed.rs:810-845) but still
           // split the block there — like the events of a removed effect
           for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK || e.cmd.type == CMD_VOICE_RELEASE ||
-                                         e.cmd.type == CMD_VOICE_MOD_ROUTE || e.cmd.type == CMD_VOICE_LFO_RATE || e.cmd.type == CMD_VOICE_LFO_WAVEFORM) && e.cmd.param == m.id) {
+                                         e.cmd.type == CMD_VOICE_MOD_ROUTE || e.cmd.type == CMD_VOICE_LFO_RATE || e.cmd.type == CMD_VOICE_LFO_WAVEFORM ||
+                                         e.cmd.type == CMD_VOICE_GRAIN_PARAM || e.cmd.type == CMD_VOICE_GRAIN_LOOP) && e.cmd.param == m.id) {
             e.cmd.type = CMD_NOP; e.cmd.target = 0;
             if (hv.mixer == 0) e.cmd.param = -1;
           }
@@ -1356,6 +1400,8 @@ static void drain_control_messages(pg_graph* g) {
         else if (m.type == pgc::CT_VOICE_MOD_ROUTE) { c.type = CMD_VOICE_MOD_ROUTE; c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }
         else if (m.type == pgc::CT_VOICE_LFO_RATE) { c.type = CMD_VOICE_LFO_RATE; c.value = (float)((double)m.value / (double)g->sample_rate); c.value64 = (uint64_t)(uint32_t)m.param; }   // Lfo::set_rate (lfo.rs:102-104)
         else if (m.type == pgc::CT_VOICE_LFO_WAVEFORM) { c.type = CMD_VOICE_LFO_WAVEFORM; c.value64 = (uint64_t)(uint32_t)m.param; }
+        else if (m.type == pgc::CT_VOICE_GRAIN_PARAM) { c.type = CMD_VOICE_GRAIN_PARAM; c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }
+        else if (m.type == pgc::CT_VOICE_GRAIN_LOOP) { uint32_t e; memcpy(&e, &m.value2, 4); c.type = CMD_VOICE_GRAIN_LOOP; c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)e << 32); }
         else { c.type = CMD_VOICE_SEEK; memcpy(&c.value64, &m.dvalue, 8); }
         push_event(g, hv.mixer, m.sample_time, c);
       } break;
@@ -2176,7 +2222,8 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
         // calls keep their super-block launches between such commands (notes that stop and start: bench.py --workload dyn --churn).
         bool may_ramp = false;
         for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK || c.type == CMD_VOICE_RELEASE ||
-                                                         c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM);   // (the matrix's commands reach pg_grain_kernel only)
+                                                         c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM ||
+                                                         c.type == CMD_VOICE_GRAIN_PARAM || c.type == CMD_VOICE_GRAIN_LOOP);   // (the matrix's and the granular parameters' commands reach pg_grain_kernel only)
         // (the round AFTER this one is the first whose scan sees what the commands left behind: this round's own count of state-deferred units
         // was taken in front of them)
         if (may_ramp) g->last_change_round = sp.round + 1;

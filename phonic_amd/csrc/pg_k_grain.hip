@@ -1,18 +1,20 @@
 // pg_grain_kernel: the grain engine of the sampler's granular voices (GrainPool<100>, src/generator/sampler/granular.rs) — one workgroup per
 // living granular voice, launched on the write's stream in front of the unit kernels of a chunk's piece. It renders the voice's frames of the
 // piece as interleaved stereo f32 into the voice's staging buffer; the exact unit kernel takes them as the voice's source output (a plain copy
-// in its source stage, pg_source_dev.h) and puts the volume envelope on top. Commands of the piece (volume, panning, speed, stop, release) are
-// read from the launch's command list and applied at their frames.
+// in its source stage, pg_source_dev.h) and puts the volume envelope on top. Commands of the piece (volume, panning, speed, stop, release, the
+// matrix's, the granular parameters and the loop range) are read from the launch's command list and applied at their frames.
 //
 // Per tile of PG_GRAIN_TILE frames (pg_grain_dev.h has the arithmetic):
 //   0  voices with a modulation matrix only (pg_graph_set_voice_modulation_matrix): one lane per LFO walks its f32 phase recurrence, wraps and
 //      draws over the tile's rendered frames and leaves the raw values in LDS; then one lane per (target, frame) forms the target's sum in slot
 //      order from the 4 x 7 routing table as of its frame. Phase 1 reads seven floats per frame, nothing else of the matrix is in its walk;
-//   1  lane 0 walks the scheduler frame by frame and leaves the activations, one slot per frame at most, in LDS;
+//   1  lane 0 walks the scheduler frame by frame — the voice's parameters and loop range as of each frame (CMD_VOICE_GRAIN_PARAM / _LOOP act in
+//      front of theirs) — and leaves the activations, one slot per frame at most, in LDS;
 //   2  lane s walks slot s: takes its activations at their frames, steps Grain::process's f64 recurrences and leaves, per frame, the f32 read
 //      position and the window table's index and fraction in LDS (12 bytes per slot and frame: 38 KB for 100 slots x 32 frames); the slot's
 //      record stays in the lane's registers for the whole launch. Slots without an active grain in the tile are left out of what follows;
-//   3  all lanes, spread over (active slot, frame): window lookup from the voice's table row in LDS, the four reads of the buffer, Catmull-Rom,
+//   3  all lanes, spread over (active slot, frame): window lookup in the row of the grain's own window_mode — the row of the voice's window as the
+//      launch began is staged in LDS, a grain born under another window reads the global table — the four reads of the buffer, Catmull-Rom,
 //      the threshold test, the two stereo terms — written over the slot's LDS words; then one lane per (frame, channel) adds the terms in
 //      ascending slot order and stores the frame.
 // State does not depend on how a render is cut into launches or tiles: every recurrence is walked frame by frame in the reference's order.
@@ -26,7 +28,24 @@ using namespace pgd;
 
 __device__ __forceinline__ bool grain_cmd_matches(const PgCmd& c, int voice) {
   return c.target == voice && (c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_SPEED || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_RELEASE ||
-                               c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM);
+                               c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM || c.type == CMD_VOICE_GRAIN_PARAM ||
+                               c.type == CMD_VOICE_GRAIN_LOOP);
+}
+// Sampler::set_granular_parameter (sampler.rs:299-360): the host has resolved the update to a raw value inside the descriptor's range
+__device__ __forceinline__ void grain_set_parameter(PgGrainParams& p, uint32_t index, float value) {
+  switch (index) {
+    case PG_GP_OVERLAP_MODE: p.overlap_mode = (int32_t)value & 1; break;
+    case PG_GP_WINDOW: p.window = (int32_t)value & (PG_GRAIN_WINDOWS - 1); break;
+    case PG_GP_SIZE: p.size = value; break;
+    case PG_GP_DENSITY: p.density = value; break;
+    case PG_GP_VARIATION: p.variation = value; break;
+    case PG_GP_SPRAY: p.spray = value; break;
+    case PG_GP_PAN_SPREAD: p.pan_spread = value; break;
+    case PG_GP_DIRECTION: { const int32_t d = (int32_t)value; p.direction = d < 0 ? 0 : (d > 2 ? 2 : d); } break;
+    case PG_GP_POSITION: p.position = value; break;
+    case PG_GP_STEP: p.step = value; break;
+    default: break;
+  }
 }
 // A route command's source and target, -1 when either is out of range (the host checks them: nothing out of range indexes the table)
 __device__ __forceinline__ int grain_route_source(const PgCmd& c) { const uint32_t s = (uint32_t)(c.value64 & 0xff); return s < PG_GMOD_SOURCES ? (int)s : -1; }
@@ -36,7 +55,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   __shared__ float s_lut[PG_GRAIN_LUT_N];
   __shared__ float s_pos[PG_GRAIN_POOL * GT];     // phase 2: read position; phase 3: the left term
   __shared__ float s_frac[PG_GRAIN_POOL * GT];    // phase 2: window fraction; phase 3: the right term
-  __shared__ uint32_t s_ti[PG_GRAIN_POOL * GT];   // window index | (1 + frame of the activation the grain's volume / panning come from, 0: the slot's as the tile began) << 16
+  __shared__ uint32_t s_ti[PG_GRAIN_POOL * GT];   // window index | (1 + frame of the activation the grain's volume / panning come from, 0: the slot's as the tile began) << 16 | the grain's window_mode << 24
   __shared__ GrainActivation s_act[GT];
   __shared__ int s_end[PG_GRAIN_POOL];
   __shared__ float s_vol[PG_GRAIN_POOL], s_pan[PG_GRAIN_POOL];
@@ -204,6 +223,14 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
           else if (c.type == CMD_VOICE_SPEED) S.pool.speed = __longlong_as_double((long long)c.value64);   // (the glide is ignored: SamplerVoice::set_speed hands the pool the speed alone)
           else if (c.type == CMD_VOICE_STOP) stop_time = c.value64;
           else if (c.type == CMD_VOICE_RELEASE && !has_env) S.pool.trigger_new_grains = 0;   // without an envelope: SamplerVoice::stop -> GrainPool::stop
+          else if (exhausted_at != UINT64_MAX) {}   // (the pool ran dry in front of this frame: the voice ends with that call, it takes no parameters any more)
+          else if (c.type == CMD_VOICE_GRAIN_PARAM) {
+            grain_set_parameter(S.p, (uint32_t)c.value64, c.value);
+            // in front of the note: GrainPool::start reads the position at note-on (:487)
+            if ((uint32_t)c.value64 == PG_GP_POSITION && L.t0 + (uint64_t)c.frame < start_time) S.pool.playhead = c.value;
+          } else if (c.type == CMD_VOICE_GRAIN_LOOP) {  // GrainPool::set_loop_range (:516-518): playing_loop_range, the playhead and living grains keep what they have
+            S.p.has_loop = (int32_t)(c.value64 & 1); S.p.loop_start = c.value; S.p.loop_end = __uint_as_float((uint32_t)(c.value64 >> 32));
+          }
           // (the modulation matrix's commands were taken in phase 0)
         }
         if (t < start_time) { s_act[f].slot = -1; continue; }
@@ -226,13 +253,13 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
     if (live) {
       uint32_t src = 0;
       for (int f = 0; f < tn; ++f) {
-        if (s_act[f].slot == tid) { grain_take_activation(g, s_act[f], window); src = (uint32_t)(f + 1); }
+        if (s_act[f].slot == tid) { grain_take_activation(g, s_act[f]); src = (uint32_t)(f + 1); }
         const int o = tid * GT + f;
         if (g.active) {
           float position, fraction;
           uint32_t index;
           grain_step(g, position, index, fraction);
-          s_pos[o] = position; s_frac[o] = fraction; s_ti[o] = index | (src << 16);
+          s_pos[o] = position; s_frac[o] = fraction; s_ti[o] = index | (src << 16) | ((uint32_t)(g.window_mode & (PG_GRAIN_WINDOWS - 1)) << 24);
         } else s_ti[o] = PG_GRAIN_INACTIVE;
       }
     }
@@ -253,9 +280,12 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
       const uint32_t w = s_ti[o];
       float l = 0.0f, r = 0.0f;
       if (w != PG_GRAIN_INACTIVE) {
-        const uint32_t a = w >> 16;
+        const uint32_t a = (w >> 16) & 0xff;
         const float vol = a ? s_act[a - 1].volume : s_vol[slot], pan = a ? s_act[a - 1].panning : s_pan[slot];
-        grain_term(s_lut, pcm, len, s_pos[o], w & (PG_GRAIN_LUT_N - 1), s_frac[o], vol, pan, l, r);
+        const uint32_t index = w & (PG_GRAIN_LUT_N - 1);
+        const int mode = (int)((w >> 24) & (PG_GRAIN_WINDOWS - 1));
+        const float env = mode == window ? grain_window_value(s_lut, index, s_frac[o]) : grain_window_value(L.lut + mode * PG_GRAIN_LUT_N, index, s_frac[o]);
+        grain_term(env, pcm, len, s_pos[o], vol, pan, l, r);
       }
       s_pos[o] = l; s_frac[o] = r;
     }
@@ -270,7 +300,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
     __syncthreads();
   }
   if (tid < PG_GRAIN_POOL) V->grains[tid] = g;
-  if (tid == 0) { V->pool = S.pool; V->stop_time = stop_time; V->exhausted_at = exhausted_at; V->stage_pos = L.chunk_t0; }
+  if (tid == 0) { V->params = S.p; V->pool = S.pool; V->stop_time = stop_time; V->exhausted_at = exhausted_at; V->stage_pos = L.chunk_t0; }
   if (has_mod) {  // (the last tile's barriers are behind every lane)
     if (tid < PG_GMOD_SOURCES * PG_GMOD_TARGETS) { (&V->mod.amount[0][0])[tid] = (&s_ramt[0][0])[tid]; (&V->mod.bipolar[0][0])[tid] = (&s_rbip[0][0])[tid]; }
     if (tid == 64 || tid == 128) V->mod.lfo[(tid >> 6) - 1] = s_lfo_state[(tid >> 6) - 1];

@@ -115,6 +115,25 @@ static const ParamSpec DIST_PARAMS[] = {
     {FCC('m', 'i', 'x', ' '), PG_PARAM_FLOAT, 0.0f, 1.0f, 1.0f, 0, 0, 0, 0, "Mix", S_EXP, 0.1f},
 };
 
+// The granular playback parameters of the Sampler, in Sampler::granular_parameters() order (src/generator/sampler.rs:219-296): the index is
+// CMD_VOICE_GRAIN_PARAM's (PG_GP_*). No smoothing: set_granular_parameter writes the value into GranularParameters (:299-360).
+static const ParamSpec GRANULAR_PARAMS[PG_GP_COUNT] = {
+    {FCC('G', 'O', 'V', 'M'), PG_PARAM_ENUM, 0, 1, 0, 0, 0, 0, 2, "Overlap Mode", S_NONE, 0},
+    {FCC('G', 'W', 'N', 'D'), PG_PARAM_ENUM, 0, 7, 0, 0, 0, 0, 8, "Window", S_NONE, 0},
+    {FCC('G', 'S', 'I', 'Z'), PG_PARAM_FLOAT, 1.0f, 1000.0f, 100.0f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Grain Size", S_NONE, 0},
+    {FCC('G', 'D', 'E', 'N'), PG_PARAM_FLOAT, 1.0f, 100.0f, 10.0f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Density", S_NONE, 0},
+    {FCC('G', 'V', 'A', 'R'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.0f, 0, 0, 0, 0, "Variation", S_NONE, 0},
+    {FCC('G', 'S', 'P', 'Y'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.0f, 0, 0, 0, 0, "Spray", S_NONE, 0},
+    {FCC('G', 'P', 'A', 'N'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.0f, 0, 0, 0, 0, "Pan Spread", S_NONE, 0},
+    {FCC('G', 'D', 'I', 'R'), PG_PARAM_ENUM, 0, 2, 0, 0, 0, 0, 3, "Direction", S_NONE, 0},
+    {FCC('G', 'P', 'O', 'S'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.5f, 0, 0, 0, 0, "Position", S_NONE, 0},
+    {FCC('G', 'S', 'T', 'P'), PG_PARAM_FLOAT, -4.0f, 4.0f, 0.0f, 0, 0, 0, 0, "Step", S_NONE, 0},
+};
+inline int find_granular_param(uint32_t fourcc) {
+  for (int i = 0; i < PG_GP_COUNT; ++i) if (GRANULAR_PARAMS[i].fourcc == fourcc) return i;
+  return -1;
+}
+
 struct KindInfo { const char* name; int weight; const ParamSpec* params; int n_params; };
 // names: EFFECT_NAME consts; weights: `fn weight` of each effect
 static const KindInfo KINDS[PG_FX_KIND_COUNT] = {

@@ -503,6 +503,22 @@ int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modu
   SHARDED_VOICE(s, voice_id, pk);
   return pg_graph_voice_modulation_state(s->shards[shard_of(pk)], local_of(pk), out);
 }
+// the granular parameters and loop range of a granular voice (pg_graph_set_voice_granular_parameter / _grain_loop_range): on the voice's shard
+int pg_sharded_set_voice_granular_parameter(pg_sharded_graph* s, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  if (!s) return pg_graph_set_voice_granular_parameter(nullptr, 0, fourcc, value, is_normalized, 0);   // (the parameter error, or the null handle's)
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_granular_parameter(s->shards[shard_of(pk)], local_of(pk), fourcc, value, is_normalized, sample_time);
+}
+int pg_sharded_set_voice_grain_loop_range(pg_sharded_graph* s, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time) {
+  if (!s) return pg_graph_set_voice_grain_loop_range(nullptr, 0, has_loop_range, loop_start, loop_end, 0);
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_grain_loop_range(s->shards[shard_of(pk)], local_of(pk), has_loop_range, loop_start, loop_end, sample_time);
+}
+int pg_sharded_voice_granular_params(pg_sharded_graph* s, int voice_id, pg_granular_params* out) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_voice_granular_params(s->shards[shard_of(pk)], local_of(pk), out);
+}
 int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) {
   if (!s || voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return -1;
   const int32_t pk = s->voice_map.get((size_t)voice_id);

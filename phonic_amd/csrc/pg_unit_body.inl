@@ -561,8 +561,8 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
           if (e && e->on) { PgEnvState st = e->state; ahdsr_note_off(st, e->params); e->state = st; }
           else { L.voices[cmd.target].has_stop = 1; L.voices[cmd.target].stop_time = cmd.value64; }
         }
-        // (CMD_VOICE_MOD_ROUTE / _LFO_RATE / _LFO_WAVEFORM belong to a granular voice's modulation matrix: pg_grain_kernel has applied them, nothing
-        // to do here — like every event of the mixer they still end a segment at their frame)
+        // (CMD_VOICE_MOD_ROUTE / _LFO_RATE / _LFO_WAVEFORM belong to a granular voice's modulation matrix, CMD_VOICE_GRAIN_PARAM / _GRAIN_LOOP to its
+        // grain pool: pg_grain_kernel has applied them, nothing to do here — like every event of the mixer they still end a segment at their frame)
         ctl[2] = flush;
       }
       __syncthreads();

@@ -185,6 +185,22 @@ class ShardedGraph:
         self._check(self._lib.pg_sharded_voice_grain_state(self._h, voice, C.byref(st)))
         return _capi.grain_state_dict(st)
 
+    def set_voice_granular_parameter(self, voice, id4, value, sample_time, normalized=False):
+        """GeneratorPlaybackHandle::set_parameter for one of the Sampler's GRAIN_* ids (_capi.GRANULAR_PARAM_IDS) on this voice, in front of frame
+        sample_time. Raw values are clamped to the descriptor's range, enum values are the variant's index."""
+        self._check(self._lib.pg_sharded_set_voice_granular_parameter(self._h, voice, _capi.fourcc(id4), float(value), 1 if normalized else 0, sample_time))
+
+    def set_voice_grain_loop_range(self, voice, loop_range, sample_time):
+        """GrainPool::set_loop_range in front of frame sample_time: (start, end) normalised to [0, 1], or None."""
+        has = loop_range is not None
+        self._check(self._lib.pg_sharded_set_voice_grain_loop_range(self._h, voice, 1 if has else 0, float(loop_range[0]) if has else 0.0, float(loop_range[1]) if has else 0.0, sample_time))
+
+    def voice_granular_params(self, voice):
+        """The voice's granular parameters and loop range as the device holds them (debug read-back: waits for the graph's stream)."""
+        p = _capi.GranularParams()
+        self._check(self._lib.pg_sharded_voice_granular_params(self._h, voice, C.byref(p)))
+        return _capi.granular_params_dict(p)
+
     def set_voice_modulation_matrix(self, voice, params=None, **kw):
         """The ModulationMatrix of a granular voice (two LFOs, velocity, keytracking -> the seven granular targets) + note_on; before the voice
         renders. `params`: a _capi.ModulationParams, or the keywords of _capi.modulation_params."""

@@ -39,7 +39,9 @@ def source(n=SR):
     return (0.5 * np.sin(2 * np.pi * 220.0 * t) + 0.2 * np.sin(2 * np.pi * 3.0 * t)).astype(np.float32)
 
 
-def run(name, voices, steps):
+def run(name, voices, steps, matrix=None, before_step=None):
+    """matrix: keywords of set_voice_modulation_matrix for every voice (None: no matrix). before_step(g, ids, k, pos): called in front of every
+    step's write, outside the timed span (tools/granular_params_cost.py schedules its commands there)."""
     import torch
 
     kw, warmup = SETTINGS[name]
@@ -49,16 +51,22 @@ def run(name, voices, steps):
     for i in range(voices):
         p = _capi.granular_params(rng_state=(i + 1, 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03, i * 7919 + 3), position=0.1 + 0.8 * (i % 97) / 97.0, **kw)
         ids.append(g.add_granular_voice(0, pcm, p, volume=0.02, panning=((i % 21) - 10) / 10.0))
+        if matrix is not None:
+            g.set_voice_modulation_matrix(ids[-1], rng_states=((i + 11, 2, 3, 4), (i + 5, 6, 7, 8)), **matrix)
     stream = torch.cuda.Stream(device=0)
     out = torch.zeros(2 * MF, dtype=torch.float32, device="cuda:0")
     pos = 0
     with torch.cuda.stream(stream):
-        for _ in range(warmup):
+        for k in range(warmup):
+            if before_step:
+                before_step(g, ids, k, pos)
             assert g.write_device(out.data_ptr(), 2 * MF, pos, stream.cuda_stream) == 2 * MF
             pos += MF
         stream.synchronize()
         ms = []
-        for _ in range(steps):
+        for k in range(steps):
+            if before_step:
+                before_step(g, ids, warmup + k, pos)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             assert g.write_device(out.data_ptr(), 2 * MF, pos, stream.cuda_stream) == 2 * MF
