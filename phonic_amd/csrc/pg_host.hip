@@ -6,7 +6,6 @@
 // here on the host and handed to the kernels as per-launch command lists — and the parameter descriptor
 // logic (pg_params.h). All per-sample work happens in pg_kernels.hip.
 #include "pg_host_internal.h"
-#include "pg_grain_dev.h"   // mod_lfo_reset: the note_on of a voice's modulation matrix runs on the host
 
 // ---- errors ---------------------------------------------------------------------------------------------
 static thread_local std::string g_last_error;
@@ -32,7 +31,6 @@ hipError_t pg_memset(void* d, int v, size_t n) { g_n_blocking_copy++; return hip
 
 // Test hook (pg_debug_fail_launch_round): the n-th launch round from now fails as if a HIP launch had — exercises the sticky failed state
 static std::atomic<int> g_fail_round_countdown{0};
-static int graph_fail(pg_graph* g, int code) { g->failed = true; return code; }
 
 // Calls that change the graph (add_* / remove_* / move_* / mode switches) are not real-time calls: they first wait for everything the
 // last write enqueued — on the graph's own stream and on the caller's stream the last write used — so that no launch in flight reads a
@@ -230,111 +228,6 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
   return PG_OK;
 }
 
-// The envelope side table and its `ended` words for `n` voices (grow-by-doubling; the graph is quiescent: nothing in flight reads the old ones).
-static int graph_env_reserve(pg_graph* g, size_t n) {
-  if (n <= g->env_cap) return PG_OK;
-  const size_t cap = std::max<size_t>(next_pow2(n), 64);
-  PgEnvTable* nt = nullptr;
-  int32_t* nh = nullptr;
-  int32_t* ndd = nullptr;
-  int32_t* ngv = nullptr;   // PgEnvTable::grain_of_voice: -1 for every voice that is not granular
-  HIP_TRY(pg_malloc((void**)&nt, sizeof(PgEnvTable) + cap * sizeof(PgEnv)));
-  PgEnv* const nd = (PgEnv*)(nt + 1);
-  if (pg_memset(nt, 0, sizeof(PgEnvTable) + cap * sizeof(PgEnv)) != hipSuccess || pg_host_malloc((void**)&nh, cap * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { (void)pg_free(nt); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
-  memset(nh, 0, cap * sizeof(int32_t));
-  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess || pg_malloc((void**)&ngv, cap * sizeof(int32_t)) != hipSuccess) { (void)pg_free(nt); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
-  auto undo = [&]() { (void)pg_free(nt); (void)pg_host_free(nh); (void)pg_free(ngv); };
-  if (pg_memset(ngv, 0xff, cap * sizeof(int32_t)) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table allocation failed"); }
-  PgEnvTable head;
-  memset(&head, 0, sizeof head);
-  head.done = ndd; head.cap = cap;
-  head.grain_of_voice = ngv; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
-  if (pg_memcpy(nt, &head, sizeof head, hipMemcpyHostToDevice) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table upload failed"); }
-  PgEnvTable* const old_tab = g->d_env_tab;
-  int32_t* const old_done = g->h_env_done;
-  int32_t* const old_gv = g->d_grain_of_voice;
-  if (g->d_env) {
-    if (pg_memcpy(nd, g->d_env, g->env_cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess ||
-        pg_memcpy(ngv, old_gv, g->env_cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess) { undo(); return set_error(PG_ERR_DEVICE, "envelope table copy failed"); }
-    memcpy(nh, g->h_env_done, g->env_cap * sizeof(int32_t));
-  }
-  // (the new table is complete: swap first, then let go of the old one — a failure above leaves the graph on its old table)
-  g->d_env_tab = nt; g->d_env = nd; g->h_env_done = nh; g->env_cap = cap; g->d_grain_of_voice = ngv;
-  if (old_tab) (void)pg_free(old_tab);
-  if (old_done) (void)pg_host_free(old_done);
-  if (old_gv) (void)pg_free(old_gv);
-  return PG_OK;
-}
-// Room for `n` granular records, their `ended` words and their launch list; the window tables with the first one. The graph is quiescent.
-static int graph_gran_reserve(pg_graph* g, size_t n) {
-  if (!g->d_grain_lut) {
-    std::vector<float> lut((size_t)PG_GRAIN_WINDOWS * PG_GRAIN_LUT_N);
-    pg_grain_build_lut(lut.data());
-    HIP_TRY(pg_malloc((void**)&g->d_grain_lut, lut.size() * sizeof(float)));
-    HIP_TRY(pg_memcpy(g->d_grain_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
-  }
-  int rc;
-  if ((rc = g->d_gran_live.reserve(std::max<size_t>(next_pow2(n), 16)))) return rc;
-  if (n <= g->gran_cap) return PG_OK;
-  const size_t cap = std::max<size_t>(next_pow2(n), 16);
-  PgGrainVoice* nd = nullptr;
-  int32_t* nh = nullptr;
-  int32_t* ndd = nullptr;
-  HIP_TRY(pg_malloc((void**)&nd, cap * sizeof(PgGrainVoice)));
-  if (pg_host_malloc((void**)&nh, cap * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { (void)pg_free(nd); return set_error(PG_ERR_DEVICE, "granular table allocation failed"); }
-  memset(nh, 0, cap * sizeof(int32_t));
-  if (hipHostGetDevicePointer((void**)&ndd, nh, 0) != hipSuccess ||
-      (g->gran_n && pg_memcpy(nd, g->d_gran, g->gran_n * sizeof(PgGrainVoice), hipMemcpyDeviceToDevice) != hipSuccess)) { (void)pg_free(nd); (void)pg_host_free(nh); return set_error(PG_ERR_DEVICE, "granular table allocation failed"); }
-  if (g->gran_n) memcpy(nh, g->h_gran_ended, g->gran_n * sizeof(int32_t));
-  if (g->d_gran) (void)pg_free(g->d_gran);
-  if (g->h_gran_ended) (void)pg_host_free(g->h_gran_ended);
-  g->d_gran = nd; g->h_gran_ended = nh; g->d_gran_ended = ndd; g->gran_cap = cap;
-  return PG_OK;
-}
-// The granular fields of the envelope table's header, as the graph holds them now (the graph is quiescent).
-static int graph_gran_publish(pg_graph* g) {
-  PgEnvTable head;
-  memset(&head, 0, sizeof head);
-  HIP_TRY(pg_memcpy(&head, g->d_env_tab, sizeof head, hipMemcpyDeviceToHost));
-  head.grain_of_voice = g->d_grain_of_voice; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
-  HIP_TRY(pg_memcpy(g->d_env_tab, &head, sizeof head, hipMemcpyHostToDevice));
-  return PG_OK;
-}
-// Granular voices pg_grain_kernel has reported as ended (or that left the graph): they leave its launch list, and their units go back to the
-// time-parallel kernels with the next topology upload. Reads mapped host words: no wait.
-static void graph_poll_granular(pg_graph* g) {
-  for (size_t i = 0; i < g->gran_voices.size();) {
-    HostVoice& hv = g->voices[g->gran_voices[i]];
-    if (hv.mixer < 0 || *(volatile int32_t*)(g->h_gran_ended + hv.gran) != 0) {
-      hv.gran_live = false;
-      g->gran_voices.erase(g->gran_voices.begin() + i);
-      g->topo_dirty = true; g->gran_live_dirty = true;
-    } else ++i;
-  }
-}
-// pg_grain_kernel for frames [t0, t0 + n) of the chunk that began at chunk_t0, in front of the unit kernels that take its frames.
-static int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
-  if (g->gran_voices.empty()) return PG_OK;
-  PgGrainLaunch L;
-  memset(&L, 0, sizeof L);
-  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gran_voices.size(); L.live = g->d_gran_live.d;
-  L.voices = g->d_voices.d; L.cmds = d_cmds; L.n_cmds = n_cmds; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->d_gran_ended;
-  L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
-  HIP_TRY(pg_launch_grain(L, stream));
-  return PG_OK;
-}
-// Enveloped voices the exact kernel has reported as ended (or that left the graph): their units go back to the time-parallel kernels with the
-// next topology upload. Reads mapped host words: no wait.
-static void graph_poll_envelopes(pg_graph* g) {
-  for (size_t i = 0; i < g->env_voices.size();) {
-    HostVoice& hv = g->voices[g->env_voices[i]];
-    if (hv.mixer < 0 || *(volatile int32_t*)(g->h_env_done + hv.dev_index) != 0) {
-      hv.env_live = false;
-      g->env_voices.erase(g->env_voices.begin() + i);
-      g->topo_dirty = true;
-    } else ++i;
-  }
-}
 
 // Per-unit output tables the write path needs: one per block of a super-block launch, and one per piece of a chunk (the mixer sum runs
 // behind a chunk's last piece).
@@ -347,7 +240,7 @@ static int graph_reserve(pg_graph* g) {
   if ((rc = g->d_topo.reserve(n_units)) || (rc = g->d_order.reserve(n_units)) || (rc = g->d_slot_info.reserve(n_units)) || (rc = g->d_slot_fx.reserve(n_units)) || (rc = g->d_slot_lead.reserve(n_units)) ||
       (rc = g->d_voice_index.reserve(n_voices)) || (rc = g->d_fx_index.reserve(n_fx)) || (rc = g->d_child_rows.reserve(n_mixers)))
     return rc;
-  if (g->d_env && n_voices > g->env_cap) { if ((rc = graph_env_reserve(g, n_voices))) return rc; }
+  if (g->d_env && (rc = graph_env_reserve(g, n_voices))) return rc;
   if (!g->d_cmd_ring) {
     HIP_TRY(pg_malloc((void**)&g->d_cmd_ring, PG_CMD_RING * sizeof(PgCmd)));
     HIP_TRY(pg_host_malloc((void**)&g->h_cmd_ring, PG_CMD_RING * sizeof(PgCmd), hipHostMallocDefault));
@@ -400,18 +293,63 @@ static int graph_flush_blocking(pg_graph* g) {
   if ((rc = g->d_units.flush()) || (rc = g->d_fx.flush()) || (rc = g->d_voices.flush()) || (rc = g->d_sched.flush())) return rc;
   return PG_OK;
 }
-
-// The reference's parameter errors (ahdsr.rs:143-152, :179-188, :224-233, :259-268) + what no Duration can hold; touches no graph and no device.
-int pg_ahdsr_params_check(const pg_ahdsr_params* p) {
-  if (!p) return set_error(PG_ERR_PARAMETER, "envelope parameters must not be null");
-  const float times[4] = {p->attack_s, p->hold_s, p->decay_s, p->release_s};
-  static const char* const names[4] = {"attack", "hold", "decay", "release"};
-  for (int i = 0; i < 4; ++i) if (!std::isfinite(times[i]) || times[i] < 0.0f) return set_error(PG_ERR_PARAMETER, "Invalid %s time: %g. Must be finite and >= 0", names[i], (double)times[i]);
-  if (!(p->attack_scaling >= -1.0f && p->attack_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid attack scaling: %g. Must be in range [-1.0, 1.0]", (double)p->attack_scaling);
-  if (!(p->decay_scaling >= -1.0f && p->decay_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid decay scaling: %g. Must be in range [-1.0, 1.0]", (double)p->decay_scaling);
-  if (!(p->sustain_level >= 0.0f && p->sustain_level <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid sustain level: %g. Must be in range [0.0, 1.0]", (double)p->sustain_level);
-  if (!(p->release_scaling >= -1.0f && p->release_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid release scaling: %g. Must be in range [-1.0, 1.0]", (double)p->release_scaling);
+int graph_read_back(pg_graph* g, void* dst, const void* d_src, size_t bytes) {
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_stream_sync(g->stream));
+  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
+  HIP_TRY(pg_memcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
   return PG_OK;
+}
+
+void voice_init_neutral(const pg_graph* g, PgVoice& v, const pg_voice_options* opt, float volume, float panning) {
+  memset(&v, 0, sizeof v);
+  v.fader_state = 0; v.fader_current = 1.0f; v.fader_target = 1.0f; v.fader_inertia = 1.0f;   // VolumeFader::new (file/common.rs:69-75, fader.rs:36-91)
+  // AmplifiedSource / PannedSource: ExponentialSmoothedValue::new(value, source.sample_rate())
+  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};
+  v.volume = make_smooth(exp_spec, volume, g->sample_rate);
+  v.panning = make_smooth(exp_spec, panning, g->sample_rate);
+  v.start_time = opt->start_time;
+  v.active = 1;
+  v.persistent = opt->non_transient != 0;
+}
+int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind) {
+  const int id = (int)g->voices.size();
+  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.transient = opt->non_transient == 0;
+  g->voices.push_back(hv);
+  if (hv.stream) g->stream_voices.push_back(id);
+  if (hv.gran >= 0) { g->gran_voices.push_back(id); g->gran_live_dirty = true; }
+  g->source_unit_of_voice.push_back(-1);
+  // AddSource: sort by start time, insert BEFORE equal start times (mixed.rs:324-329)
+  HostMixer& mx = g->mixers[mixer_id];
+  size_t pos = 0;
+  while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
+  mx.voices.insert(mx.voices.begin() + pos, id);
+  if (mixer_id == 0) {
+    int slot = new_unit(g, UNIT_SOURCE);
+    if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
+    g->source_unit_of_voice[id] = slot;
+    g->main_active_voices += 1;
+    g->ever_had_main_voice = true;
+  }
+  if (!g->voice_alive_tab.append(kind)) return -set_error(PG_ERR_STATE, "too many voices");
+  g->topo_dirty = true;
+  if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  return id;
+}
+
+static int ctrl_push(pg_graph* g, const pgc::CtrlMsg& m) {
+  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");  // Error::SendError
+  return PG_OK;
+}
+int voice_message(pg_graph* g, int voice_id, VoiceKind need, int type, uint64_t sample_time, float value, int param, double dvalue, float value2) {
+  const VoiceKind kind = voice_kind(g, voice_id);
+  if (kind == VOICE_DEAD) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  if (need == VOICE_GRANULAR && !voice_kind_is_granular(kind)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  if (need == VOICE_GRANULAR_MOD && kind != VOICE_GRANULAR_MOD) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = type; m.id = voice_id; m.param = param; m.value = value; m.value2 = value2; m.dvalue = dvalue; m.sample_time = sample_time;
+  return ctrl_push(g, m);
 }
 
 extern "C" {
@@ -492,13 +430,7 @@ void pg_graph_destroy(pg_graph* g) {
   if (g->d_bus_progress) (void)pg_free(g->d_bus_progress);
   if (g->h_pinned) (void)pg_host_free(g->h_pinned);
   if (g->h_feedback) (void)pg_host_free(g->h_feedback);
-  if (g->d_env_tab) (void)pg_free(g->d_env_tab);
-  if (g->h_env_done) (void)pg_host_free(g->h_env_done);
-  if (g->d_grain_of_voice) (void)pg_free(g->d_grain_of_voice);
-  if (g->d_gran) (void)pg_free(g->d_gran);
-  if (g->d_grain_lut) (void)pg_free(g->d_grain_lut);
-  if (g->h_gran_ended) (void)pg_host_free(g->h_gran_ended);
-  g->d_gran_live.release();
+  graph_sampler_release(g);
   graph_meter_release(g);
   for (auto& e : g->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_bus_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -554,7 +486,6 @@ int pg_graph_add_effect(pg_graph* g, int mixer_id, int kind, const pg_effect_ini
 // Player::stop_all_sources (src/player.rs:1012-1045): every playing file source is told to stop (fades out from the next write on,
 // like pg_graph_stop_voice at "now"), and every mixer gets MixerMessage::RemoveAllPendingEvents (src/source/mixed.rs:298-305), which
 // at the start of the next write drops the sources that have not started yet and the events scheduled after that write's position.
-static void drain_control_messages(pg_graph* g);
 static void stop_all_voices_now(pg_graph* g) {
   for (size_t v = 0; v < g->voices.size(); ++v) {
     if (g->voices[v].mixer < 0 || !g->voices[v].transient) continue;   // (stop_all_sources stops the transient sources, player.rs:1013-1031)
@@ -564,10 +495,6 @@ static void stop_all_voices_now(pg_graph* g) {
     g->mixers[g->voices[v].mixer].messages.push_back(c);
   }
   for (HostMixer& mx : g->mixers) if (!mx.removed) { mx.remove_pending = true; mx.remove_event_seq = g->event_seq; mx.remove_voice_limit = g->voices.size(); }
-}
-static int ctrl_push(pg_graph* g, const pgc::CtrlMsg& m) {
-  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");  // Error::SendError
-  return PG_OK;
 }
 int pg_graph_stop_all_voices(pg_graph* g) {
   pgc::CtrlMsg m;
@@ -584,7 +511,7 @@ static void apply_remove_pending(pg_graph* g, uint64_t pos) {
       if ((size_t)v < mx.remove_voice_limit && g->voices[v].transient && g->voices[v].start_time > pos) {   // (source.is_transient && source.start_time > time.pos_in_frames, mixed.rs:300-302)
         mx.messages.erase(std::remove_if(mx.messages.begin(), mx.messages.end(), [v](const PgCmd& c) { return c.param == v; }), mx.messages.end());
         g->voices[v].mixer = -1;
-        g->voice_alive_tab.set((size_t)v, 0);
+        g->voice_alive_tab.set((size_t)v, VOICE_DEAD);
         g->retired_voices.push_back(v);
         mx.voices.erase(mx.voices.begin() + i);
         if (&mx == &g->mixers[0] && g->main_active_voices > 0) g->main_active_voices -= 1;
@@ -612,7 +539,7 @@ int pg_graph_remove_mixer(pg_graph* g, int mixer_id) {
     HostMixer& mx = g->mixers[gone[i]];
     for (int c : mx.children) gone.push_back(c);
     for (int f : mx.fx) { g->fx_mixer[f] = -1; g->fx_kind_tab.set((size_t)f, -1); }
-    for (int v : mx.voices) { g->voices[v].mixer = -1; g->voice_alive_tab.set((size_t)v, 0); g->retired_voices.push_back(v); }
+    for (int v : mx.voices) { g->voices[v].mixer = -1; g->voice_alive_tab.set((size_t)v, VOICE_DEAD); g->retired_voices.push_back(v); }
     mx.children.clear(); mx.fx.clear(); mx.voices.clear(); mx.events.clear(); mx.messages.clear(); mx.bus_events.clear();
     mx.removed = true;
     g->mixer_alive_tab.set((size_t)gone[i], 0);
@@ -675,14 +602,10 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   if (!opt) { pg_voice_options_default(&def); opt = &def; }
   if (!(opt->speed > 0.0)) return -set_error(PG_ERR_PARAMETER, "speed must be > 0");
   if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
-  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  // (every check of the arguments stands in front of the first allocation: what fails here has nothing to release)
   PgVoice v;
-  memset(&v, 0, sizeof v);
-  size_t n_samples = n_frames * src_channels;
-  void* d_pcm = nullptr;
-  if (pg_malloc(&d_pcm, n_samples * sizeof(float)) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "pg_malloc(pcm) failed"));
-  if (pg_memcpy(d_pcm, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "pcm upload failed"));
-  v.pcm = (const float*)d_pcm;
+  voice_init_neutral(g, v, opt, opt->volume, opt->panning);
+  const size_t n_samples = n_frames * src_channels;
   // the rate the file source is created with: the mixer's, unless the caller asks for a ResampledSource behind it (source_rate)
   const uint32_t inner_rate = opt->source_rate ? opt->source_rate : g->sample_rate;
   v.n_samples = n_samples; v.channels = src_channels; v.src_rate = src_rate; v.out_rate = inner_rate;
@@ -701,22 +624,19 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
     v.loop_end = std::min<uint64_t>(opt->loop_end, fc);
     if (v.loop_start >= v.loop_end) return -set_error(PG_ERR_PARAMETER, "file buffer loop range is out of bounds");
   }
-  // VolumeFader::new + optional fade-in (file/common.rs:69-75, fader.rs:36-91)
-  v.fader_state = 0; v.fader_current = 1.0f; v.fader_target = 1.0f; v.fader_inertia = 1.0f;
-  if (opt->fade_in_seconds > 0.0f) {
+  if (opt->fade_in_seconds > 0.0f) {  // optional fade-in (file/common.rs:69-75, fader.rs:36-91)
     v.fader_state = 1; v.fader_current = 0.0f; v.fader_target = 1.0f;
     float samples_duration = (float)inner_rate * opt->fade_in_seconds / 4.605f;
     v.fader_inertia = 1.0f - std::exp(-1.0f / samples_duration);
   }
   v.fade_out_seconds = opt->fade_out_seconds;
-  // AmplifiedSource / PannedSource: ExponentialSmoothedValue::new(value, source.sample_rate())
-  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};
-  v.volume = make_smooth(exp_spec, opt->volume, g->sample_rate);
-  v.panning = make_smooth(exp_spec, opt->panning, g->sample_rate);
-  v.start_time = opt->start_time;
-  v.active = 1;
-  v.persistent = opt->non_transient != 0;
   v.current_speed = opt->speed; v.target_speed = opt->speed; v.speed_glide_rate = 0.0f; v.samples_to_next_speed_update = 0;
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  HostVoice hv;
+  auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.d_stage) (void)pg_free(hv.d_stage); };   // (error returns below)
+  if (pg_malloc(&hv.d_pcm, n_samples * sizeof(float)) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "pg_malloc(pcm) failed"));
+  if (pg_memcpy(hv.d_pcm, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "pcm upload failed")); }
+  v.pcm = (const float*)hv.d_pcm;
   {  // resampler schedule cache class: voices sharing the f32 ratio; the first one publishes
     uint32_t rb;
     memcpy(&rb, &v.ratio, 4);
@@ -725,7 +645,7 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
       PgSchedEntry blank;
       memset(&blank, 0, sizeof blank);
       int i0 = -1, i1 = -1;
-      if (g->d_sched.push(blank, &i0) || g->d_sched.push(blank, &i1)) return -graph_fail(g, PG_ERR_DEVICE);
+      if (g->d_sched.push(blank, &i0) || g->d_sched.push(blank, &i1)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
       it = g->sched_class_of_ratio.emplace(rb, i0 / 2).first;
       v.sched_rep = 1;
     }
@@ -733,39 +653,22 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   }
   // ConvertedSource::new (converted.rs:15-45): a source whose rate is not the mixer's gets ResampledSource::new(source, mixer rate, Default)
   // = a cubic resampler inner rate -> mixer rate (speed 1.0, resampled.rs:44-98) with two TempBuffers of 512 frames
-  void* d_stage = nullptr;
-  if (inner_rate != g->sample_rate) {
+  hv.outer = inner_rate != g->sample_rate;
+  if (hv.outer) {
     v.outer_on = 1;
     v.outer_ratio = (float)((double)inner_rate / (double)g->sample_rate);
     const size_t stage_floats = 2 * 512 * (size_t)src_channels;
-    if (pg_malloc(&d_stage, stage_floats * sizeof(float)) != hipSuccess || pg_memset(d_stage, 0, stage_floats * sizeof(float)) != hipSuccess)
+    if (pg_malloc(&hv.d_stage, stage_floats * sizeof(float)) != hipSuccess || pg_memset(hv.d_stage, 0, stage_floats * sizeof(float)) != hipSuccess) {
+      release();
       return -graph_fail(g, set_error(PG_ERR_DEVICE, "hipMalloc(staging) failed"));
-    v.stage_in = (float*)d_stage; v.stage_out = v.stage_in + 512 * src_channels;
+    }
+    v.stage_in = (float*)hv.d_stage; v.stage_out = v.stage_in + 512 * src_channels;
     v.sched_class = -1;  // (rendered serially on the generic kernel: no schedule cache)
   }
   int dev_index = -1;
   int rc = g->d_voices.push(v, &dev_index);
-  if (rc) return -graph_fail(g, rc);
-  int id = (int)g->voices.size();
-  { HostVoice hv; hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_pcm; hv.d_stage = d_stage; hv.outer = inner_rate != g->sample_rate;
-    hv.transient = opt->non_transient == 0; g->voices.push_back(hv); }
-  g->source_unit_of_voice.push_back(-1);
-  // AddSource: sort by start time, insert BEFORE equal start times (mixed.rs:324-329)
-  HostMixer& mx = g->mixers[mixer_id];
-  size_t pos = 0;
-  while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
-  mx.voices.insert(mx.voices.begin() + pos, id);
-  if (mixer_id == 0) {
-    int slot = new_unit(g, UNIT_SOURCE);
-    if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
-    g->source_unit_of_voice[id] = slot;
-    g->main_active_voices += 1;
-    g->ever_had_main_voice = true;
-  }
-  if (!g->voice_alive_tab.append(1)) return -set_error(PG_ERR_STATE, "too many voices");
-  g->topo_dirty = true;
-  if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
-  return id;
+  if (rc) { release(); return -graph_fail(g, rc); }
+  return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_FILE);
 }
 
 // ---- host-fed sources ------------------------------------------------------------------------------------------------------------
@@ -787,65 +690,35 @@ int pg_graph_add_stream_voice(pg_graph* g, int mixer_id, uint32_t channels, uint
   if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
   PgVoice v;
-  memset(&v, 0, sizeof v);
+  voice_init_neutral(g, v, opt, opt->volume, opt->panning);
   const size_t ring_floats = capacity_frames * channels;
-  void* d_ring = nullptr;
-  float* h_ring = nullptr;
-  void* d_stage = nullptr;
-  auto release = [&]() { if (d_ring) (void)pg_free(d_ring); if (h_ring) (void)pg_host_free(h_ring); if (d_stage) (void)pg_free(d_stage); };   // (error returns below)
-  if (pg_malloc(&d_ring, ring_floats * sizeof(float)) != hipSuccess || pg_memset(d_ring, 0, ring_floats * sizeof(float)) != hipSuccess ||
-      pg_host_malloc((void**)&h_ring, ring_floats * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+  HostVoice hv;   // (d_pcm: the device ring)
+  hv.stream = true; hv.channels = channels; hv.cap_frames = capacity_frames; hv.outer = rate != g->sample_rate;
+  auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.h_ring) (void)pg_host_free(hv.h_ring); if (hv.d_stage) (void)pg_free(hv.d_stage); };   // (error returns below)
+  if (pg_malloc(&hv.d_pcm, ring_floats * sizeof(float)) != hipSuccess || pg_memset(hv.d_pcm, 0, ring_floats * sizeof(float)) != hipSuccess ||
+      pg_host_malloc((void**)&hv.h_ring, ring_floats * sizeof(float), hipHostMallocDefault) != hipSuccess) {
     release();
     return -graph_fail(g, set_error(PG_ERR_DEVICE, "ring allocation failed"));
   }
-  v.pcm = (const float*)d_ring;
+  v.pcm = (const float*)hv.d_pcm;
   v.channels = channels; v.src_rate = rate; v.out_rate = rate; v.ratio = 1.0f;
   v.stream_on = 1; v.stream_cap = (uint32_t)capacity_frames; v.stream_fed = 0;
-  v.fader_state = 0; v.fader_current = 1.0f; v.fader_target = 1.0f; v.fader_inertia = 1.0f;
-  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};
-  v.volume = make_smooth(exp_spec, opt->volume, g->sample_rate);
-  v.panning = make_smooth(exp_spec, opt->panning, g->sample_rate);
-  v.start_time = opt->start_time;
-  v.active = 1;
-  v.persistent = opt->non_transient != 0;
   v.current_speed = 1.0; v.target_speed = 1.0;
   v.sched_class = -1;
-  if (rate != g->sample_rate) {  // ConvertedSource::new -> ResampledSource::new(source, mixer rate, Default)  (converted.rs:15-45, resampled.rs:44-98)
+  if (hv.outer) {  // ConvertedSource::new -> ResampledSource::new(source, mixer rate, Default)  (converted.rs:15-45, resampled.rs:44-98)
     v.outer_on = 1;
     v.outer_ratio = (float)((double)rate / (double)g->sample_rate);
     const size_t stage_floats = 2 * 512 * (size_t)channels;
-    if (pg_malloc(&d_stage, stage_floats * sizeof(float)) != hipSuccess || pg_memset(d_stage, 0, stage_floats * sizeof(float)) != hipSuccess) {
+    if (pg_malloc(&hv.d_stage, stage_floats * sizeof(float)) != hipSuccess || pg_memset(hv.d_stage, 0, stage_floats * sizeof(float)) != hipSuccess) {
       release();
       return -graph_fail(g, set_error(PG_ERR_DEVICE, "hipMalloc(staging) failed"));
     }
-    v.stage_in = (float*)d_stage; v.stage_out = v.stage_in + 512 * channels;
+    v.stage_in = (float*)hv.d_stage; v.stage_out = v.stage_in + 512 * channels;
   }
   int dev_index = -1;
   int rc = g->d_voices.push(v, &dev_index);
   if (rc) { release(); return -graph_fail(g, rc); }
-  const int id = (int)g->voices.size();
-  HostVoice hv;
-  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_ring; hv.d_stage = d_stage; hv.outer = rate != g->sample_rate;
-  hv.stream = true; hv.h_ring = h_ring; hv.channels = channels; hv.cap_frames = capacity_frames;
-  hv.transient = opt->non_transient == 0;
-  g->voices.push_back(hv);
-  g->stream_voices.push_back(id);
-  g->source_unit_of_voice.push_back(-1);
-  HostMixer& mx = g->mixers[mixer_id];
-  size_t pos = 0;
-  while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
-  mx.voices.insert(mx.voices.begin() + pos, id);
-  if (mixer_id == 0) {
-    int slot = new_unit(g, UNIT_SOURCE);
-    if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
-    g->source_unit_of_voice[id] = slot;
-    g->main_active_voices += 1;
-    g->ever_had_main_voice = true;
-  }
-  if (!g->voice_alive_tab.append(2)) return -set_error(PG_ERR_STATE, "too many voices");   // (2: alive and host-fed — no seek, no speed)
-  g->topo_dirty = true;
-  if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
-  return id;
+  return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_HOST_FED);
 }
 static HostVoice* stream_voice(pg_graph* g, int voice_id) {
   if (voice_id < 0 || voice_id >= (int)g->voices.size() || !g->voices[voice_id].stream) { set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a host-fed source", voice_id); return nullptr; }
@@ -879,11 +752,9 @@ int pg_graph_end_stream_voice(pg_graph* g, int voice_id) {
 int64_t pg_graph_stream_voice_consumed(pg_graph* g, int voice_id) {
   HostVoice* hv = stream_voice(g, voice_id);
   if (!hv) return -1;
-  (void)hipSetDevice(g->device);
-  if (pg_stream_sync(g->stream) != hipSuccess || (g->last_stream && g->last_stream != g->stream && pg_stream_sync(g->last_stream) != hipSuccess)) return -1;
-  if (graph_flush_blocking(g)) return -1;
+  // (a record still in the staging block belongs to a voice added since the last write: the streams are idle, the upload needs no wait in front of it)
   uint64_t rd = 0;
-  if (pg_memcpy(&rd, (const char*)(g->d_voices.d + hv->dev_index) + offsetof(PgVoice, playback_pos), 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (graph_flush_blocking(g) || graph_read_back(g, &rd, (const char*)(g->d_voices.d + hv->dev_index) + offsetof(PgVoice, playback_pos), 8)) return -1;
   hv->consumed_known = rd;
   return (int64_t)rd;
 }
@@ -897,12 +768,6 @@ static int fx_kind_of(pg_graph* g, int effect_id) {  // -1: unknown or removed
   if (effect_id < 0 || (size_t)effect_id >= g->fx_kind_tab.size()) return -1;
   return (int)g->fx_kind_tab.get((size_t)effect_id);
 }
-static bool voice_alive(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) != 0; }
-// Seek and speed exist on FilePlaybackHandle only (src/player/handles/file.rs): a host-fed source (the host's own `dyn Source` behind a ring) has
-// neither a position to seek to nor a resampler to re-target — the device would rewind the ring's read position over stale frames.
-static bool voice_is_granular(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) >= 3; }
-static bool voice_has_matrix(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 4; }   // (4: granular with a modulation matrix)
-static bool voice_is_host_fed(pg_graph* g, int voice_id) { return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() && g->voice_alive_tab.get((size_t)voice_id) == 2; }
 
 int pg_graph_schedule_param(pg_graph* g, int effect_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
   const int kind = fx_kind_of(g, effect_id);
@@ -926,406 +791,60 @@ int pg_graph_schedule_reset(pg_graph* g, int effect_id, uint64_t sample_time) {
   m.type = pgc::CT_FX_RESET; m.id = effect_id; m.sample_time = sample_time;
   return ctrl_push(g, m);
 }
-static int voice_message(pg_graph* g, int voice_id, int type, float value, double dvalue, uint64_t sample_time) {
-  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = type; m.id = voice_id; m.value = value; m.dvalue = dvalue; m.sample_time = sample_time;
-  return ctrl_push(g, m);
-}
-int pg_graph_set_voice_volume(pg_graph* g, int voice_id, float volume, uint64_t sample_time) { return voice_message(g, voice_id, pgc::CT_VOICE_VOLUME, volume, 0.0, sample_time); }
-int pg_graph_set_voice_panning(pg_graph* g, int voice_id, float panning, uint64_t sample_time) { return voice_message(g, voice_id, pgc::CT_VOICE_PAN, panning, 0.0, sample_time); }
+// (VOICE_FILE: the call is for every living voice)
+int pg_graph_set_voice_volume(pg_graph* g, int voice_id, float volume, uint64_t sample_time) { return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_VOLUME, sample_time, volume); }
+int pg_graph_set_voice_panning(pg_graph* g, int voice_id, float panning, uint64_t sample_time) { return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_PAN, sample_time, panning); }
+// Seek and speed exist on FilePlaybackHandle only (src/player/handles/file.rs): a host-fed source (the host's own `dyn Source` behind a ring) has
+// neither a position to seek to nor a resampler to re-target — the device would rewind the ring's read position over stale frames.
 int pg_graph_set_voice_speed(pg_graph* g, int voice_id, double speed, float glide, uint64_t sample_time) {
   if (!(speed > 0.0)) return set_error(PG_ERR_PARAMETER, "speed must be > 0");
-  if (voice_is_host_fed(g, voice_id)) return set_error(PG_ERR_PARAMETER, "Source with id %d is host-fed: it takes volume, panning and stop only", voice_id);
-  return voice_message(g, voice_id, pgc::CT_VOICE_SPEED, glide, speed, sample_time);
+  if (voice_kind(g, voice_id) == VOICE_HOST_FED) return set_error(PG_ERR_PARAMETER, "Source with id %d is host-fed: it takes volume, panning and stop only", voice_id);
+  return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_SPEED, sample_time, glide, 0, speed);
 }
 int pg_graph_seek_voice(pg_graph* g, int voice_id, double position_seconds, uint64_t sample_time) {
   if (!(position_seconds >= 0.0)) return set_error(PG_ERR_PARAMETER, "seek position must be >= 0");
-  if (voice_is_host_fed(g, voice_id)) return set_error(PG_ERR_PARAMETER, "Source with id %d is host-fed: it takes volume, panning and stop only", voice_id);
-  if (voice_is_granular(g, voice_id)) return set_error(PG_ERR_STATE, "Source with id %d is a granular voice: its grains have positions of their own, there is nothing to seek", voice_id);
-  return voice_message(g, voice_id, pgc::CT_VOICE_SEEK, 0.0f, position_seconds, sample_time);
+  const VoiceKind kind = voice_kind(g, voice_id);
+  if (kind == VOICE_HOST_FED) return set_error(PG_ERR_PARAMETER, "Source with id %d is host-fed: it takes volume, panning and stop only", voice_id);
+  if (voice_kind_is_granular(kind)) return set_error(PG_ERR_STATE, "Source with id %d is a granular voice: its grains have positions of their own, there is nothing to seek", voice_id);
+  return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_SEEK, sample_time, 0.0f, 0, position_seconds);
 }
 int pg_graph_stop_voice(pg_graph* g, int voice_id, uint64_t sample_time) {  // MixerMessage::StopSource (mixed.rs:389-400): not an event
-  return voice_message(g, voice_id, pgc::CT_VOICE_STOP, 0.0f, 0.0, sample_time);
+  return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_STOP, sample_time);
 }
 // SamplerVoice::stop (generator/sampler/voice.rs:196-212): an event of the voice's mixer, like the other voice commands — the block is split at its frame
 int pg_graph_release_voice(pg_graph* g, int voice_id, uint64_t sample_time) {
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  return voice_message(g, voice_id, pgc::CT_VOICE_RELEASE, 0.0f, 0.0, sample_time);
-}
-void pg_ahdsr_params_default(pg_ahdsr_params* p) {  // AhdsrParameters::default (utils/ahdsr.rs:348-359)
-  if (!p) return;
-  p->attack_s = 0.010f; p->attack_scaling = 0.0f; p->hold_s = 1.0f; p->decay_s = 0.5f; p->decay_scaling = 0.0f; p->sustain_level = 0.75f; p->release_s = 1.0f; p->release_scaling = 0.0f;
-}
-// AhdsrParameters::new_with_scaling + set_sample_rate(sample_rate) (ahdsr.rs:75-98, :123-136), setter by setter in the reference's order: the
-// first setup runs at the placeholder rate with the sustain level still 0 when set_decay_time divides (:205-214, :307-309); the second one —
-// set_sample_rate's, skipped when the rate IS the placeholder — is what gives decay_rate its final value.
-static PgEnvParams ahdsr_build_params(const pg_ahdsr_params& a, uint32_t sample_rate) {
-  PgEnvParams p;
-  memset(&p, 0, sizeof p);
-  uint32_t sr = 66666;  // UNINITIALIZED_SAMPLE_RATE
-  auto set_attack = [&]() { p.attack_rate = a.attack_s == 0.0f ? FLT_MAX : 1.0f / (a.attack_s * (float)sr); };
-  auto set_decay = [&]() { p.decay_rate = a.decay_s == 0.0f ? FLT_MAX : (1.0f - p.sustain_level) / (a.decay_s * (float)sr); };
-  auto set_release = [&]() { p.release_rate = a.release_s == 0.0f ? FLT_MAX : 1.0f / (a.release_s * (float)sr); };
-  set_attack(); p.attack_scaling = a.attack_scaling; set_decay(); p.decay_scaling = a.decay_scaling; p.sustain_level = a.sustain_level; set_release(); p.release_scaling = a.release_scaling;
-  if (sr != sample_rate) { sr = sample_rate; set_attack(); set_decay(); p.sustain_level = a.sustain_level; set_release(); }
-  p.hold_samples = a.hold_s * (float)sr;
-  p.zero_times = (a.hold_s == 0.0f ? PG_AHDSR_HOLD_ZERO : 0) | (a.decay_s == 0.0f ? PG_AHDSR_DECAY_ZERO : 0) | (a.release_s == 0.0f ? PG_AHDSR_RELEASE_ZERO : 0);
-  return p;
-}
-int pg_graph_set_voice_envelope(pg_graph* g, int voice_id, const pg_ahdsr_params* p) {
-  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  drain_control_messages(g);
-  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  HostVoice& hv = g->voices[voice_id];
-  // note_on belongs to the voice's start (voice.rs:181-184): no envelope for a voice that has rendered frames already
-  // (a voice renders in every write that ends behind its start time — a start time at or before a write's position starts it at once,
-  // voice_process — so it has rendered iff a write issued since it was added ended behind its start time, wherever the earlier ones stood)
-  uint64_t end_since_add = 0;
-  for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) { end_since_add = w.second; break; }
-  if (end_since_add > hv.start_time) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: an envelope is attached before the voice starts", voice_id);
-  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
-  if (graph_env_reserve(g, std::max<size_t>(g->voices.size(), (size_t)hv.dev_index + 1))) return graph_fail(g, PG_ERR_DEVICE);
-  PgEnv e;
-  memset(&e, 0, sizeof e);
-  e.on = 1;
-  e.params = ahdsr_build_params(*p, g->sample_rate);
-  // AhdsrEnvelope::note_on(parameters, 1.0) (ahdsr.rs:402-419)
-  e.state.target_volume = 1.0f;
-  if (e.params.attack_rate == FLT_MAX) {
-    e.state.output = 1.0f;
-    if (!(e.params.zero_times & PG_AHDSR_HOLD_ZERO)) { e.state.stage = PG_AHDSR_HOLD; e.state.hold_samples_remaining = e.params.hold_samples; }
-    else e.state.stage = PG_AHDSR_DECAY;
-  } else { e.state.output = 0.0f; e.state.stage = PG_AHDSR_ATTACK; }
-  (void)hipSetDevice(g->device);
-  HIP_TRY(pg_memcpy(g->d_env + hv.dev_index, &e, sizeof e, hipMemcpyHostToDevice));
-  g->h_env_done[hv.dev_index] = 0;
-  if (hv.gran >= 0) {  // pg_grain_kernel: a release is the envelope's note_off from here on, not GrainPool::stop
-    const int32_t one = 1;
-    HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, has_env), &one, sizeof one, hipMemcpyHostToDevice));
-  }
-  if (!hv.env_live) g->env_voices.push_back(voice_id);
-  hv.env = true; hv.env_live = true;
-  g->topo_dirty = true;
-  return PG_OK;
-}
-int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id) {
-  if (!g || voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].mixer < 0 || !g->voices[voice_id].env || !g->d_env) return -1;
-  (void)hipSetDevice(g->device);
-  if (pg_stream_sync(g->stream) != hipSuccess) return -1;
-  if (g->last_stream && g->last_stream != g->stream && pg_stream_sync(g->last_stream) != hipSuccess) return -1;
-  PgEnv e;
-  if (pg_memcpy(&e, g->d_env + g->voices[voice_id].dev_index, sizeof e, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return e.on ? (int)e.state.stage : -1;
-}
-// ---- granular voices (src/generator/sampler/granular.rs; pg_k_grain.hip) ----
-// The Xoshiro256++ state an all-zero `rng_state` stands for (pg_granular_params, pg_mod_lfo): SplitMix64 of the fixed seed, four times
-static void rng_default_state(uint64_t out[4]) {
-  uint64_t z = 0x5EED0000ull;
-  for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; out[i] = x ^ (x >> 31); }
-}
-void pg_granular_params_default(pg_granular_params* p) {  // GranularParameters::default (granular.rs:268-283)
-  if (!p) return;
-  memset(p, 0, sizeof *p);
-  p->overlap_mode = 0; p->window = 2; p->size = 100.0f; p->density = 10.0f; p->playback_direction = 0; p->position = 0.5f;
-}
-int pg_granular_params_check(const pg_granular_params* p) {  // GranularParameters::validate (granular.rs:291-335); a NaN fails every range
-  if (!p) return set_error(PG_ERR_PARAMETER, "granular parameters must not be null");
-  if (p->overlap_mode < 0 || p->overlap_mode > 1) return set_error(PG_ERR_PARAMETER, "Invalid grain overlap mode: %d", p->overlap_mode);
-  if (p->window < 0 || p->window >= PG_GRAIN_WINDOWS) return set_error(PG_ERR_PARAMETER, "Invalid grain window mode: %d", p->window);
-  if (p->playback_direction < 0 || p->playback_direction > 2) return set_error(PG_ERR_PARAMETER, "Invalid grain playback direction: %d", p->playback_direction);
-  if (!(p->size >= 1.0f && p->size <= 1000.0f)) return set_error(PG_ERR_PARAMETER, "Grain size must be between 1 and 1000 ms");
-  if (!(p->density >= 1.0f && p->density <= 100.0f)) return set_error(PG_ERR_PARAMETER, "Grain density must be between 1.0 and 100.0 Hz");
-  if (!(p->spray >= 0.0f && p->spray <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain spray must be between 0.0 and 1.0");
-  if (!(p->variation >= 0.0f && p->variation <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain variation must be between 0.0 and 1.0");
-  if (!(p->pan_spread >= 0.0f && p->pan_spread <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain pan spread must be between 0.0 and 1.0");
-  if (!(p->position >= 0.0f && p->position <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Position must be between 0.0 and 1.0");
-  if (!(p->step >= -4.0f && p->step <= 4.0f)) return set_error(PG_ERR_PARAMETER, "Step must be between -4.0 and 4.0");
-  if (p->has_loop_range && !(p->loop_start >= 0.0f && p->loop_start <= 1.0f && p->loop_end >= 0.0f && p->loop_end <= 1.0f))
-    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)p->loop_start, (double)p->loop_end);
-  return PG_OK;
-}
-int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
-  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
-  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (!mono_pcm || n_frames < 1) return -set_error(PG_ERR_PARAMETER, "Need a valid, non empty sample buffer");
-  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
-  drain_control_messages(g);
-  pg_voice_options def;
-  if (!opt) { pg_voice_options_default(&def); opt = &def; }
-  if (!(opt->speed > 0.0)) return -set_error(PG_ERR_PARAMETER, "speed must be > 0");
-  if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
-  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
-  // the voice as the mixer sees it: a stereo source at the graph's rate whose frames pg_grain_kernel renders; AmplifiedSource / PannedSource /
-  // fader are neutral — the granular branch of SamplerVoice::process does not pass them (voice.rs:412-427)
-  PgVoice v;
-  memset(&v, 0, sizeof v);
-  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
-  v.fader_state = 0; v.fader_current = 1.0f; v.fader_target = 1.0f; v.fader_inertia = 1.0f;
-  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};
-  v.volume = make_smooth(exp_spec, 1.0f, g->sample_rate);
-  v.panning = make_smooth(exp_spec, 0.0f, g->sample_rate);
-  v.start_time = opt->start_time;
-  v.active = 1;
-  v.persistent = opt->non_transient != 0;
-  v.current_speed = 1.0; v.target_speed = 1.0;
-  v.sched_class = -1;
-  void* d_pcm = nullptr;
-  void* d_stage = nullptr;
-  auto release = [&]() { if (d_pcm) (void)pg_free(d_pcm); if (d_stage) (void)pg_free(d_stage); };
-  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
-  if (pg_malloc(&d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      pg_malloc(&d_stage, stage_bytes) != hipSuccess || pg_memset(d_stage, 0, stage_bytes) != hipSuccess) {
-    release();
-    return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice allocation failed"));
-  }
-  if (graph_gran_reserve(g, g->gran_n + 1)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
-  int dev_index = -1;
-  int rc = g->d_voices.push(v, &dev_index);
-  if (rc) { release(); return -graph_fail(g, rc); }
-  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + 1, (size_t)dev_index + 1))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
-  // GrainPool::new + start(parameters, speed, volume, panning) (granular.rs:384-429, :474-489)
-  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
-  memset(r.get(), 0, sizeof(PgGrainVoice));
-  PgGrainParams& q = r->params;
-  q.overlap_mode = p->overlap_mode; q.window = p->window; q.size = p->size; q.density = p->density; q.variation = p->variation; q.spray = p->spray;
-  q.pan_spread = p->pan_spread; q.direction = p->playback_direction; q.position = p->position; q.step = p->step;
-  q.has_loop = p->has_loop_range ? 1 : 0; q.loop_start = p->has_loop_range ? p->loop_start : 0.0f; q.loop_end = p->has_loop_range ? p->loop_end : 0.0f;
-  PgGrainPool& pool = r->pool;
-  if ((p->rng_state[0] | p->rng_state[1] | p->rng_state[2] | p->rng_state[3]) != 0) memcpy(pool.rng, p->rng_state, sizeof pool.rng);
-  else rng_default_state(pool.rng);
-  pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
-  pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
-  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
-  for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
-  r->pcm = (const float*)d_pcm; r->n_frames = n_frames; r->staged = (float*)d_stage; r->stage_pos = 0;
-  r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
-  const int rec = (int)g->gran_n;
-  const int32_t rec32 = rec;
-  (void)hipSetDevice(g->device);
-  if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
-      pg_memcpy(g->d_grain_of_voice + dev_index, &rec32, sizeof rec32, hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
-  g->h_gran_ended[rec] = 0;
-  g->gran_n += 1;
-  if (graph_gran_publish(g)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
-  const int id = (int)g->voices.size();
-  HostVoice hv;
-  hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.d_pcm = d_pcm; hv.d_stage = d_stage;
-  hv.transient = opt->non_transient == 0; hv.gran = rec; hv.gran_live = true;
-  g->voices.push_back(hv);
-  g->gran_voices.push_back(id); g->gran_live_dirty = true;
-  g->source_unit_of_voice.push_back(-1);
-  // AddSource: sort by start time, insert BEFORE equal start times (mixed.rs:324-329)
-  HostMixer& mx = g->mixers[mixer_id];
-  size_t pos = 0;
-  while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
-  mx.voices.insert(mx.voices.begin() + pos, id);
-  if (mixer_id == 0) {
-    int slot = new_unit(g, UNIT_SOURCE);
-    if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
-    g->source_unit_of_voice[id] = slot;
-    g->main_active_voices += 1;
-    g->ever_had_main_voice = true;
-  }
-  if (!g->voice_alive_tab.append(3)) return -set_error(PG_ERR_STATE, "too many voices");   // (3: alive and granular — no seek)
-  g->topo_dirty = true;
-  if (graph_reserve(g)) return -graph_fail(g, PG_ERR_DEVICE);
-  return id;
-}
-int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
-  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
-  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  (void)hipSetDevice(g->device);
-  HIP_TRY(pg_stream_sync(g->stream));
-  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
-  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
-  HIP_TRY(pg_memcpy(r.get(), g->d_gran + g->voices[voice_id].gran, sizeof(PgGrainVoice), hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof *out);
-  const PgGrainPool& pool = r->pool;
-  out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
-  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->overlap_mode = pool.overlap_mode; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
-  memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
-  for (int i = 0; i < PG_GRAIN_POOL; ++i) {
-    const PgGrain& s = r->grains[i];
-    pg_grain_slot& o = out->slots[i];
-    o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
-    o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
-  }
-  return PG_OK;
-}
-// ---- the granular parameters and the loop range while the voice plays (Sampler::set_granular_parameter, sampler.rs:299-360, :1132-1147;
-// SamplerMessage::SetLoopRange -> GrainPool::set_loop_range, sampler.rs:1246-1270, granular.rs:516-518) ----
-// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
-static int grain_message(pg_graph* g, int voice_id, int type, int param, float value, float value2, uint64_t sample_time) {
-  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  if (!voice_is_granular(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = type; m.id = voice_id; m.param = param; m.value = value; m.value2 = value2; m.sample_time = sample_time;
-  return ctrl_push(g, m);
-}
-int pg_graph_set_voice_granular_parameter(pg_graph* g, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
-  const int pi = find_granular_param(fourcc);
-  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown granular playback parameter 0x%08x", fourcc);
-  if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  float raw;
-  if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) {  // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
-    if (!voice_alive(g, voice_id) || !voice_is_granular(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-    return PG_OK;
-  }
-  return grain_message(g, voice_id, pgc::CT_VOICE_GRAIN_PARAM, pi, raw, 0.0f, sample_time);
-}
-int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time) {
-  if (has_loop_range && !(loop_start >= 0.0f && loop_start <= 1.0f && loop_end >= 0.0f && loop_end <= 1.0f))
-    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)loop_start, (double)loop_end);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  return grain_message(g, voice_id, pgc::CT_VOICE_GRAIN_LOOP, has_loop_range ? 1 : 0, has_loop_range ? loop_start : 0.0f, has_loop_range ? loop_end : 0.0f, sample_time);
-}
-int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out) {
-  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
-  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  (void)hipSetDevice(g->device);
-  HIP_TRY(pg_stream_sync(g->stream));
-  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
-  PgGrainParams q;
-  HIP_TRY(pg_memcpy(&q, (const char*)(g->d_gran + g->voices[voice_id].gran) + offsetof(PgGrainVoice, params), sizeof q, hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof *out);
-  out->overlap_mode = q.overlap_mode; out->window = q.window; out->size = q.size; out->density = q.density; out->variation = q.variation; out->spray = q.spray;
-  out->pan_spread = q.pan_spread; out->playback_direction = q.direction; out->position = q.position; out->step = q.step;
-  out->has_loop_range = q.has_loop; out->loop_start = q.loop_start; out->loop_end = q.loop_end;
-  return PG_OK;
-}
-// ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
-static_assert(PG_MOD_SOURCES == PG_GMOD_SOURCES && PG_MOD_TARGETS == PG_GMOD_TARGETS, "the header's and the device's matrix agree");
-static float mod_clamp_rate(float rate_hz) { return rate_hz < 0.01f ? 0.01f : (rate_hz > 20.0f ? 20.0f : rate_hz); }   // FloatParameter::clamp_value of ML1R / ML2R (sampler.rs:369-384)
-void pg_modulation_params_default(pg_modulation_params* p) {  // Sampler::modulation_config (sampler.rs:369-427), a note at full velocity
-  if (!p) return;
-  memset(p, 0, sizeof *p);
-  p->lfo[0].rate_hz = 1.0f; p->lfo[0].waveform = 0;
-  p->lfo[1].rate_hz = 2.0f; p->lfo[1].waveform = 1;
-  p->velocity = 1.0f; p->note = 60;
-}
-static int mod_check_route(int source, int target, float amount) {  // ModulationState::set_modulation (state.rs:174-201)
-  if (source < 0 || source >= PG_MOD_SOURCES) return set_error(PG_ERR_PARAMETER, "Unknown modulation source '%d'", source);
-  if (target < 0 || target >= PG_MOD_TARGETS) return set_error(PG_ERR_PARAMETER, "Unknown modulation target '%d'", target);
-  if (!(amount >= -1.0f && amount <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Modulation amount must be in range -1..-1.0 but is %g", (double)amount);
-  return PG_OK;
-}
-int pg_modulation_params_check(const pg_modulation_params* p) {
-  if (!p) return set_error(PG_ERR_PARAMETER, "modulation parameters must not be null");
-  for (int l = 0; l < 2; ++l) {
-    if (p->lfo[l].rate_hz != p->lfo[l].rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", l + 1);
-    if (p->lfo[l].waveform < 0 || p->lfo[l].waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", l + 1, p->lfo[l].waveform);
-  }
-  if (!(p->velocity >= 0.0f && p->velocity <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Velocity must be in range [0.0, 1.0]");
-  if (p->note < 0 || p->note > 127) return set_error(PG_ERR_PARAMETER, "MIDI note must be in range [0, 127]");
-  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { const int rc = mod_check_route(s, t, p->routes[s][t].amount); if (rc) return rc; }
-  return PG_OK;
-}
-int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_modulation_params* p) {
-  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  drain_control_messages(g);
-  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  HostVoice& hv = g->voices[voice_id];
-  if (hv.gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  // the matrix is created with the voice and note_on belongs to its start (voice.rs:341-373, :181-184): not for a voice that has rendered frames
-  // (see pg_graph_set_voice_envelope)
-  uint64_t end_since_add = 0;
-  for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) { end_since_add = w.second; break; }
-  if (end_since_add > hv.start_time) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: the modulation matrix is attached before the voice starts", voice_id);
-  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
-  PgGrainMod m;
-  memset(&m, 0, sizeof m);
-  m.on = 1;
-  for (int l = 0; l < 2; ++l) {
-    PgModLfo& o = m.lfo[l];
-    const pg_mod_lfo& in = p->lfo[l];
-    if ((in.rng_state[0] | in.rng_state[1] | in.rng_state[2] | in.rng_state[3]) != 0) memcpy(o.rng, in.rng_state, sizeof o.rng);
-    else rng_default_state(o.rng);
-    // create_matrix: Lfo::new(sample_rate, default rate, default waveform) (state.rs:96-113, lfo.rs:70-86)
-    o.phase = 0.0f;
-    o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
-    // the parameter updates in front of the note: set_rate / set_waveform (lfo.rs:102-119)
-    o.phase_inc = (float)((double)mod_clamp_rate(in.rate_hz) / (double)g->sample_rate);
-    o.waveform = in.waveform;
-  }
-  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {  // update_target on an empty slot (matrix.rs:75-82)
-    const pg_mod_route& r = p->routes[s][t];
-    if (fabsf(r.amount) >= 0.001f) { m.amount[s][t] = r.amount; m.bipolar[s][t] = r.bipolar ? 1 : 0; }
-  }
-  // SamplerVoiceModulationState::start(note, velocity) = ModulationMatrix::note_on (matrix.rs:394-408)
-  for (int l = 0; l < 2; ++l) mod_lfo_reset(m.lfo[l]);
-  m.velocity = p->velocity;
-  m.note_pitch = (float)p->note / 127.0f;
-  (void)hipSetDevice(g->device);
-  HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, mod), &m, sizeof m, hipMemcpyHostToDevice));
-  hv.mod = true;
-  g->voice_alive_tab.set((size_t)voice_id, 4);
-  return PG_OK;
-}
-// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
-static int mod_message(pg_graph* g, int voice_id, int type, int packed, float value, uint64_t sample_time) {
-  if (!voice_alive(g, voice_id)) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  if (!voice_has_matrix(g, voice_id)) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = type; m.id = voice_id; m.param = packed; m.value = value; m.sample_time = sample_time;
-  return ctrl_push(g, m);
-}
-int pg_graph_set_voice_modulation(pg_graph* g, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
-  { const int rc = mod_check_route(source, target, amount); if (rc) return rc; }
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  const bool keep = fabsf(amount) >= 0.001f;   // update_target's threshold (matrix.rs:61): below it the route is removed, or not added
-  return mod_message(g, voice_id, pgc::CT_VOICE_MOD_ROUTE, source | (target << 8) | ((keep && bipolar) ? 1 << 16 : 0), keep ? amount : 0.0f, sample_time);
-}
-int pg_graph_clear_voice_modulation(pg_graph* g, int voice_id, int source, int target, uint64_t sample_time) {  // set_modulation(.., 0.0, false) (state.rs:223-231)
-  return pg_graph_set_voice_modulation(g, voice_id, source, target, 0.0f, 0, sample_time);
-}
-int pg_graph_set_voice_lfo_rate(pg_graph* g, int voice_id, int lfo, float rate_hz, uint64_t sample_time) {
-  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
-  if (rate_hz != rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", lfo + 1);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  return mod_message(g, voice_id, pgc::CT_VOICE_LFO_RATE, lfo, mod_clamp_rate(rate_hz), sample_time);
-}
-int pg_graph_set_voice_lfo_waveform(pg_graph* g, int voice_id, int lfo, int waveform, uint64_t sample_time) {
-  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
-  if (waveform < 0 || waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", lfo + 1, waveform);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  return mod_message(g, voice_id, pgc::CT_VOICE_LFO_WAVEFORM, lfo | (waveform << 8), 0.0f, sample_time);
-}
-int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_state* out) {
-  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
-  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  if (!g->voices[voice_id].mod) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
-  (void)hipSetDevice(g->device);
-  HIP_TRY(pg_stream_sync(g->stream));
-  if (g->last_stream && g->last_stream != g->stream) HIP_TRY(pg_stream_sync(g->last_stream));
-  PgGrainMod m;
-  HIP_TRY(pg_memcpy(&m, (const char*)(g->d_gran + g->voices[voice_id].gran) + offsetof(PgGrainVoice, mod), sizeof m, hipMemcpyDeviceToHost));
-  memset(out, 0, sizeof *out);
-  for (int l = 0; l < 2; ++l) {
-    const PgModLfo& s = m.lfo[l];
-    pg_mod_lfo_state& o = out->lfo[l];
-    o.phase = s.phase; o.phase_inc = s.phase_inc; o.sample_hold = s.sample_hold; o.jitter_current = s.jitter_current; o.jitter_target = s.jitter_target; o.waveform = s.waveform;
-    memcpy(o.rng_state, s.rng, sizeof o.rng_state);
-  }
-  out->velocity = m.velocity; out->note_pitch = m.note_pitch;
-  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
-  for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
-  return PG_OK;
+  return voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_RELEASE, sample_time);
 }
 int pg_graph_remove_voice(pg_graph* g, int voice_id) {  // MixerMessage::RemoveSource (mixed.rs:149-151,400-402)
-  const int rc = voice_message(g, voice_id, pgc::CT_VOICE_REMOVE, 0.0f, 0.0, 0);
+  const int rc = voice_message(g, voice_id, VOICE_FILE, pgc::CT_VOICE_REMOVE, 0);
   // the id is dead for every later call from here on (a second remove, a volume change: PG_ERR_NOT_FOUND as the header says), not only once the
   // next write has drained the message; messages pushed before this one are still delivered (the ring keeps their order)
-  if (rc == PG_OK) g->voice_alive_tab.set((size_t)voice_id, 0);
+  if (rc == PG_OK) g->voice_alive_tab.set((size_t)voice_id, VOICE_DEAD);
   return rc;
+}
+
+}  // extern "C"
+
+// The timed voice messages — each becomes an event of the voice's mixer — with the command a message turns into and what the command carries
+// beyond its voice (pg_dev.h: PgCmdType). The ONE list of them: drain_control_messages builds the events from it, and the removal of a source
+// finds the source's queued events by it.
+struct VoiceEvent { int32_t msg, cmd; void (*fill)(const pgc::CtrlMsg& m, uint32_t sample_rate, PgCmd& c); };
+static const VoiceEvent VOICE_EVENTS[] = {
+  {pgc::CT_VOICE_VOLUME, CMD_VOICE_VOLUME, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
+  {pgc::CT_VOICE_PAN, CMD_VOICE_PAN, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
+  {pgc::CT_VOICE_SPEED, CMD_VOICE_SPEED, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }},
+  {pgc::CT_VOICE_SEEK, CMD_VOICE_SEEK, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { memcpy(&c.value64, &m.dvalue, 8); }},
+  {pgc::CT_VOICE_RELEASE, CMD_VOICE_RELEASE, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = m.sample_time; }},
+  {pgc::CT_VOICE_MOD_ROUTE, CMD_VOICE_MOD_ROUTE, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_LFO_RATE, CMD_VOICE_LFO_RATE, [](const pgc::CtrlMsg& m, uint32_t sr, PgCmd& c) { c.value = (float)((double)m.value / (double)sr); c.value64 = (uint64_t)(uint32_t)m.param; }},   // Lfo::set_rate (lfo.rs:102-104)
+  {pgc::CT_VOICE_LFO_WAVEFORM, CMD_VOICE_LFO_WAVEFORM, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_GRAIN_PARAM, CMD_VOICE_GRAIN_PARAM, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_GRAIN_LOOP, CMD_VOICE_GRAIN_LOOP, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { uint32_t end; memcpy(&end, &m.value2, 4); c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)end << 32); }},
+};
+static bool cmd_is_voice_event(int cmd_type) {
+  for (const VoiceEvent& ve : VOICE_EVENTS) if (ve.cmd == cmd_type) return true;
+  return false;
 }
 
 static void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd) {
@@ -1336,7 +855,7 @@ static void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd
   mx.events.insert(mx.events.begin() + pos, e);
 }
 // MixedSource::process_messages (src/source/mixed.rs:294-499) for the whole graph: the writing thread only.
-static void drain_control_messages(pg_graph* g) {
+void drain_control_messages(pg_graph* g) {
   pgc::CtrlMsg m;
   while (g->ctrl.pop(m)) {
     PgCmd c;
@@ -1377,9 +896,7 @@ static void drain_control_messages(pg_graph* g) {
           mx.messages.erase(std::remove_if(mx.messages.begin(), mx.messages.end(), [&](const PgCmd& x) { return x.param == m.id; }), mx.messages.end());
           // events already queued for the source stay the mixer's events: when they come due they find no source (mixed.rs:810-845) but still
           // split the block there — like the events of a removed effect
-          for (Event& e : mx.events) if ((e.cmd.type == CMD_VOICE_VOLUME || e.cmd.type == CMD_VOICE_PAN || e.cmd.type == CMD_VOICE_SPEED || e.cmd.type == CMD_VOICE_SEEK || e.cmd.type == CMD_VOICE_RELEASE ||
-                                         e.cmd.type == CMD_VOICE_MOD_ROUTE || e.cmd.type == CMD_VOICE_LFO_RATE || e.cmd.type == CMD_VOICE_LFO_WAVEFORM ||
-                                         e.cmd.type == CMD_VOICE_GRAIN_PARAM || e.cmd.type == CMD_VOICE_GRAIN_LOOP) && e.cmd.param == m.id) {
+          for (Event& e : mx.events) if (e.cmd.param == m.id && cmd_is_voice_event(e.cmd.type)) {
             e.cmd.type = CMD_NOP; e.cmd.target = 0;
             if (hv.mixer == 0) e.cmd.param = -1;
           }
@@ -1387,27 +904,24 @@ static void drain_control_messages(pg_graph* g) {
           // definition — a transient one may have ended already: its removal shows with the next count)
           if (hv.mixer == 0 && !hv.transient && g->main_active_voices > 0) g->main_active_voices -= 1;
           g->voices[m.id].mixer = -1;
-          g->voice_alive_tab.set((size_t)m.id, 0);
+          g->voice_alive_tab.set((size_t)m.id, VOICE_DEAD);
           g->retired_voices.push_back(m.id);
           g->topo_dirty = true;
           break;
         }
         if (m.type == pgc::CT_VOICE_STOP) { c.type = CMD_VOICE_STOP; c.value64 = m.sample_time; g->mixers[hv.mixer].messages.push_back(c); break; }
-        if (m.type == pgc::CT_VOICE_VOLUME) { c.type = CMD_VOICE_VOLUME; c.value = m.value; }
-        else if (m.type == pgc::CT_VOICE_PAN) { c.type = CMD_VOICE_PAN; c.value = m.value; }
-        else if (m.type == pgc::CT_VOICE_SPEED) { c.type = CMD_VOICE_SPEED; c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }
-        else if (m.type == pgc::CT_VOICE_RELEASE) { c.type = CMD_VOICE_RELEASE; c.value64 = m.sample_time; }
-        else if (m.type == pgc::CT_VOICE_MOD_ROUTE) { c.type = CMD_VOICE_MOD_ROUTE; c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }
-        else if (m.type == pgc::CT_VOICE_LFO_RATE) { c.type = CMD_VOICE_LFO_RATE; c.value = (float)((double)m.value / (double)g->sample_rate); c.value64 = (uint64_t)(uint32_t)m.param; }   // Lfo::set_rate (lfo.rs:102-104)
-        else if (m.type == pgc::CT_VOICE_LFO_WAVEFORM) { c.type = CMD_VOICE_LFO_WAVEFORM; c.value64 = (uint64_t)(uint32_t)m.param; }
-        else if (m.type == pgc::CT_VOICE_GRAIN_PARAM) { c.type = CMD_VOICE_GRAIN_PARAM; c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }
-        else if (m.type == pgc::CT_VOICE_GRAIN_LOOP) { uint32_t e; memcpy(&e, &m.value2, 4); c.type = CMD_VOICE_GRAIN_LOOP; c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)e << 32); }
-        else { c.type = CMD_VOICE_SEEK; memcpy(&c.value64, &m.dvalue, 8); }
-        push_event(g, hv.mixer, m.sample_time, c);
+        for (const VoiceEvent& ve : VOICE_EVENTS) if (ve.msg == m.type) {
+          c.type = ve.cmd;
+          ve.fill(m, g->sample_rate, c);
+          push_event(g, hv.mixer, m.sample_time, c);
+          break;
+        }
       } break;
     }
   }
 }
+
+extern "C" {
 
 int pg_graph_diag(pg_graph* g, unsigned long long* out, int n) {  // diagnostic builds: shader-clock stamps of workgroup 0
   (void)hipSetDevice(g->device);
@@ -1853,7 +1367,6 @@ bool graph_is_empty(const pg_graph* g) {
   for (size_t m = 1; m < g->mixers.size(); ++m) no_sub_mixers &= g->mixers[m].removed;
   return g->main_active_voices == 0 && g->mixers[0].fx.empty() && no_sub_mixers && g->mixers[0].events.empty();
 }
-void drain_control_messages_public(pg_graph* g) { drain_control_messages(g); }
 uint64_t graph_next_main_event(const pg_graph* g) { return g->mixers[0].events.empty() ? UINT64_MAX : g->mixers[0].events.front().sample_time; }
 // The number of main-mixer sources still alive -> the graph's mapped status word, behind everything enqueued on `stream` so far;
 // graph_collect_status reads it once the stream has drained.
@@ -2047,15 +1560,9 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
   if (g->last_stream && g->last_stream != stream) { if (pg_stream_sync(g->last_stream) != hipSuccess) { g->failed = true; return 0; } g->cmds_since_sync = 0; }
   g->last_stream = stream;
   if (begin) { graph_begin_write(g, pos); g->call_end = pos + n_samples / 2; }
-  if (!g->env_voices.empty()) graph_poll_envelopes(g);
-  if (!g->gran_voices.empty()) graph_poll_granular(g);
+  graph_sampler_poll(g);
   if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return 0; } }
-  if (g->gran_live_dirty) {  // the records pg_grain_kernel renders from here on
-    std::vector<int32_t> live;
-    for (int id : g->gran_voices) live.push_back(g->voices[id].gran);
-    if (g->d_gran_live.upload_async(live, stream)) { g->failed = true; return 0; }
-    g->gran_live_dirty = false;
-  }
+  if (g->gran_live_dirty && graph_gran_upload_live(g, stream)) { g->failed = true; return 0; }
   if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return 0; } }
   if (g->overlap_stream != stream) { g->rows_free_fresh = false; g->overlap_stream = stream; }
   g->write_done_attached = false;
@@ -2459,7 +1966,7 @@ int pg_graph_process_bus_device(pg_graph* g, float* d_bus, size_t n_samples, uin
 }
 int pg_graph_audible_words(pg_graph* g) { return g->audible_valid ? g->defer_words : 0; }
 uint64_t pg_graph_next_main_event(pg_graph* g, uint64_t pos_in_frames) {
-  drain_control_messages_public(g);
+  drain_control_messages(g);
   for (const Event& e : g->mixers[0].events) if (e.sample_time > pos_in_frames) return e.sample_time;
   return UINT64_MAX;
 }

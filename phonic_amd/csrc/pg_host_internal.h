@@ -1,6 +1,6 @@
 // Internals shared by the host-side translation units of libphonic_gpu.so (pg_host.hip: the mixer graph and its write path;
-// pg_fxstate.hip: effect construction and parameter descriptors; pg_effect.hip: the standalone `Effect` handle; pg_sharded.hip: the
-// multi-GPU handle). Nothing here is part of the ABI (include/phonic_gpu.h).
+// pg_sampler.hip: envelopes, granular voices and their modulation; pg_fxstate.hip: effect construction and parameter descriptors;
+// pg_effect.hip: the standalone `Effect` handle; pg_sharded.hip: the multi-GPU handle). Nothing here is part of the ABI (include/phonic_gpu.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -208,6 +208,15 @@ struct MeterRing {
   bool in_flight[2] = {false, false};
 };
 #define PG_METER_PUB_CHUNKS 64   // chunks of 1024 published levels: never moved or freed before the graph dies (read from any thread)
+// Words in mapped host memory that a kernel sets and the host polls without a wait (pg_sampler.hip): one `ended` word per record
+struct MappedWords {
+  int32_t* h = nullptr;   // the host's view ...
+  int32_t* d = nullptr;   // ... and the device's
+  size_t cap = 0;
+  int reserve(size_t n, const MappedWords& from);   // (on an empty one) n zeroed words that begin with `from`'s; PG_ERR_DEVICE leaves it empty
+  void release();
+  volatile int32_t& operator[](size_t i) const { return *(volatile int32_t*)(h + i); }
+};
 
 // ---- the graph --------------------------------------------------------------------------------------------
 struct Event {  // MixerEvent (src/source/mixed.rs:47-109) resolved to a device command
@@ -217,8 +226,18 @@ struct Event {  // MixerEvent (src/source/mixed.rs:47-109) resolved to a device 
   int mixer;  // owning mixer (0 = main)
 };
 
+// What a voice id stands for, as the control calls of any thread see it (pg_graph::voice_alive_tab)
+enum VoiceKind : int8_t {
+  VOICE_DEAD = 0,          // removed (or never added): takes no messages
+  VOICE_FILE = 1,          // pg_graph_add_voice
+  VOICE_HOST_FED = 2,      // pg_graph_add_stream_voice: no seek, no speed
+  VOICE_GRANULAR = 3,      // pg_graph_add_granular_voice: no seek
+  VOICE_GRANULAR_MOD = 4,  // ... with a modulation matrix (pg_graph_set_voice_modulation_matrix)
+};
+static inline bool voice_kind_is_granular(VoiceKind k) { return k == VOICE_GRANULAR || k == VOICE_GRANULAR_MOD; }
+
 struct HostVoice {
-  int mixer; int dev_index; uint64_t start_time; void* d_pcm; void* d_stage; bool outer;
+  int mixer = -1; int dev_index = -1; uint64_t start_time = 0; void* d_pcm = nullptr; void* d_stage = nullptr; bool outer = false;
   // host-fed source (pg_graph_add_stream_voice): pinned ring + word the feeds are staged in, device ring = d_pcm
   bool transient = true;           // PlayingSource::is_transient (pg_voice_options::non_transient == 0)
   bool stream = false, ended = false, ended_sent = false;
@@ -341,7 +360,7 @@ struct pg_graph {
   // control path (pg_ctrl.h): messages from any thread, drained at the top of write like MixedSource::process_messages
   pgc::CtrlRing ctrl{PG_CTRL_RING};
   pgc::ChunkTable<int8_t> fx_kind_tab;     // effect id -> kind, -1 once removed (readable from any thread)
-  pgc::ChunkTable<int8_t> voice_alive_tab; // voice id -> 1 while it can take messages
+  pgc::ChunkTable<int8_t> voice_alive_tab; // voice id -> its VoiceKind: VOICE_DEAD once it takes no more messages (voice_kind)
   DeviceVec<PgSchedEntry> d_sched;       // [classes][2 banks]
   std::map<uint32_t, int> sched_class_of_ratio;
   uint64_t launch_counter = 0;
@@ -382,8 +401,7 @@ struct pg_graph {
   // per voice in mapped host memory that the exact kernel sets when an enveloped voice ends (polled at the top of a write: no wait)
   PgEnvTable* d_env_tab = nullptr; // header + entries (PgLaunch::env)
   PgEnv* d_env = nullptr;          // its entries
-  int32_t* h_env_done = nullptr;
-  size_t env_cap = 0;
+  MappedWords env_done;            // one word per entry
   std::vector<int> env_voices;     // ids of the voices whose envelope is alive
   // level metering (pg_graph_set_metering, pg_k_meter.hip)
   bool metering = false;           // owner thread's view; meter_on is what pg_graph_mixer_audio_level reads from any thread
@@ -403,23 +421,34 @@ struct pg_graph {
   // through the envelope table's header; the window tables, built with the first granular voice; one `ended` word per record in mapped host
   // memory (polled at the top of a write); the records pg_grain_kernel still renders, uploaded when the set changes
   PgGrainVoice* d_gran = nullptr;
-  size_t gran_n = 0, gran_cap = 0;
-  int32_t* d_grain_of_voice = nullptr;   // env_cap entries
+  size_t gran_n = 0;                     // records in use (room for gran_ended.cap)
+  int32_t* d_grain_of_voice = nullptr;   // one entry per entry of d_env
   float* d_grain_lut = nullptr;
-  int32_t* h_gran_ended = nullptr;       // gran_cap words, mapped
-  int32_t* d_gran_ended = nullptr;       // ... as the device sees them
+  MappedWords gran_ended;                // one word per record
   std::vector<int> gran_voices;          // ids of the living granular voices
   DeviceTable<int32_t> d_gran_live;      // their records
+  std::vector<int32_t> gran_live;        // ... as the next upload puts them together (capacity kept across writes)
   bool gran_live_dirty = false;
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };
 
-// ---- graph internals used by the sharded handle (pg_host.hip) -------------------------------------------------
+// ---- graph internals used by the sharded handle and the sampler voices (pg_host.hip) ---------------------------
 int graph_quiesce(pg_graph* g);
-int pg_ahdsr_params_check(const pg_ahdsr_params* p);   // the reference's parameter errors (PG_OK / PG_ERR_PARAMETER): no graph, no device
+static inline int graph_fail(pg_graph* g, int code) { g->failed = true; return code; }
 void graph_begin_write(pg_graph* g, uint64_t pos);
-void drain_control_messages_public(pg_graph* g);
+void drain_control_messages(pg_graph* g);
+static inline VoiceKind voice_kind(pg_graph* g, int voice_id) {   // any thread
+  return voice_id >= 0 && (size_t)voice_id < g->voice_alive_tab.size() ? (VoiceKind)g->voice_alive_tab.get((size_t)voice_id) : VOICE_DEAD;
+}
+// One timed message for a voice into the control ring. `need`: VOICE_GRANULAR / VOICE_GRANULAR_MOD for the calls only such a voice takes.
+int voice_message(pg_graph* g, int voice_id, VoiceKind need, int type, uint64_t sample_time, float value = 0.0f, int param = 0, double dvalue = 0.0, float value2 = 0.0f);
+// The fields every new voice starts with: fader neutral, exponential smoothers at `volume` / `panning`, active, start time and persistence of `opt`
+void voice_init_neutral(const pg_graph* g, PgVoice& v, const pg_voice_options* opt, float volume, float panning);
+// MixerMessage::AddSource for a voice whose record is d_voices[dev_index]: fills in what every HostVoice holds and returns the new id (< 0: -PG_ERR_*)
+int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind);
+// Debug read-backs: waits for the graph's stream and the last write's, then copies `bytes` from device memory (PG_OK / PG_ERR_DEVICE)
+int graph_read_back(pg_graph* g, void* dst, const void* d_src, size_t bytes);
 bool graph_is_empty(const pg_graph* g);
 uint64_t graph_next_main_event(const pg_graph* g);
 int graph_enqueue_status(pg_graph* g, hipStream_t stream);
@@ -431,3 +460,10 @@ int graph_meter_reserve(pg_graph* g);    // mutating calls, graph quiescent: may
 void graph_meter_release(pg_graph* g);
 int graph_meter_launch(pg_graph* g, hipStream_t stream);   // g->meter_jobs / g->meter_spans -> one pg_meter_kernel launch
 int graph_meter_main(pg_graph* g, const float* d_ptr, uint64_t frames, uint64_t time, bool end_of_record, hipStream_t stream);
+// sampler voices (pg_sampler.hip)
+int pg_ahdsr_params_check(const pg_ahdsr_params* p);   // the reference's parameter errors (PG_OK / PG_ERR_PARAMETER): no graph, no device
+int graph_env_reserve(pg_graph* g, size_t n);          // mutating calls, graph quiescent: may allocate
+void graph_sampler_release(pg_graph* g);
+void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel
+int graph_gran_upload_live(pg_graph* g, hipStream_t stream);
+int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream);

@@ -1,0 +1,455 @@
+// Host side of the sampler voices: per-voice AHDSR envelopes (src/utils/ahdsr.rs, src/generator/sampler/voice.rs:181-212), granular voices
+// (src/generator/sampler/granular.rs; rendered by pg_grain_kernel, pg_k_grain.hip), their modulation matrix (src/modulation/matrix.rs,
+// src/generator/sampler/modulation.rs) and the granular parameters that change while a voice plays (src/generator/sampler.rs:299-360).
+// The graph, the control ring's drain and the write path are pg_host.hip's; what crosses between the two files stands in pg_host_internal.h.
+#include "pg_host_internal.h"
+#include "pg_grain_dev.h"   // mod_lfo_reset: the note_on of a voice's modulation matrix runs on the host
+
+// ---- `ended` words: one per envelope / granular record, set by the kernel that finds the record's voice ended ----
+int MappedWords::reserve(size_t n, const MappedWords& from) {
+  if (pg_host_malloc((void**)&h, n * sizeof(int32_t), hipHostMallocMapped) != hipSuccess) { h = nullptr; return PG_ERR_DEVICE; }
+  memset(h, 0, n * sizeof(int32_t));
+  if (hipHostGetDevicePointer((void**)&d, h, 0) != hipSuccess) { release(); return PG_ERR_DEVICE; }
+  if (from.cap) memcpy(h, from.h, from.cap * sizeof(int32_t));
+  cap = n;
+  return PG_OK;
+}
+void MappedWords::release() {
+  if (h) (void)pg_host_free(h);
+  h = nullptr; d = nullptr; cap = 0;
+}
+// Voices of `ids` whose word is set (or that left the graph): `live` goes off, the id leaves the list and the voice's unit goes back to the
+// time-parallel kernels with the next topology upload. Reads mapped host words: no wait. Returns whether any left.
+static bool poll_ended(pg_graph* g, std::vector<int>& ids, const MappedWords& words, int HostVoice::*word, bool HostVoice::*live) {
+  bool any = false;
+  for (size_t i = 0; i < ids.size();) {
+    HostVoice& hv = g->voices[ids[i]];
+    if (hv.mixer < 0 || words[(size_t)(hv.*word)] != 0) {
+      hv.*live = false;
+      ids.erase(ids.begin() + i);
+      g->topo_dirty = true;
+      any = true;
+    } else ++i;
+  }
+  return any;
+}
+// Enveloped voices the exact kernel has reported as ended, granular voices pg_grain_kernel has (they leave its launch list too)
+void graph_sampler_poll(pg_graph* g) {
+  if (!g->env_voices.empty()) poll_ended(g, g->env_voices, g->env_done, &HostVoice::dev_index, &HostVoice::env_live);
+  if (!g->gran_voices.empty() && poll_ended(g, g->gran_voices, g->gran_ended, &HostVoice::gran, &HostVoice::gran_live)) g->gran_live_dirty = true;
+}
+
+// The header of envelope table `tab` — its words, its grain_of_voice list, the granular records as the graph holds them now (the graph is quiescent)
+static hipError_t env_head_upload(const pg_graph* g, PgEnvTable* tab, const MappedWords& done, const int32_t* grain_of_voice) {
+  PgEnvTable head;
+  memset(&head, 0, sizeof head);
+  head.done = done.d; head.cap = done.cap;
+  head.grain_of_voice = grain_of_voice; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
+  return pg_memcpy(tab, &head, sizeof head, hipMemcpyHostToDevice);
+}
+// The envelope side table and its `ended` words for `n` voices (grow-by-doubling; the graph is quiescent: nothing in flight reads the old ones).
+int graph_env_reserve(pg_graph* g, size_t n) {
+  if (n <= g->env_done.cap) return PG_OK;
+  const size_t cap = std::max<size_t>(next_pow2(n), 64), bytes = sizeof(PgEnvTable) + cap * sizeof(PgEnv);
+  PgEnvTable* nt = nullptr;
+  int32_t* ngv = nullptr;   // PgEnvTable::grain_of_voice: -1 for every voice that is not granular
+  MappedWords done;
+  HIP_TRY(pg_malloc((void**)&nt, bytes));
+  PgEnv* const nd = (PgEnv*)(nt + 1);
+  auto fail = [&](const char* what) { (void)pg_free(nt); if (ngv) (void)pg_free(ngv); done.release(); return set_error(PG_ERR_DEVICE, "envelope table %s failed", what); };
+  if (pg_memset(nt, 0, bytes) != hipSuccess || done.reserve(cap, g->env_done) || pg_malloc((void**)&ngv, cap * sizeof(int32_t)) != hipSuccess ||
+      pg_memset(ngv, 0xff, cap * sizeof(int32_t)) != hipSuccess) return fail("allocation");
+  if (env_head_upload(g, nt, done, ngv) != hipSuccess) return fail("upload");
+  if (g->d_env && (pg_memcpy(nd, g->d_env, g->env_done.cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess ||
+                   pg_memcpy(ngv, g->d_grain_of_voice, g->env_done.cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess)) return fail("copy");
+  // (the new table is complete: let go of the old one and swap — a failure above leaves the graph on its old table)
+  if (g->d_env_tab) (void)pg_free(g->d_env_tab);
+  if (g->d_grain_of_voice) (void)pg_free(g->d_grain_of_voice);
+  g->env_done.release();
+  g->d_env_tab = nt; g->d_env = nd; g->env_done = done; g->d_grain_of_voice = ngv;
+  return PG_OK;
+}
+// Room for `n` granular records, their `ended` words and their launch list; the window tables with the first one. The graph is quiescent.
+// A failure leaves the graph on its old records.
+static int graph_gran_reserve(pg_graph* g, size_t n) {
+  if (!g->d_grain_lut) {
+    std::vector<float> lut((size_t)PG_GRAIN_WINDOWS * PG_GRAIN_LUT_N);
+    pg_grain_build_lut(lut.data());
+    HIP_TRY(pg_malloc((void**)&g->d_grain_lut, lut.size() * sizeof(float)));
+    HIP_TRY(pg_memcpy(g->d_grain_lut, lut.data(), lut.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  const size_t cap = std::max<size_t>(next_pow2(n), 16);
+  int rc;
+  if ((rc = g->d_gran_live.reserve(cap))) return rc;
+  g->gran_live.reserve(g->d_gran_live.cap);   // (graph_gran_upload_live runs inside write: it must not allocate)
+  if (n <= g->gran_ended.cap) return PG_OK;
+  PgGrainVoice* nd = nullptr;
+  MappedWords ended;
+  HIP_TRY(pg_malloc((void**)&nd, cap * sizeof(PgGrainVoice)));
+  if (ended.reserve(cap, g->gran_ended) || (g->gran_n && pg_memcpy(nd, g->d_gran, g->gran_n * sizeof(PgGrainVoice), hipMemcpyDeviceToDevice) != hipSuccess))
+    { (void)pg_free(nd); ended.release(); return set_error(PG_ERR_DEVICE, "granular table allocation failed"); }
+  if (g->d_gran) (void)pg_free(g->d_gran);
+  g->gran_ended.release();
+  g->d_gran = nd; g->gran_ended = ended;
+  return PG_OK;
+}
+// The records pg_grain_kernel renders from here on -> its launch list (inside write: capacity was reserved with the voices, nothing allocates)
+int graph_gran_upload_live(pg_graph* g, hipStream_t stream) {
+  g->gran_live.clear();
+  for (int id : g->gran_voices) g->gran_live.push_back(g->voices[id].gran);
+  g->gran_live_dirty = false;   // (a failure is the graph's: it renders nothing from then on)
+  return g->d_gran_live.upload_async(g->gran_live, stream);
+}
+// pg_grain_kernel for frames [t0, t0 + n) of the chunk that began at chunk_t0, in front of the unit kernels that take its frames.
+int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
+  if (g->gran_voices.empty()) return PG_OK;
+  PgGrainLaunch L;
+  memset(&L, 0, sizeof L);
+  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gran_voices.size(); L.live = g->d_gran_live.d;
+  L.voices = g->d_voices.d; L.cmds = d_cmds; L.n_cmds = n_cmds; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->gran_ended.d;
+  L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
+  HIP_TRY(pg_launch_grain(L, stream));
+  return PG_OK;
+}
+void graph_sampler_release(pg_graph* g) {
+  if (g->d_env_tab) (void)pg_free(g->d_env_tab);
+  if (g->d_grain_of_voice) (void)pg_free(g->d_grain_of_voice);
+  if (g->d_gran) (void)pg_free(g->d_gran);
+  if (g->d_grain_lut) (void)pg_free(g->d_grain_lut);
+  g->env_done.release(); g->gran_ended.release(); g->d_gran_live.release();
+}
+
+// note_on belongs to a voice's start (voice.rs:181-184): neither an envelope nor a matrix for a voice that has rendered frames already.
+// A voice renders in every write that ends behind its start time — a start time at or before a write's position starts it at once,
+// voice_process — so it has rendered iff a write issued since it was added ended behind its start time, wherever the earlier ones stood.
+static bool voice_has_rendered(const pg_graph* g, const HostVoice& hv) {
+  for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) return w.second > hv.start_time;
+  return false;
+}
+// The Xoshiro256++ state an `rng_state` input stands for (pg_granular_params, pg_mod_lfo): all-zero = SplitMix64 of the fixed seed, four times
+static void rng_state_from(const uint64_t in[4], uint64_t out[4]) {
+  if ((in[0] | in[1] | in[2] | in[3]) != 0) { memcpy(out, in, 4 * sizeof(uint64_t)); return; }
+  uint64_t z = 0x5EED0000ull;
+  for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; out[i] = x ^ (x >> 31); }
+}
+// pg_granular_params <-> the device's PgGrainParams (rng_state is the pool's, not a parameter: it reads 0 on the way back)
+static void grain_params_to_device(const pg_granular_params& p, PgGrainParams& q) {
+  q.overlap_mode = p.overlap_mode; q.window = p.window; q.size = p.size; q.density = p.density; q.variation = p.variation; q.spray = p.spray;
+  q.pan_spread = p.pan_spread; q.direction = p.playback_direction; q.position = p.position; q.step = p.step;
+  q.has_loop = p.has_loop_range ? 1 : 0; q.loop_start = p.has_loop_range ? p.loop_start : 0.0f; q.loop_end = p.has_loop_range ? p.loop_end : 0.0f;
+}
+static void grain_params_from_device(const PgGrainParams& q, pg_granular_params& p) {
+  memset(&p, 0, sizeof p);
+  p.overlap_mode = q.overlap_mode; p.window = q.window; p.size = q.size; p.density = q.density; p.variation = q.variation; p.spray = q.spray;
+  p.pan_spread = q.pan_spread; p.playback_direction = q.direction; p.position = q.position; p.step = q.step;
+  p.has_loop_range = q.has_loop; p.loop_start = q.loop_start; p.loop_end = q.loop_end;
+}
+// The reference's parameter errors (ahdsr.rs:143-152, :179-188, :224-233, :259-268) + what no Duration can hold; touches no graph and no device.
+int pg_ahdsr_params_check(const pg_ahdsr_params* p) {
+  if (!p) return set_error(PG_ERR_PARAMETER, "envelope parameters must not be null");
+  const float times[4] = {p->attack_s, p->hold_s, p->decay_s, p->release_s};
+  static const char* const names[4] = {"attack", "hold", "decay", "release"};
+  for (int i = 0; i < 4; ++i) if (!std::isfinite(times[i]) || times[i] < 0.0f) return set_error(PG_ERR_PARAMETER, "Invalid %s time: %g. Must be finite and >= 0", names[i], (double)times[i]);
+  if (!(p->attack_scaling >= -1.0f && p->attack_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid attack scaling: %g. Must be in range [-1.0, 1.0]", (double)p->attack_scaling);
+  if (!(p->decay_scaling >= -1.0f && p->decay_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid decay scaling: %g. Must be in range [-1.0, 1.0]", (double)p->decay_scaling);
+  if (!(p->sustain_level >= 0.0f && p->sustain_level <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid sustain level: %g. Must be in range [0.0, 1.0]", (double)p->sustain_level);
+  if (!(p->release_scaling >= -1.0f && p->release_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid release scaling: %g. Must be in range [-1.0, 1.0]", (double)p->release_scaling);
+  return PG_OK;
+}
+
+extern "C" {
+
+void pg_ahdsr_params_default(pg_ahdsr_params* p) {  // AhdsrParameters::default (utils/ahdsr.rs:348-359)
+  if (!p) return;
+  p->attack_s = 0.010f; p->attack_scaling = 0.0f; p->hold_s = 1.0f; p->decay_s = 0.5f; p->decay_scaling = 0.0f; p->sustain_level = 0.75f; p->release_s = 1.0f; p->release_scaling = 0.0f;
+}
+// AhdsrParameters::new_with_scaling + set_sample_rate(sample_rate) (ahdsr.rs:75-98, :123-136), setter by setter in the reference's order: the
+// first setup runs at the placeholder rate with the sustain level still 0 when set_decay_time divides (:205-214, :307-309); the second one —
+// set_sample_rate's, skipped when the rate IS the placeholder — is what gives decay_rate its final value.
+static PgEnvParams ahdsr_build_params(const pg_ahdsr_params& a, uint32_t sample_rate) {
+  PgEnvParams p;
+  memset(&p, 0, sizeof p);
+  uint32_t sr = 66666;  // UNINITIALIZED_SAMPLE_RATE
+  auto set_attack = [&]() { p.attack_rate = a.attack_s == 0.0f ? FLT_MAX : 1.0f / (a.attack_s * (float)sr); };
+  auto set_decay = [&]() { p.decay_rate = a.decay_s == 0.0f ? FLT_MAX : (1.0f - p.sustain_level) / (a.decay_s * (float)sr); };
+  auto set_release = [&]() { p.release_rate = a.release_s == 0.0f ? FLT_MAX : 1.0f / (a.release_s * (float)sr); };
+  set_attack(); p.attack_scaling = a.attack_scaling; set_decay(); p.decay_scaling = a.decay_scaling; p.sustain_level = a.sustain_level; set_release(); p.release_scaling = a.release_scaling;
+  if (sr != sample_rate) { sr = sample_rate; set_attack(); set_decay(); p.sustain_level = a.sustain_level; set_release(); }
+  p.hold_samples = a.hold_s * (float)sr;
+  p.zero_times = (a.hold_s == 0.0f ? PG_AHDSR_HOLD_ZERO : 0) | (a.decay_s == 0.0f ? PG_AHDSR_DECAY_ZERO : 0) | (a.release_s == 0.0f ? PG_AHDSR_RELEASE_ZERO : 0);
+  return p;
+}
+int pg_graph_set_voice_envelope(pg_graph* g, int voice_id, const pg_ahdsr_params* p) {
+  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (voice_kind(g, voice_id) == VOICE_DEAD) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  drain_control_messages(g);
+  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  HostVoice& hv = g->voices[voice_id];
+  if (voice_has_rendered(g, hv)) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: an envelope is attached before the voice starts", voice_id);
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size(), (size_t)hv.dev_index + 1))) return graph_fail(g, PG_ERR_DEVICE);
+  PgEnv e;
+  memset(&e, 0, sizeof e);
+  e.on = 1;
+  e.params = ahdsr_build_params(*p, g->sample_rate);
+  // AhdsrEnvelope::note_on(parameters, 1.0) (ahdsr.rs:402-419)
+  e.state.target_volume = 1.0f;
+  if (e.params.attack_rate == FLT_MAX) {
+    e.state.output = 1.0f;
+    if (!(e.params.zero_times & PG_AHDSR_HOLD_ZERO)) { e.state.stage = PG_AHDSR_HOLD; e.state.hold_samples_remaining = e.params.hold_samples; }
+    else e.state.stage = PG_AHDSR_DECAY;
+  } else { e.state.output = 0.0f; e.state.stage = PG_AHDSR_ATTACK; }
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_memcpy(g->d_env + hv.dev_index, &e, sizeof e, hipMemcpyHostToDevice));
+  g->env_done[(size_t)hv.dev_index] = 0;
+  if (hv.gran >= 0) {  // pg_grain_kernel: a release is the envelope's note_off from here on, not GrainPool::stop
+    const int32_t one = 1;
+    HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, has_env), &one, sizeof one, hipMemcpyHostToDevice));
+  }
+  if (!hv.env_live) g->env_voices.push_back(voice_id);
+  hv.env = true; hv.env_live = true;
+  g->topo_dirty = true;
+  return PG_OK;
+}
+int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id) {
+  if (!g || voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].mixer < 0 || !g->voices[voice_id].env || !g->d_env) return -1;
+  PgEnv e;
+  if (graph_read_back(g, &e, g->d_env + g->voices[voice_id].dev_index, sizeof e)) return -1;
+  return e.on ? (int)e.state.stage : -1;
+}
+
+// ---- granular voices (src/generator/sampler/granular.rs; pg_k_grain.hip) ----
+void pg_granular_params_default(pg_granular_params* p) {  // GranularParameters::default (granular.rs:268-283)
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->overlap_mode = 0; p->window = 2; p->size = 100.0f; p->density = 10.0f; p->playback_direction = 0; p->position = 0.5f;
+}
+int pg_granular_params_check(const pg_granular_params* p) {  // GranularParameters::validate (granular.rs:291-335); a NaN fails every range
+  if (!p) return set_error(PG_ERR_PARAMETER, "granular parameters must not be null");
+  if (p->overlap_mode < 0 || p->overlap_mode > 1) return set_error(PG_ERR_PARAMETER, "Invalid grain overlap mode: %d", p->overlap_mode);
+  if (p->window < 0 || p->window >= PG_GRAIN_WINDOWS) return set_error(PG_ERR_PARAMETER, "Invalid grain window mode: %d", p->window);
+  if (p->playback_direction < 0 || p->playback_direction > 2) return set_error(PG_ERR_PARAMETER, "Invalid grain playback direction: %d", p->playback_direction);
+  if (!(p->size >= 1.0f && p->size <= 1000.0f)) return set_error(PG_ERR_PARAMETER, "Grain size must be between 1 and 1000 ms");
+  if (!(p->density >= 1.0f && p->density <= 100.0f)) return set_error(PG_ERR_PARAMETER, "Grain density must be between 1.0 and 100.0 Hz");
+  if (!(p->spray >= 0.0f && p->spray <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain spray must be between 0.0 and 1.0");
+  if (!(p->variation >= 0.0f && p->variation <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain variation must be between 0.0 and 1.0");
+  if (!(p->pan_spread >= 0.0f && p->pan_spread <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Grain pan spread must be between 0.0 and 1.0");
+  if (!(p->position >= 0.0f && p->position <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Position must be between 0.0 and 1.0");
+  if (!(p->step >= -4.0f && p->step <= 4.0f)) return set_error(PG_ERR_PARAMETER, "Step must be between -4.0 and 4.0");
+  if (p->has_loop_range && !(p->loop_start >= 0.0f && p->loop_start <= 1.0f && p->loop_end >= 0.0f && p->loop_end <= 1.0f))
+    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)p->loop_start, (double)p->loop_end);
+  return PG_OK;
+}
+int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!mono_pcm || n_frames < 1) return -set_error(PG_ERR_PARAMETER, "Need a valid, non empty sample buffer");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  drain_control_messages(g);
+  pg_voice_options def;
+  if (!opt) { pg_voice_options_default(&def); opt = &def; }
+  if (!(opt->speed > 0.0)) return -set_error(PG_ERR_PARAMETER, "speed must be > 0");
+  if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  // the voice as the mixer sees it: a stereo source at the graph's rate whose frames pg_grain_kernel renders; AmplifiedSource / PannedSource /
+  // fader are neutral — the granular branch of SamplerVoice::process does not pass them (voice.rs:412-427)
+  PgVoice v;
+  voice_init_neutral(g, v, opt, 1.0f, 0.0f);
+  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
+  v.current_speed = 1.0; v.target_speed = 1.0;
+  v.sched_class = -1;
+  HostVoice hv;
+  auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.d_stage) (void)pg_free(hv.d_stage); };
+  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
+  if (pg_malloc(&hv.d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(hv.d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      pg_malloc(&hv.d_stage, stage_bytes) != hipSuccess || pg_memset(hv.d_stage, 0, stage_bytes) != hipSuccess) {
+    release();
+    return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice allocation failed"));
+  }
+  if (graph_gran_reserve(g, g->gran_n + 1)) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  int dev_index = -1;
+  int rc = g->d_voices.push(v, &dev_index);
+  if (rc) { release(); return -graph_fail(g, rc); }
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + 1, (size_t)dev_index + 1))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  // GrainPool::new + start(parameters, speed, volume, panning) (granular.rs:384-429, :474-489)
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  memset(r.get(), 0, sizeof(PgGrainVoice));
+  grain_params_to_device(*p, r->params);
+  PgGrainPool& pool = r->pool;
+  rng_state_from(p->rng_state, pool.rng);
+  pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
+  pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
+  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
+  r->pcm = (const float*)hv.d_pcm; r->n_frames = n_frames; r->staged = (float*)hv.d_stage; r->stage_pos = 0;
+  r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
+  const int32_t rec = (int32_t)g->gran_n;
+  (void)hipSetDevice(g->device);
+  if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
+      pg_memcpy(g->d_grain_of_voice + dev_index, &rec, sizeof rec, hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
+  g->gran_ended[(size_t)rec] = 0;
+  g->gran_n += 1;
+  if (env_head_upload(g, g->d_env_tab, g->env_done, g->d_grain_of_voice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
+  hv.gran = rec; hv.gran_live = true;
+  return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_GRANULAR);
+}
+int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  const HostVoice* hv = &g->voices[voice_id];
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  { const int rc = graph_read_back(g, r.get(), g->d_gran + hv->gran, sizeof(PgGrainVoice)); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  const PgGrainPool& pool = r->pool;
+  out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
+  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->overlap_mode = pool.overlap_mode; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
+  memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) {
+    const PgGrain& s = r->grains[i];
+    pg_grain_slot& o = out->slots[i];
+    o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
+    o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
+  }
+  return PG_OK;
+}
+// ---- the granular parameters and the loop range while the voice plays (Sampler::set_granular_parameter, sampler.rs:299-360, :1132-1147;
+// SamplerMessage::SetLoopRange -> GrainPool::set_loop_range, sampler.rs:1246-1270, granular.rs:516-518) ----
+// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
+int pg_graph_set_voice_granular_parameter(pg_graph* g, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  const int pi = find_granular_param(fourcc);
+  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown granular playback parameter 0x%08x", fourcc);
+  if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  float raw;
+  if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) {  // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
+    if (!voice_kind_is_granular(voice_kind(g, voice_id))) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+    return PG_OK;
+  }
+  return voice_message(g, voice_id, VOICE_GRANULAR, pgc::CT_VOICE_GRAIN_PARAM, sample_time, raw, pi);
+}
+int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time) {
+  if (has_loop_range && !(loop_start >= 0.0f && loop_start <= 1.0f && loop_end >= 0.0f && loop_end <= 1.0f))
+    return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)loop_start, (double)loop_end);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return voice_message(g, voice_id, VOICE_GRANULAR, pgc::CT_VOICE_GRAIN_LOOP, sample_time, has_loop_range ? loop_start : 0.0f, has_loop_range ? 1 : 0, 0.0, has_loop_range ? loop_end : 0.0f);
+}
+int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  const HostVoice* hv = &g->voices[voice_id];
+  PgGrainParams q;
+  { const int rc = graph_read_back(g, &q, (const char*)(g->d_gran + hv->gran) + offsetof(PgGrainVoice, params), sizeof q); if (rc) return rc; }
+  grain_params_from_device(q, *out);
+  return PG_OK;
+}
+
+// ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
+static_assert(PG_MOD_SOURCES == PG_GMOD_SOURCES && PG_MOD_TARGETS == PG_GMOD_TARGETS, "the header's and the device's matrix agree");
+static float mod_clamp_rate(float rate_hz) { return rate_hz < 0.01f ? 0.01f : (rate_hz > 20.0f ? 20.0f : rate_hz); }   // FloatParameter::clamp_value of ML1R / ML2R (sampler.rs:369-384)
+void pg_modulation_params_default(pg_modulation_params* p) {  // Sampler::modulation_config (sampler.rs:369-427), a note at full velocity
+  if (!p) return;
+  memset(p, 0, sizeof *p);
+  p->lfo[0].rate_hz = 1.0f; p->lfo[0].waveform = 0;
+  p->lfo[1].rate_hz = 2.0f; p->lfo[1].waveform = 1;
+  p->velocity = 1.0f; p->note = 60;
+}
+static int mod_check_route(int source, int target, float amount) {  // ModulationState::set_modulation (state.rs:174-201)
+  if (source < 0 || source >= PG_MOD_SOURCES) return set_error(PG_ERR_PARAMETER, "Unknown modulation source '%d'", source);
+  if (target < 0 || target >= PG_MOD_TARGETS) return set_error(PG_ERR_PARAMETER, "Unknown modulation target '%d'", target);
+  if (!(amount >= -1.0f && amount <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Modulation amount must be in range -1..-1.0 but is %g", (double)amount);
+  return PG_OK;
+}
+int pg_modulation_params_check(const pg_modulation_params* p) {
+  if (!p) return set_error(PG_ERR_PARAMETER, "modulation parameters must not be null");
+  for (int l = 0; l < 2; ++l) {
+    if (p->lfo[l].rate_hz != p->lfo[l].rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", l + 1);
+    if (p->lfo[l].waveform < 0 || p->lfo[l].waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", l + 1, p->lfo[l].waveform);
+  }
+  if (!(p->velocity >= 0.0f && p->velocity <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Velocity must be in range [0.0, 1.0]");
+  if (p->note < 0 || p->note > 127) return set_error(PG_ERR_PARAMETER, "MIDI note must be in range [0, 127]");
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { const int rc = mod_check_route(s, t, p->routes[s][t].amount); if (rc) return rc; }
+  return PG_OK;
+}
+int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_modulation_params* p) {
+  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (voice_kind(g, voice_id) == VOICE_DEAD) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  drain_control_messages(g);
+  if (g->voices[voice_id].mixer < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
+  HostVoice& hv = g->voices[voice_id];
+  if (hv.gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  // the matrix is created with the voice and note_on belongs to its start (voice.rs:341-373, :181-184)
+  if (voice_has_rendered(g, hv)) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: the modulation matrix is attached before the voice starts", voice_id);
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
+  PgGrainMod m;
+  memset(&m, 0, sizeof m);
+  m.on = 1;
+  for (int l = 0; l < 2; ++l) {
+    PgModLfo& o = m.lfo[l];
+    const pg_mod_lfo& in = p->lfo[l];
+    rng_state_from(in.rng_state, o.rng);
+    // create_matrix: Lfo::new(sample_rate, default rate, default waveform) (state.rs:96-113, lfo.rs:70-86)
+    o.phase = 0.0f;
+    o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
+    // the parameter updates in front of the note: set_rate / set_waveform (lfo.rs:102-119)
+    o.phase_inc = (float)((double)mod_clamp_rate(in.rate_hz) / (double)g->sample_rate);
+    o.waveform = in.waveform;
+  }
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {  // update_target on an empty slot (matrix.rs:75-82)
+    const pg_mod_route& r = p->routes[s][t];
+    if (fabsf(r.amount) >= 0.001f) { m.amount[s][t] = r.amount; m.bipolar[s][t] = r.bipolar ? 1 : 0; }
+  }
+  // SamplerVoiceModulationState::start(note, velocity) = ModulationMatrix::note_on (matrix.rs:394-408)
+  for (int l = 0; l < 2; ++l) mod_lfo_reset(m.lfo[l]);
+  m.velocity = p->velocity;
+  m.note_pitch = (float)p->note / 127.0f;
+  (void)hipSetDevice(g->device);
+  HIP_TRY(pg_memcpy((char*)(g->d_gran + hv.gran) + offsetof(PgGrainVoice, mod), &m, sizeof m, hipMemcpyHostToDevice));
+  hv.mod = true;
+  g->voice_alive_tab.set((size_t)voice_id, VOICE_GRANULAR_MOD);
+  return PG_OK;
+}
+// The timed calls: records in the control ring like the other voice commands; the writing thread turns them into events of the voice's mixer.
+int pg_graph_set_voice_modulation(pg_graph* g, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
+  { const int rc = mod_check_route(source, target, amount); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  const bool keep = fabsf(amount) >= 0.001f;   // update_target's threshold (matrix.rs:61): below it the route is removed, or not added
+  return voice_message(g, voice_id, VOICE_GRANULAR_MOD, pgc::CT_VOICE_MOD_ROUTE, sample_time, keep ? amount : 0.0f, source | (target << 8) | ((keep && bipolar) ? 1 << 16 : 0));
+}
+int pg_graph_clear_voice_modulation(pg_graph* g, int voice_id, int source, int target, uint64_t sample_time) {  // set_modulation(.., 0.0, false) (state.rs:223-231)
+  return pg_graph_set_voice_modulation(g, voice_id, source, target, 0.0f, 0, sample_time);
+}
+int pg_graph_set_voice_lfo_rate(pg_graph* g, int voice_id, int lfo, float rate_hz, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (rate_hz != rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", lfo + 1);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return voice_message(g, voice_id, VOICE_GRANULAR_MOD, pgc::CT_VOICE_LFO_RATE, sample_time, mod_clamp_rate(rate_hz), lfo);
+}
+int pg_graph_set_voice_lfo_waveform(pg_graph* g, int voice_id, int lfo, int waveform, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (waveform < 0 || waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", lfo + 1, waveform);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  return voice_message(g, voice_id, VOICE_GRANULAR_MOD, pgc::CT_VOICE_LFO_WAVEFORM, sample_time, 0.0f, lfo | (waveform << 8));
+}
+int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_state* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
+  const HostVoice* hv = &g->voices[voice_id];
+  if (!hv->mod) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
+  PgGrainMod m;
+  { const int rc = graph_read_back(g, &m, (const char*)(g->d_gran + hv->gran) + offsetof(PgGrainVoice, mod), sizeof m); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  for (int l = 0; l < 2; ++l) {
+    const PgModLfo& s = m.lfo[l];
+    pg_mod_lfo_state& o = out->lfo[l];
+    o.phase = s.phase; o.phase_inc = s.phase_inc; o.sample_hold = s.sample_hold; o.jitter_current = s.jitter_current; o.jitter_target = s.jitter_target; o.waveform = s.waveform;
+    memcpy(o.rng_state, s.rng, sizeof o.rng_state);
+  }
+  out->velocity = m.velocity; out->note_pitch = m.note_pitch;
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
+  for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
+  return PG_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // Random plans through the C ABI of libphonic_gpu against the stub HIP runtime (hip_stub.cpp), built with -fsanitize=address,undefined:
 // host memory safety of graph construction and mutation, event scheduling, command lists, topology rebuilds, chunk / piece walking of
-// long writes, host-fed voices, the sharded handle's routing and worker threads, the standalone effect handle. usage: host_fuzz [seeds] [steps]
+// long writes, host-fed voices, the sampler voices (envelopes, granular voices, their modulation matrix and parameters, the debug read-backs),
+// the sharded handle's routing and worker threads, the standalone effect handle. usage: host_fuzz [seeds] [steps]
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -54,6 +55,31 @@ struct Api {
   int stop_all() { return sharded ? pg_sharded_stop_all_voices((pg_sharded_graph*)h) : pg_graph_stop_all_voices((pg_graph*)h); }
   size_t write(float* out, size_t n, uint64_t pos) { return sharded ? pg_sharded_write((pg_sharded_graph*)h, out, n, pos) : pg_graph_write((pg_graph*)h, out, n, pos); }
   int playing(int v) { return sharded ? pg_sharded_is_voice_playing((pg_sharded_graph*)h, v) : pg_graph_is_voice_playing((pg_graph*)h, v); }
+  // the sampler voices: envelopes, granular voices, the modulation matrix, the granular parameters, their read-backs
+  pg_graph* G() { return (pg_graph*)h; }
+  pg_sharded_graph* S() { return (pg_sharded_graph*)h; }
+  int add_granular(int m, const float* pcm, size_t n, const pg_granular_params* p, const pg_voice_options* o) {
+    return sharded ? pg_sharded_add_granular_voice(S(), m, pcm, n, p, o) : pg_graph_add_granular_voice(G(), m, pcm, n, p, o);
+  }
+  int envelope(int v, const pg_ahdsr_params* p) { return sharded ? pg_sharded_set_voice_envelope(S(), v, p) : pg_graph_set_voice_envelope(G(), v, p); }
+  int release(int v, uint64_t t) { return sharded ? pg_sharded_release_voice(S(), v, t) : pg_graph_release_voice(G(), v, t); }
+  int matrix(int v, const pg_modulation_params* p) { return sharded ? pg_sharded_set_voice_modulation_matrix(S(), v, p) : pg_graph_set_voice_modulation_matrix(G(), v, p); }
+  int route(int v, int src, int dst, float amount, int bipolar, uint64_t t) {
+    return sharded ? pg_sharded_set_voice_modulation(S(), v, src, dst, amount, bipolar, t) : pg_graph_set_voice_modulation(G(), v, src, dst, amount, bipolar, t);
+  }
+  int clear_route(int v, int src, int dst, uint64_t t) { return sharded ? pg_sharded_clear_voice_modulation(S(), v, src, dst, t) : pg_graph_clear_voice_modulation(G(), v, src, dst, t); }
+  int lfo_rate(int v, int lfo, float hz, uint64_t t) { return sharded ? pg_sharded_set_voice_lfo_rate(S(), v, lfo, hz, t) : pg_graph_set_voice_lfo_rate(G(), v, lfo, hz, t); }
+  int lfo_waveform(int v, int lfo, int w, uint64_t t) { return sharded ? pg_sharded_set_voice_lfo_waveform(S(), v, lfo, w, t) : pg_graph_set_voice_lfo_waveform(G(), v, lfo, w, t); }
+  int grain_param(int v, uint32_t id, float x, int norm, uint64_t t) {
+    return sharded ? pg_sharded_set_voice_granular_parameter(S(), v, id, x, norm, t) : pg_graph_set_voice_granular_parameter(G(), v, id, x, norm, t);
+  }
+  int grain_loop(int v, int has, float a, float b, uint64_t t) {
+    return sharded ? pg_sharded_set_voice_grain_loop_range(S(), v, has, a, b, t) : pg_graph_set_voice_grain_loop_range(G(), v, has, a, b, t);
+  }
+  int envelope_stage(int v) { return sharded ? pg_sharded_voice_envelope_stage(S(), v) : pg_graph_voice_envelope_stage(G(), v); }
+  int grain_state(int v, pg_grain_state* o) { return sharded ? pg_sharded_voice_grain_state(S(), v, o) : pg_graph_voice_grain_state(G(), v, o); }
+  int granular_params(int v, pg_granular_params* o) { return sharded ? pg_sharded_voice_granular_params(S(), v, o) : pg_graph_voice_granular_params(G(), v, o); }
+  int modulation_state(int v, pg_modulation_state* o) { return sharded ? pg_sharded_voice_modulation_state(S(), v, o) : pg_graph_voice_modulation_state(G(), v, o); }
   void destroy() { if (sharded) pg_sharded_destroy((pg_sharded_graph*)h); else pg_graph_destroy((pg_graph*)h); }
 };
 
@@ -75,12 +101,14 @@ static void run_plan(uint64_t seed, int steps, bool sharded) {
   }
   if (!a.h) { fprintf(stderr, "create failed: %s\n", pg_last_error_message()); exit(2); }
   const size_t cap_frames = sharded ? mf * 8 : 9000;   // (a sharded write holds at most max_blocks x max_frames frames: larger calls are refused)
-  std::vector<int> mixers(1, 0), fx, voices, streams;
+  std::vector<int> mixers(1, 0), fx, voices, streams;   // (`voices` keeps the ids of removed voices: calls on them must fail cleanly)
+  int n_granular = 0;
+  pg_grain_state grain_state;   // (24 KB: not on the stack of a sanitized build's deep call chains)
   std::vector<float> pcm(4096), out(2 * 9000);
   for (size_t i = 0; i < pcm.size(); ++i) pcm[i] = 0.25f * (float)((int)(i % 97) - 48) / 48.0f;
   uint64_t pos = 0;
   for (int s = 0; s < steps; ++s) {
-    const int act = r.below(22);
+    const int act = r.below(32);
     const uint64_t t = pos + (uint64_t)r.below(12000) - (r.below(4) == 0 ? (uint64_t)r.below((int)(pos < 3000 ? pos + 1 : 3000)) : 0);
     switch (act) {
       case 0: case 1: if (mixers.size() < 12) { int m = a.add_mixer(r.below(3) ? 0 : mixers[r.below((int)mixers.size())]); if (m > 0) mixers.push_back(m); } break;
@@ -116,6 +144,69 @@ static void run_plan(uint64_t seed, int steps, bool sharded) {
       case 15: if (!voices.empty()) { int v = voices[r.below((int)voices.size())]; if (r.below(2)) a.speed(v, 0.3 + 3.0 * r.unit(), r.below(2) ? 12.0f : 0.0f, t); else a.seek(v, 0.01 * r.unit(), t); } break;
       case 16: if (!voices.empty()) { int v = voices[r.below((int)voices.size())]; if (r.below(3)) a.stop(v, t); else a.remove_voice(v); (void)a.playing(v); } break;
       case 17: if (r.below(6) == 0) a.stop_all(); break;
+      case 18: if (n_granular < 8) {
+        pg_granular_params p;
+        pg_granular_params_default(&p);
+        p.overlap_mode = r.below(2); p.window = r.below(4); p.playback_direction = r.below(3);
+        p.size = 1.0f + 400.0f * r.unit(); p.density = 1.0f + 99.0f * r.unit(); p.variation = r.unit(); p.spray = r.unit(); p.pan_spread = r.unit();
+        p.position = r.unit(); p.step = 8.0f * r.unit() - 4.0f;
+        if (r.below(3) == 0) { p.has_loop_range = 1; p.loop_start = r.unit(); p.loop_end = r.unit(); }
+        if (r.below(2)) for (int i = 0; i < 4; ++i) p.rng_state[i] = r.next() | 1;
+        pg_voice_options o;
+        pg_voice_options_default(&o);
+        o.volume = r.unit(); o.panning = 2.0f * r.unit() - 1.0f; o.start_time = r.below(2) ? 0 : t;
+        if (r.below(4) == 0) o.speed = 0.25 + 3.5 * r.unit();
+        if (r.below(6) == 0) o.non_transient = 1;
+        int v = a.add_granular(mixers[r.below((int)mixers.size())], pcm.data(), (size_t)(16 + r.below(1785)), &p, &o);
+        if (v >= 0) { voices.push_back(v); ++n_granular; }
+      } break;
+      case 19: if (!voices.empty()) {  // any voice: one that has rendered already answers PG_ERR_STATE, a removed one PG_ERR_NOT_FOUND
+        pg_ahdsr_params p;
+        pg_ahdsr_params_default(&p);
+        p.attack_s = r.below(3) ? 0.02f * r.unit() : 0.0f; p.hold_s = r.below(3) ? 0.02f * r.unit() : 0.0f; p.decay_s = r.below(3) ? 0.05f * r.unit() : 0.0f;
+        p.release_s = r.below(3) ? 0.05f * r.unit() : 0.0f; p.sustain_level = r.unit(); p.attack_scaling = 2.0f * r.unit() - 1.0f; p.release_scaling = 2.0f * r.unit() - 1.0f;
+        (void)a.envelope(voices[r.below((int)voices.size())], &p);
+      } break;
+      case 20: if (!voices.empty()) (void)a.release(voices[r.below((int)voices.size())], t); break;
+      case 21: if (!voices.empty()) {
+        pg_modulation_params p;
+        pg_modulation_params_default(&p);
+        for (int l = 0; l < 2; ++l) { p.lfo[l].rate_hz = 25.0f * r.unit(); p.lfo[l].waveform = r.below(7); if (r.below(2)) for (int i = 0; i < 4; ++i) p.lfo[l].rng_state[i] = r.next() | 1; }
+        p.velocity = r.unit(); p.note = r.below(128);
+        for (int i = 0; i < 6; ++i) { pg_mod_route& x = p.routes[r.below(PG_MOD_SOURCES)][r.below(PG_MOD_TARGETS)]; x.amount = 2.0f * r.unit() - 1.0f; x.bipolar = r.below(2); }
+        (void)a.matrix(voices[r.below((int)voices.size())], &p);
+      } break;
+      case 22: if (!voices.empty()) {
+        const int v = voices[r.below((int)voices.size())];
+        switch (r.below(4)) {
+          case 0: (void)a.route(v, r.below(PG_MOD_SOURCES), r.below(PG_MOD_TARGETS), 2.0f * r.unit() - 1.0f, r.below(2), t); break;
+          case 1: (void)a.clear_route(v, r.below(PG_MOD_SOURCES), r.below(PG_MOD_TARGETS), t); break;
+          case 2: (void)a.lfo_rate(v, r.below(2), 25.0f * r.unit(), t); break;
+          default: (void)a.lfo_waveform(v, r.below(2), r.below(7), t); break;
+        }
+      } break;
+      case 23: case 24: if (!voices.empty()) {
+        const int v = voices[r.below((int)voices.size())];
+        if (r.below(4) == 0) { (void)a.grain_loop(v, r.below(3) != 0, r.unit(), r.unit(), t); break; }
+        pg_param_desc d;
+        memset(&d, 0, sizeof d);
+        if (pg_granular_param(r.below(pg_granular_param_count()), &d) != 0) break;
+        if (r.below(2)) (void)a.grain_param(v, d.fourcc, r.unit(), 1, t);
+        else (void)a.grain_param(v, d.fourcc, d.min + (d.max - d.min) * (1.2f * r.unit() - 0.1f), 0, t);   // (raw: a little beyond the range too)
+      } break;
+      case 25: if (!voices.empty()) {  // the debug read-backs, on ids of every voice kind
+        const int v = voices[r.below((int)voices.size())];
+        pg_granular_params gp;
+        pg_modulation_state ms;
+        (void)a.envelope_stage(v); (void)a.grain_state(v, &grain_state); (void)a.granular_params(v, &gp); (void)a.modulation_state(v, &ms);
+      } break;
+      case 26: {  // add_voice calls that fail behind the argument checks: nothing of theirs may stay allocated
+        pg_voice_options o;
+        pg_voice_options_default(&o);
+        if (r.below(2)) { o.has_loop_range = 1; o.loop_start = 5; o.loop_end = 5; }   // loop_start >= loop_end
+        else o.speed = 64.0;                                                          // 192 kHz at 64x: a resampling ratio above 64
+        if (a.add_voice(mixers[r.below((int)mixers.size())], pcm.data(), 100, 1, 192000, &o) >= 0) { fprintf(stderr, "an invalid add_voice was accepted\n"); exit(3); }
+      } break;
       default: {  // a write: any length, host buffer (status feedback and staging spans) — the bulk of the steps
         static const size_t LEN[] = {1, 64, 333, 700, 1024, 2048, 2500, 4096, 4097, 5000, 8192, 9000};
         size_t n = LEN[r.below(12)];

@@ -2243,3 +2243,27 @@ def test_voice_commands_do_not_end_the_steady_state_of_offline_calls():
     c = run(oracle.OracleGraph(SR, 2, N), False)
     compare(a, c)
     assert np.abs(a).max() > 1e-2
+
+
+def test_add_voice_that_fails_its_argument_checks_keeps_no_device_memory():
+    """pg_graph_add_voice checks the resampling ratio and the loop range in front of its first allocation: a call that fails there with a
+    ParameterError leaves the library's allocation and release counters (pg_debug_hip_calls) grown by the same amount, and the graph takes the
+    next voice and renders it."""
+    import gc
+
+    import phonic_amd
+    from phonic_amd.graph import Graph, hip_calls
+    g = Graph(48000, 2, 256)
+    pcm = (0.5 * np.sin(np.arange(64) * 0.3)).astype(np.float32)
+    gc.collect()   # (the counters are process-wide: graphs of earlier tests are released here, not inside the window)
+    before = hip_calls()
+    for opts in (dict(has_loop_range=1, loop_start=5, loop_end=5),     # loop_start >= loop_end
+                 dict(speed=64.0)):                                     # 192 kHz at 64x: a resampling ratio above 64
+        with pytest.raises(phonic_amd.PhonicError) as ei:
+            g.add_voice(0, pcm, 1, 192000, **opts)
+        assert ei.value.code == _capi.PG_ERR_PARAMETER, ei.value
+    after = hip_calls()
+    assert after["alloc"] - before["alloc"] == after["free"] - before["free"], (before, after)
+    assert g.add_voice(0, pcm, 1, 48000) == 0
+    assert g.write(np.zeros(512, np.float32), 0) == 512
+    assert g.device_errors() == 0

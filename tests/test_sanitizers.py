@@ -44,7 +44,7 @@ def _build_host_fuzz(tmp_path, sanitize):
     jobs = []
     kernel_tus = sorted(os.path.basename(f)[:-4] for f in __import__("glob").glob(os.path.join(csrc, "pg_k_*.hip")))   # one kernel per translation unit (host side: the stubs)
     assert len(kernel_tus) >= 7, kernel_tus
-    for tu in ["pg_host", "pg_fxstate", "pg_effect", "pg_sharded", "pg_kernels"] + kernel_tus:
+    for tu in ["pg_host", "pg_sampler", "pg_fxstate", "pg_effect", "pg_sharded", "pg_kernels"] + kernel_tus:
         o = str(tmp_path / (tu + ".o"))
         objs.append(o)
         jobs.append(subprocess.Popen([hipcc] + flags + ["-c", os.path.join(csrc, tu + ".hip"), "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
