@@ -297,10 +297,11 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
  * The voice's modulation matrix is pg_graph_set_voice_modulation_matrix below; without one every `*_mod` input of try_trigger_grain /
  * advance_playhead is 0.0 — what a sampler without routings feeds.
  * The granular parameters and the loop range change while the voice plays: pg_graph_set_voice_granular_parameter / _grain_loop_range below.
- * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the mono down-mix and resample of
- * create_granular_sample_buffer (sampler.rs:908-952: the caller hands over the mono f32 buffer at the graph's rate that function would have
- * produced); the Sampler's base transpose, finetune, volume and panning parameters (pg_graph_set_voice_speed / _volume / _panning carry their
- * effect); AHDSR parameter changes on a running envelope.
+ * The mono buffer the pool reads is what create_granular_sample_buffer (sampler.rs:908-952) makes of a file: hand it over here as `mono_pcm`, or
+ * let the device make it from a sample buffer (pg_graph_add_granular_voice_from_buffer below).
+ * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the Sampler's
+ * base transpose, finetune, volume and panning parameters (pg_graph_set_voice_speed / _volume / _panning carry their effect);
+ * AHDSR parameter changes on a running envelope.
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
  * 2 Triangle, 3 Tukey, 4 Trapezoid, 5 Exponential, 6 RampUp, 7 RampDown (:61-70); size in ms, density in Hz, playback_direction 0 Forward,
  * 1 Backward, 2 Random (:19-26); plus GrainPool::sample_loop_range (:357, voice.rs:355-360) as has_loop_range / loop_start / loop_end,
@@ -389,6 +390,56 @@ int pg_granular_param(int index, pg_param_desc* out);
 int pg_graph_set_voice_granular_parameter(pg_graph* g, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
 int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time);
 int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out);
+
+/* Sample buffers: one decoded file on the device, played by any number of voices — the reference's Arc<AudioFileBuffer> (src/source/file/buffer.rs),
+ * which every PreloadedFileSource::from_shared_buffer / clone (src/source/file/preloaded.rs:71-135) and every voice of a Sampler
+ * (src/generator/sampler.rs) plays from. The buffer is uploaded once; voices made from it point at its memory and own none of it.
+ * pg_graph_add_sample_buffer: `pcm` is what pg_graph_add_voice takes (interleaved, including symphonia's extra zero frame), copied to the device
+ * once. Returns a buffer id >= 0. -PG_ERR_PARAMETER — checked before the handle and before anything touches the device — for a null `pcm`, a null
+ * desc, n_frames < 1, channels other than 1 or 2, rate 0, or a loop range with loop_start >= n_frames, loop_end > n_frames or
+ * loop_start >= loop_end (AudioFileBuffer::new refuses an empty range, file/buffer.rs:49-55).
+ * pg_graph_release_sample_buffer drops the host's reference (Arc semantics): the id returns PG_ERR_NOT_FOUND from then on, voices that play the
+ * buffer keep playing, unchanged, and the device memory — the granular mono buffer too, if one was made — is freed when the last such voice's
+ * memory is released: like a voice's private copy, in the first graph-changing call after the write that carried the voice's removal to the
+ * device (never inside a write), or with pg_graph_destroy. Voices of pg_graph_add_voice keep their private copy.
+ * pg_graph_add_voice_from_buffer = PreloadedFileSource::from_shared_buffer(buffer, options, rate): pg_graph_add_voice with the buffer's PCM,
+ * channels and rate, and every timed call works on the voice as on any file voice. The buffer's embedded loop range plays the role the reference
+ * gives it (preloaded.rs:90-104, :150-156): without a repeat count (has_repeat == 0) the voice repeats forever iff the buffer has a loop range;
+ * the active loop range is opt's override if set, else the buffer's.
+ * pg_graph_add_granular_voice_from_buffer = pg_graph_add_granular_voice with the buffer's granular mono buffer: what
+ * Sampler::create_granular_sample_buffer (sampler.rs:908-952) makes of the file — a temporary PreloadedFileSource at the graph's rate (default
+ * options, repeat(0), cubic resampler) pulled in writes of 1024 frames until one returns 0, each frame the f32 sum of its channels divided by
+ * their count; a single 0.0 if nothing came. It is made on the device (pg_sample_sched_kernel + pg_sample_interp_kernel, DESIGN.md "Sample
+ * buffers") on first use, or earlier by pg_graph_prepare_granular_buffer (a no-op once it exists), once per buffer, shared by all its granular
+ * voices as Sampler::new shares its Arc<Box<[f32]>>; a mono buffer at the graph's rate IS its granular buffer (sampler.rs:912-914: no copy
+ * here). Every sample equals the reference's; an all-zero frame's sum may differ in the sign of its zero (the identity of the Rust release's
+ * f32 Sum). If p->has_loop_range == 0 and the buffer carries a loop range, the pool's sample_loop_range is (start as f32 / n_frames as f32,
+ * end as f32 / n_frames as f32) (voice.rs:355-360). Conversion with ResamplingQuality::HighQuality (rubato) is out of scope.
+ * pg_graph_sample_buffer_info: use_count = voices holding the buffer; granular_frames = -1 while the granular buffer has not been made.
+ * pg_graph_read_granular_buffer: debug read-back of up to cap_frames frames; returns the granular buffer's length (negative: -PG_ERR_*); makes the
+ * buffer if it is not there. All calls: owner thread; the graph-changing ones wait for the work of earlier writes. */
+typedef struct pg_sample_buffer_desc {
+  uint32_t channels;        /* 1 or 2 */
+  uint32_t rate;            /* > 0 */
+  uint32_t has_loop_range;  /* AudioFileBuffer::loop_range(), the file's embedded loop */
+  uint32_t reserved;
+  uint64_t loop_start, loop_end;   /* source frames */
+} pg_sample_buffer_desc;
+typedef struct pg_sample_buffer_info {
+  uint64_t n_frames;
+  uint32_t channels, rate;
+  uint32_t has_loop_range;
+  int32_t use_count;
+  uint64_t loop_start, loop_end;
+  int64_t granular_frames;
+} pg_sample_buffer_info;
+int pg_graph_add_sample_buffer(pg_graph* g, const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc);
+int pg_graph_release_sample_buffer(pg_graph* g, int buffer_id);
+int pg_graph_add_voice_from_buffer(pg_graph* g, int mixer_id, int buffer_id, const pg_voice_options* opt);
+int pg_graph_add_granular_voice_from_buffer(pg_graph* g, int mixer_id, int buffer_id, const pg_granular_params* p, const pg_voice_options* opt);
+int pg_graph_prepare_granular_buffer(pg_graph* g, int buffer_id);
+int pg_graph_sample_buffer_info(pg_graph* g, int buffer_id, pg_sample_buffer_info* out);
+int64_t pg_graph_read_granular_buffer(pg_graph* g, int buffer_id, float* out, size_t cap_frames);
 
 /* The modulation matrix of a granular voice: the ModulationMatrix every granular sampler voice owns (src/generator/sampler/voice.rs:341-373,
  * src/modulation/matrix.rs, src/generator/sampler/modulation.rs), run in front of the grain engine (voice.rs:412-427) — on the device as phase 0
@@ -513,6 +564,10 @@ int pg_graph_set_max_blocks_per_launch(pg_graph* g, int n_blocks);
  * assert_no_alloc (src/output/cpal.rs:712-715); with these counters a test asserts the same of pg_graph_write*: on a built graph it
  * allocates nothing and frees nothing, and on a caller's stream it never blocks the host. */
 void pg_debug_hip_calls(uint64_t out[4]);
+/* Measurement hook (tools/sample_buffer_cost.py): hipEvent times in ms of a sample buffer's upload, of pass A (the schedule) and of pass B
+ * (interpolation and down-mix) of its conversion; 0 where none ran. The events exist only in a process with PHONIC_DEBUG_HOOKS=1 in its
+ * environment: without it pg_graph_add_sample_buffer and the conversion create and record none, and this reads zeros. */
+int pg_debug_sample_buffer_times(pg_graph* g, int buffer_id, float out_ms[3]);
 /* Test hook: the nth launch round from now (process-wide, any graph) fails the way a HIP launch failure does — the graph it hits becomes
  * silent for good: write returns 0, like the reference's GuardedSource after a panic (src/source/guarded.rs:87-107). 0 disarms. Armed only in
  * a process with PHONIC_DEBUG_HOOKS=1 in its environment; a no-op otherwise. */
@@ -621,6 +676,19 @@ int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_sta
 int pg_sharded_set_voice_granular_parameter(pg_sharded_graph* s, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
 int pg_sharded_set_voice_grain_loop_range(pg_sharded_graph* s, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time);
 int pg_sharded_voice_granular_params(pg_sharded_graph* s, int voice_id, pg_granular_params* out);
+/* pg_graph_add_sample_buffer / _release_sample_buffer / _add_voice_from_buffer / _add_granular_voice_from_buffer / _prepare_granular_buffer /
+ * _sample_buffer_info / _read_granular_buffer on the sharded mixer. The handle keeps a host copy of the PCM until release; a buffer reaches a
+ * shard (one upload) the first time a voice that uses it is placed there, and each shard makes its own granular buffer — the same one, the
+ * conversion is deterministic. prepare converts on the shards the buffer has reached (on the root if it has reached none); info sums use_count
+ * over the shards; read_granular_buffer reads from shard `shard` (-1: the first that holds the
+ * buffer, the root if none does), uploading and converting there if need be. */
+int pg_sharded_add_sample_buffer(pg_sharded_graph* s, const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc);
+int pg_sharded_release_sample_buffer(pg_sharded_graph* s, int buffer_id);
+int pg_sharded_add_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_voice_options* opt);
+int pg_sharded_add_granular_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_granular_params* p, const pg_voice_options* opt);
+int pg_sharded_prepare_granular_buffer(pg_sharded_graph* s, int buffer_id);
+int pg_sharded_sample_buffer_info(pg_sharded_graph* s, int buffer_id, pg_sample_buffer_info* out);
+int64_t pg_sharded_read_granular_buffer(pg_sharded_graph* s, int buffer_id, int shard, float* out, size_t cap_frames);
 /* pg_graph_set_voice_modulation_matrix / _set_voice_modulation / _clear_voice_modulation / _set_voice_lfo_rate / _set_voice_lfo_waveform /
  * _voice_modulation_state (src/modulation/matrix.rs, src/generator/sampler/modulation.rs) on the voice's shard */
 int pg_sharded_set_voice_modulation_matrix(pg_sharded_graph* s, int voice_id, const pg_modulation_params* p);

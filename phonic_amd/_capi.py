@@ -270,6 +270,30 @@ def modulation_state_dict(st):
     return d
 
 
+class SampleBufferDesc(C.Structure):
+    """pg_sample_buffer_desc: AudioFileBuffer (reference src/source/file/buffer.rs) — channels, rate, the file's embedded loop range in source frames."""
+    _fields_ = [("channels", C.c_uint32), ("rate", C.c_uint32), ("has_loop_range", C.c_uint32), ("reserved", C.c_uint32), ("loop_start", C.c_uint64), ("loop_end", C.c_uint64)]
+
+
+class SampleBufferInfo(C.Structure):
+    """pg_sample_buffer_info"""
+    _fields_ = [("n_frames", C.c_uint64), ("channels", C.c_uint32), ("rate", C.c_uint32), ("has_loop_range", C.c_uint32), ("use_count", C.c_int32),
+                ("loop_start", C.c_uint64), ("loop_end", C.c_uint64), ("granular_frames", C.c_int64)]
+
+
+def sample_buffer_desc(channels, rate, loop_range=None):
+    """loop_range = (start, end) in source frames: the file's embedded loop, or None."""
+    d = SampleBufferDesc(channels=channels, rate=rate)
+    if loop_range is not None:
+        d.has_loop_range, d.loop_start, d.loop_end = 1, int(loop_range[0]), int(loop_range[1])
+    return d
+
+
+def sample_buffer_info_dict(info):
+    return dict(n_frames=info.n_frames, channels=info.channels, rate=info.rate, loop_range=(info.loop_start, info.loop_end) if info.has_loop_range else None,
+                use_count=info.use_count, granular_frames=info.granular_frames)
+
+
 def mono_downmix(pcm, channels):
     """The down-mix of Sampler::create_granular_sample_buffer (sampler.rs:940-943) for a buffer that is already at the graph's rate: per frame, the f32
     sum of the channels in order, divided by the channel count."""
@@ -503,6 +527,19 @@ def load():
         fn = getattr(lib, prefix + "voice_grain_state")
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int, P(GrainState)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        for name, res, args in (("add_sample_buffer", C.c_int, [P(C.c_float), C.c_size_t, P(SampleBufferDesc)]),
+                                ("release_sample_buffer", C.c_int, [C.c_int]),
+                                ("add_voice_from_buffer", C.c_int, [C.c_int, C.c_int, P(VoiceOptions)]),
+                                ("add_granular_voice_from_buffer", C.c_int, [C.c_int, C.c_int, P(GranularParams), P(VoiceOptions)]),
+                                ("prepare_granular_buffer", C.c_int, [C.c_int]),
+                                ("sample_buffer_info", C.c_int, [C.c_int, P(SampleBufferInfo)]),
+                                ("read_granular_buffer", C.c_int64, [C.c_int] + ([C.c_int] if prefix == "pg_sharded_" else []) + [P(C.c_float), C.c_size_t])):
+            fn = getattr(lib, prefix + name)
+            fn.restype = res
+            fn.argtypes = [vp] + args
+    lib.pg_debug_sample_buffer_times.restype = C.c_int
+    lib.pg_debug_sample_buffer_times.argtypes = [vp, C.c_int, P(C.c_float)]
     lib.pg_granular_param_count.restype = C.c_int
     lib.pg_granular_param_count.argtypes = []
     lib.pg_granular_param.restype = C.c_int

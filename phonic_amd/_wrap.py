@@ -149,6 +149,46 @@ class GraphHandle:
         o = _capi.default_voice_options(**opts)
         return self._id(self._fn("graph_add_granular_voice")(self._h, mixer_id, _f32p(mono), mono.size, C.byref(p), C.byref(o)))
 
+    # ---- sample buffers: one decoded file on the device (Arc<AudioFileBuffer>), played by any number of file and granular voices ----
+    def add_sample_buffer(self, pcm, channels, rate, loop_range=None):
+        """Uploads `pcm` (interleaved, with the decoder's extra zero frame) once and returns a buffer id. loop_range = the file's embedded loop
+        (start, end) in source frames, or None."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        assert pcm.size % channels == 0
+        d = _capi.sample_buffer_desc(channels, rate, loop_range)
+        return self._id(self._fn("graph_add_sample_buffer")(self._h, _f32p(pcm), pcm.size // channels, C.byref(d)))
+
+    def release_sample_buffer(self, buffer_id):
+        """Drops the host's reference: the id is gone, voices that play the buffer keep playing, the last of them frees the memory."""
+        self._check(self._fn("graph_release_sample_buffer")(self._h, buffer_id))
+
+    def add_voice_from_buffer(self, mixer_id, buffer_id, **opts):
+        """PreloadedFileSource::from_shared_buffer: add_voice on the buffer's PCM, without a copy; the buffer's loop range is the file's embedded one."""
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._fn("graph_add_voice_from_buffer")(self._h, mixer_id, buffer_id, C.byref(o)))
+
+    def add_granular_voice_from_buffer(self, mixer_id, buffer_id, params=None, **opts):
+        """add_granular_voice on the buffer's granular mono buffer (Sampler::create_granular_sample_buffer, made on the device, once per buffer)."""
+        p = params if params is not None else _capi.granular_params()
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._fn("graph_add_granular_voice_from_buffer")(self._h, mixer_id, buffer_id, C.byref(p), C.byref(o)))
+
+    def prepare_granular_buffer(self, buffer_id):
+        """Makes the buffer's granular mono buffer now (load time) instead of with its first granular voice."""
+        self._check(self._fn("graph_prepare_granular_buffer")(self._h, buffer_id))
+
+    def sample_buffer_info(self, buffer_id):
+        info = _capi.SampleBufferInfo()
+        self._check(self._fn("graph_sample_buffer_info")(self._h, buffer_id, C.byref(info)))
+        return _capi.sample_buffer_info_dict(info)
+
+    def read_granular_buffer(self, buffer_id):
+        """The buffer's granular mono buffer as a float32 array (debug read-back; makes it if it is not there)."""
+        n = self._fn("graph_read_granular_buffer")(self._h, buffer_id, None, 0)
+        out = np.zeros(self._id(n), np.float32)
+        self._id(self._fn("graph_read_granular_buffer")(self._h, buffer_id, _f32p(out), out.size))
+        return out
+
     def voice_grain_state(self, voice):
         """The voice's GrainPool and its 100 grains as a dict (debug read-back: waits for the graph's stream)."""
         st = _capi.GrainState()

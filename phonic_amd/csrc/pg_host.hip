@@ -48,14 +48,19 @@ int graph_quiesce(pg_graph* g) {
   // removed source on its collector thread (src/player.rs:1178-1196), never on the audio thread: this is a graph-changing call, not a write.
   for (int id : g->retired_ready) {
     HostVoice& hv = g->voices[id];
-    if (hv.d_pcm) (void)pg_free(hv.d_pcm);
-    if (hv.d_stage) (void)pg_free(hv.d_stage);
-    if (hv.h_ring) (void)pg_host_free(hv.h_ring);
-    hv.d_pcm = nullptr; hv.d_stage = nullptr; hv.h_ring = nullptr;
+    graph_voice_release(g, hv);
     if (hv.stream) g->stream_voices.erase(std::remove(g->stream_voices.begin(), g->stream_voices.end(), id), g->stream_voices.end());
   }
   g->retired_ready.clear();
   return PG_OK;
+}
+// A voice frees only what it owns: its private PCM / ring / staging memory; the PCM of a sample buffer goes with the buffer's last reference
+void graph_voice_release(pg_graph* g, HostVoice& hv) {
+  if (hv.d_pcm) (void)pg_free(hv.d_pcm);
+  if (hv.d_stage) (void)pg_free(hv.d_stage);
+  if (hv.h_ring) (void)pg_host_free(hv.h_ring);
+  hv.d_pcm = nullptr; hv.d_stage = nullptr; hv.h_ring = nullptr;
+  if (hv.sbuf >= 0) { sample_buffer_unref(g, hv.sbuf); hv.sbuf = -1; }
 }
 
 // topology tables: unit -> voices / effects. Unit slots are stable; PgUnit state fields live on the device and are
@@ -412,7 +417,8 @@ void pg_graph_destroy(pg_graph* g) {
   (void)hipSetDevice(g->device);
   (void)pg_stream_sync(g->stream);
   if (g->last_stream && g->last_stream != g->stream) (void)pg_stream_sync(g->last_stream);
-  for (auto& v : g->voices) { if (v.d_pcm) (void)pg_free(v.d_pcm); if (v.d_stage) (void)pg_free(v.d_stage); if (v.h_ring) (void)pg_host_free(v.h_ring); }
+  for (auto& v : g->voices) graph_voice_release(g, v);
+  graph_sample_buffers_release(g);
   for (auto& f : g->fx) if (f->d_mem) (void)pg_free(f->d_mem);
   g->d_units.release(); g->d_voices.release(); g->d_fx.release(); g->d_voice_index.release(); g->d_fx_index.release(); g->d_order.release();
   g->d_sched.release(); g->d_slot_info.release(); g->d_slot_fx.release(); g->d_slot_lead.release(); g->d_child_rows.release(); g->d_topo.release();
@@ -590,13 +596,13 @@ int pg_graph_move_effect(pg_graph* g, int effect_id, int mixer_id, int movement,
   return PG_OK;
 }
 
-int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_frames, uint32_t src_channels, uint32_t src_rate,
-                       const pg_voice_options* opt) {
+}  // extern "C"
+int graph_add_file_voice(pg_graph* g, int mixer_id, const float* pcm, int sbuf, size_t n_frames, uint32_t src_channels, uint32_t src_rate, const pg_voice_options* opt) {
   if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
   // AudioFileBuffer::new validation (file/buffer.rs:22-60)
   if (src_rate == 0) return -set_error(PG_ERR_PARAMETER, "file buffer sample rate must be > 0");
   if (src_channels != 1 && src_channels != 2) return -set_error(PG_ERR_PARAMETER, "only mono and stereo file buffers are supported");
-  if (n_frames == 0 || !pcm) return -set_error(PG_ERR_PARAMETER, "file buffer must not be empty");
+  if (n_frames == 0 || (!pcm && sbuf < 0)) return -set_error(PG_ERR_PARAMETER, "file buffer must not be empty");
   drain_control_messages(g);  // control calls made before this one come first (a stop_all_voices must not take this source with it)
   pg_voice_options def;
   if (!opt) { pg_voice_options_default(&def); opt = &def; }
@@ -614,9 +620,12 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   if (res_out == 0) return -set_error(PG_ERR_PARAMETER, "Invalid resampling ratio");
   v.ratio = (float)((double)src_rate / (double)res_out);
   if (!(v.ratio > 0.0f) || v.ratio > 64.0f) return -set_error(PG_ERR_PARAMETER, "Invalid resampling ratio");
-  // repeat / loop range (preloaded.rs:89-104): no embedded loop points (decoding is out of scope)
-  v.repeat = opt->has_repeat ? opt->repeat : 0;
+  // repeat / loop range (preloaded.rs:89-104, :150-156): a private copy has no embedded loop points (decoding is out of scope); a sample
+  // buffer may carry the file's — then a voice without a repeat count repeats forever, and the range is the override if set, else the file's
+  const SampleBuffer* sb = sbuf >= 0 ? &g->sample_buffers[sbuf] : nullptr;
+  v.repeat = opt->has_repeat ? opt->repeat : (sb && sb->has_loop ? PG_USIZE_MAX : 0);
   v.repeat_count = v.repeat;
+  if (!opt->has_loop_range && sb && sb->has_loop) { v.has_loop = 1; v.loop_start = sb->loop_start; v.loop_end = sb->loop_end; }
   if (opt->has_loop_range) {
     uint64_t fc = n_frames;
     v.has_loop = 1;
@@ -634,9 +643,12 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
   HostVoice hv;
   auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.d_stage) (void)pg_free(hv.d_stage); };   // (error returns below)
-  if (pg_malloc(&hv.d_pcm, n_samples * sizeof(float)) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "pg_malloc(pcm) failed"));
-  if (pg_memcpy(hv.d_pcm, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "pcm upload failed")); }
-  v.pcm = (const float*)hv.d_pcm;
+  if (sb) v.pcm = (const float*)sb->d_pcm;   // (the buffer's memory: the voice holds a reference, taken when nothing can fail any more)
+  else {
+    if (pg_malloc(&hv.d_pcm, n_samples * sizeof(float)) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "pg_malloc(pcm) failed"));
+    if (pg_memcpy(hv.d_pcm, pcm, n_samples * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "pcm upload failed")); }
+    v.pcm = (const float*)hv.d_pcm;
+  }
   {  // resampler schedule cache class: voices sharing the f32 ratio; the first one publishes
     uint32_t rb;
     memcpy(&rb, &v.ratio, 4);
@@ -668,7 +680,13 @@ int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_fra
   int dev_index = -1;
   int rc = g->d_voices.push(v, &dev_index);
   if (rc) { release(); return -graph_fail(g, rc); }
+  if (sb) { hv.sbuf = sbuf; g->sample_buffers[sbuf].use_count += 1; }
   return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_FILE);
+}
+extern "C" {
+int pg_graph_add_voice(pg_graph* g, int mixer_id, const float* pcm, size_t n_frames, uint32_t src_channels, uint32_t src_rate,
+                       const pg_voice_options* opt) {
+  return graph_add_file_voice(g, mixer_id, pcm, -1, n_frames, src_channels, src_rate, opt);
 }
 
 // ---- host-fed sources ------------------------------------------------------------------------------------------------------------

@@ -252,6 +252,21 @@ struct HostVoice {
   int gran = -1;                   // granular voice (pg_graph_add_granular_voice): its record in pg_graph::d_gran; d_pcm = the mono buffer, d_stage = the staging buffer
   bool gran_live = false;          // ... and pg_grain_kernel has not reported the voice ended: it renders the voice, the exact kernel its unit
   bool mod = false;                // ... with a modulation matrix (pg_graph_set_voice_modulation_matrix): PgGrainVoice::mod of its record
+  int sbuf = -1;                   // the voice plays pg_graph::sample_buffers[sbuf] (pg_graph_add_*_voice_from_buffer): d_pcm stays null — the PCM is the buffer's
+};
+// A sample buffer on the device (pg_graph_add_sample_buffer): AudioFileBuffer behind an Arc (src/source/file/buffer.rs). The host holds one
+// reference until pg_graph_release_sample_buffer, every voice made from it one until its memory is released (graph_voice_release).
+struct SampleBuffer {
+  void* d_pcm = nullptr;           // interleaved PCM, n_frames * channels floats; null once the last reference is gone
+  size_t n_frames = 0;
+  uint32_t channels = 0, rate = 0;
+  bool has_loop = false;           // AudioFileBuffer::loop_range(), source frames
+  uint64_t loop_start = 0, loop_end = 0;
+  float* d_mono = nullptr;         // the granular mono buffer at the graph's rate (pg_k_sample.hip); == d_pcm for a mono buffer at that rate
+  int64_t mono_frames = -1;        // -1: not made yet
+  int use_count = 0;               // voices holding a reference
+  bool held = true;                // the host's reference
+  float upload_ms = 0.0f, sched_ms = 0.0f, interp_ms = 0.0f;   // pg_debug_sample_buffer_times: taken only while sample_buffer_timing()
 };
 struct HostMixer {
   int unit_slot = -1;              // sub-mixer unit; for the main mixer: the bus unit
@@ -429,6 +444,7 @@ struct pg_graph {
   DeviceTable<int32_t> d_gran_live;      // their records
   std::vector<int32_t> gran_live;        // ... as the next upload puts them together (capacity kept across writes)
   bool gran_live_dirty = false;
+  std::vector<SampleBuffer> sample_buffers;   // by buffer id (ids are never reused)
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };
@@ -467,3 +483,13 @@ void graph_sampler_release(pg_graph* g);
 void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel
 int graph_gran_upload_live(pg_graph* g, hipStream_t stream);
 int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream);
+// sample buffers (pg_sampler.hip; the conversion: pg_k_sample.hip)
+int sample_buffer_desc_check(const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc);   // PG_OK / PG_ERR_PARAMETER: no graph, no device
+SampleBuffer* sample_buffer_find(pg_graph* g, int buffer_id);      // the buffer while the host holds it, else null (PG_ERR_NOT_FOUND is set)
+void sample_buffer_unref(pg_graph* g, int sbuf);                   // a voice's reference goes: the last one frees the device memory
+bool sample_buffer_timing();                                       // PHONIC_DEBUG_HOOKS=1: the upload and the conversion's passes are timed with hipEvents
+int sample_buffer_convert(pg_graph* g, SampleBuffer& b);           // makes b.d_mono if it is not there yet; the graph is quiescent
+void graph_voice_release(pg_graph* g, HostVoice& hv);              // what a voice owns goes back (graph quiescent): its memory, its buffer reference
+void graph_sample_buffers_release(pg_graph* g);                    // pg_graph_destroy: whatever the host still holds
+// pg_graph_add_voice / _from_buffer: `pcm` (copied to the device, owned by the voice) or, with pcm null, sample buffer `sbuf`
+int graph_add_file_voice(pg_graph* g, int mixer_id, const float* pcm, int sbuf, size_t n_frames, uint32_t src_channels, uint32_t src_rate, const pg_voice_options* opt);

@@ -241,10 +241,13 @@ int pg_granular_params_check(const pg_granular_params* p) {  // GranularParamete
     return set_error(PG_ERR_PARAMETER, "Invalid loop points (should be relative positions), but are: (%g, %g)", (double)p->loop_start, (double)p->loop_end);
   return PG_OK;
 }
-int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
+}  // extern "C"
+// pg_graph_add_granular_voice / _from_buffer: `mono_pcm` (copied to the device, owned by the voice) or, with mono_pcm null, the granular mono
+// buffer of sample buffer `sbuf` (made already; n_frames is its length)
+static int graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, int sbuf, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
   { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
   if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (!mono_pcm || n_frames < 1) return -set_error(PG_ERR_PARAMETER, "Need a valid, non empty sample buffer");
+  if ((!mono_pcm && sbuf < 0) || n_frames < 1) return -set_error(PG_ERR_PARAMETER, "Need a valid, non empty sample buffer");
   if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
   drain_control_messages(g);
   pg_voice_options def;
@@ -262,7 +265,7 @@ int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm
   HostVoice hv;
   auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.d_stage) (void)pg_free(hv.d_stage); };
   const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
-  if (pg_malloc(&hv.d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(hv.d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+  if ((sbuf < 0 && (pg_malloc(&hv.d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(hv.d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) ||
       pg_malloc(&hv.d_stage, stage_bytes) != hipSuccess || pg_memset(hv.d_stage, 0, stage_bytes) != hipSuccess) {
     release();
     return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice allocation failed"));
@@ -282,7 +285,7 @@ int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm
   pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
   pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
   for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
-  r->pcm = (const float*)hv.d_pcm; r->n_frames = n_frames; r->staged = (float*)hv.d_stage; r->stage_pos = 0;
+  r->pcm = sbuf >= 0 ? g->sample_buffers[sbuf].d_mono : (const float*)hv.d_pcm; r->n_frames = n_frames; r->staged = (float*)hv.d_stage; r->stage_pos = 0;
   r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
   const int32_t rec = (int32_t)g->gran_n;
   (void)hipSetDevice(g->device);
@@ -292,7 +295,126 @@ int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm
   g->gran_n += 1;
   if (env_head_upload(g, g->d_env_tab, g->env_done, g->d_grain_of_voice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
   hv.gran = rec; hv.gran_live = true;
+  if (sbuf >= 0) { hv.sbuf = sbuf; g->sample_buffers[sbuf].use_count += 1; }   // (nothing fails behind this that would release the voice)
   return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_GRANULAR);
+}
+
+// ---- sample buffers (src/source/file/buffer.rs behind an Arc; the granular mono buffer: pg_k_sample.hip) ----
+int sample_buffer_desc_check(const float* pcm, size_t n_frames, const pg_sample_buffer_desc* d) {   // AudioFileBuffer::new (file/buffer.rs:22-60)
+  if (!pcm || !d) return set_error(PG_ERR_PARAMETER, "sample buffer PCM and description must not be empty");
+  if (n_frames < 1) return set_error(PG_ERR_PARAMETER, "file buffer must not be empty");
+  if (d->channels != 1 && d->channels != 2) return set_error(PG_ERR_PARAMETER, "only mono and stereo file buffers are supported");
+  if (d->rate == 0) return set_error(PG_ERR_PARAMETER, "file buffer sample rate must be > 0");
+  if (d->has_loop_range && (d->loop_start >= n_frames || d->loop_end > n_frames || d->loop_start >= d->loop_end))
+    return set_error(PG_ERR_PARAMETER, "file buffer loop range is out of bounds");
+  return PG_OK;
+}
+SampleBuffer* sample_buffer_find(pg_graph* g, int buffer_id) {
+  if (buffer_id < 0 || buffer_id >= (int)g->sample_buffers.size() || !g->sample_buffers[buffer_id].held) { set_error(PG_ERR_NOT_FOUND, "Sample buffer with id %d not found", buffer_id); return nullptr; }
+  return &g->sample_buffers[buffer_id];
+}
+bool sample_buffer_timing() {   // the measurement hook is armed like the fault injector: only with PHONIC_DEBUG_HOOKS=1 in the environment
+  static const bool armed = [] { const char* e = getenv("PHONIC_DEBUG_HOOKS"); return e && e[0] == '1'; }();
+  return armed;
+}
+static void sample_buffer_free(SampleBuffer& b) {   // nobody holds it: nothing in flight reads it (the graph is quiescent)
+  if (b.d_mono && b.d_mono != (float*)b.d_pcm) (void)pg_free(b.d_mono);
+  if (b.d_pcm) (void)pg_free(b.d_pcm);
+  b.d_pcm = nullptr; b.d_mono = nullptr;
+}
+void sample_buffer_unref(pg_graph* g, int sbuf) {
+  SampleBuffer& b = g->sample_buffers[sbuf];
+  if (--b.use_count == 0 && !b.held) sample_buffer_free(b);
+}
+void graph_sample_buffers_release(pg_graph* g) {
+  for (SampleBuffer& b : g->sample_buffers) sample_buffer_free(b);
+  g->sample_buffers.clear();
+}
+
+extern "C" {
+
+int pg_graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
+  return graph_add_granular_voice(g, mixer_id, mono_pcm, -1, n_frames, p, opt);
+}
+int pg_graph_add_sample_buffer(pg_graph* g, const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc) {
+  { const int rc = sample_buffer_desc_check(pcm, n_frames, desc); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  SampleBuffer b;
+  b.n_frames = n_frames; b.channels = desc->channels; b.rate = desc->rate;
+  b.has_loop = desc->has_loop_range != 0; b.loop_start = b.has_loop ? desc->loop_start : 0; b.loop_end = b.has_loop ? desc->loop_end : 0;
+  const size_t bytes = n_frames * desc->channels * sizeof(float);
+  hipEvent_t e0 = nullptr, e1 = nullptr;   // (measurement hook, pg_debug_sample_buffer_times: no event without PHONIC_DEBUG_HOOKS=1)
+  hipError_t err = pg_malloc(&b.d_pcm, bytes);
+  const bool timed = sample_buffer_timing() && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, g->stream) == hipSuccess;
+  if (err == hipSuccess) err = pg_memcpy(b.d_pcm, pcm, bytes, hipMemcpyHostToDevice);
+  if (err == hipSuccess && timed && hipEventRecord(e1, g->stream) == hipSuccess && hipEventSynchronize(e1) == hipSuccess) (void)hipEventElapsedTime(&b.upload_ms, e0, e1);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (err != hipSuccess) { if (b.d_pcm) (void)pg_free(b.d_pcm); return -graph_fail(g, set_error(PG_ERR_DEVICE, "sample buffer upload failed: %s", hipGetErrorString(err))); }
+  g->sample_buffers.push_back(b);
+  return (int)g->sample_buffers.size() - 1;
+}
+int pg_graph_release_sample_buffer(pg_graph* g, int buffer_id) {
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SampleBuffer* b = sample_buffer_find(g, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);   // (voices retired by earlier writes let go of their references here)
+  b->held = false;
+  if (b->use_count == 0) sample_buffer_free(*b);
+  return PG_OK;
+}
+int pg_graph_add_voice_from_buffer(pg_graph* g, int mixer_id, int buffer_id, const pg_voice_options* opt) {
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  const SampleBuffer* b = sample_buffer_find(g, buffer_id);
+  if (!b) return -PG_ERR_NOT_FOUND;
+  return graph_add_file_voice(g, mixer_id, nullptr, buffer_id, b->n_frames, b->channels, b->rate, opt);
+}
+int pg_graph_prepare_granular_buffer(pg_graph* g, int buffer_id) {
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  SampleBuffer* b = sample_buffer_find(g, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  if (b->mono_frames >= 0) return PG_OK;
+  if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
+  const int rc = sample_buffer_convert(g, *b);
+  return rc == PG_ERR_DEVICE ? graph_fail(g, rc) : rc;
+}
+int pg_graph_add_granular_voice_from_buffer(pg_graph* g, int mixer_id, int buffer_id, const pg_granular_params* p, const pg_voice_options* opt) {
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  { const int rc = pg_graph_prepare_granular_buffer(g, buffer_id); if (rc) return -rc; }
+  const SampleBuffer& b = g->sample_buffers[buffer_id];
+  pg_granular_params q = *p;
+  if (!q.has_loop_range && b.has_loop) {   // SamplerVoice::enable_granular_playback (voice.rs:355-360)
+    const float total = (float)b.n_frames;
+    q.has_loop_range = 1; q.loop_start = (float)b.loop_start / total; q.loop_end = (float)b.loop_end / total;
+  }
+  return graph_add_granular_voice(g, mixer_id, nullptr, buffer_id, (size_t)b.mono_frames, &q, opt);
+}
+int pg_graph_sample_buffer_info(pg_graph* g, int buffer_id, pg_sample_buffer_info* out) {
+  if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  const SampleBuffer* b = sample_buffer_find(g, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  memset(out, 0, sizeof *out);
+  out->n_frames = b->n_frames; out->channels = b->channels; out->rate = b->rate; out->has_loop_range = b->has_loop ? 1 : 0; out->use_count = b->use_count;
+  out->loop_start = b->loop_start; out->loop_end = b->loop_end; out->granular_frames = b->mono_frames;
+  return PG_OK;
+}
+int pg_debug_sample_buffer_times(pg_graph* g, int buffer_id, float out_ms[3]) {
+  if (!g || !out_ms) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  const SampleBuffer* b = sample_buffer_find(g, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  out_ms[0] = b->upload_ms; out_ms[1] = b->sched_ms; out_ms[2] = b->interp_ms;
+  return PG_OK;
+}
+int64_t pg_graph_read_granular_buffer(pg_graph* g, int buffer_id, float* out, size_t cap_frames) {
+  if (!g || (!out && cap_frames)) return -set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  { const int rc = pg_graph_prepare_granular_buffer(g, buffer_id); if (rc) return -rc; }
+  const SampleBuffer& b = g->sample_buffers[buffer_id];
+  const size_t n = std::min<size_t>(cap_frames, (size_t)b.mono_frames);
+  if (n) { const int rc = graph_read_back(g, out, b.d_mono, n * sizeof(float)); if (rc) return -rc; }
+  return b.mono_frames;
 }
 int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
   if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");

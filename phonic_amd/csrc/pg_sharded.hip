@@ -159,6 +159,10 @@ struct pg_sharded_graph {
   std::vector<ncclComm_t> comms;         // PG_REDUCE_RCCL: one communicator per shard (ncclCommInitAll over the shards' devices)
   // global id -> shard << 24 | local id; append-only, readable from any thread (control calls)
   pgc::ChunkTable<int32_t> mixer_map, fx_map, voice_map;
+  // sample buffers (pg_sharded_add_sample_buffer): the host copy lives until release; local[shard] = the buffer's id on that shard, -1 until a
+  // voice that uses it is placed there
+  struct SampleBuf { std::vector<float> pcm; size_t n_frames = 0; pg_sample_buffer_desc desc; std::vector<int> local; bool held = true; };
+  std::vector<SampleBuf> sample_buffers;
 };
 static inline int shard_of(int32_t packed) { return (int)((uint32_t)packed >> 24); }
 static inline int local_of(int32_t packed) { return (int)((uint32_t)packed & 0xffffffu); }
@@ -365,6 +369,99 @@ int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float
   const int id = (int)s->voice_map.size();
   if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
   return id;
+}
+// sample buffers: one host copy, one upload per shard that plays the buffer, one granular mono buffer per shard (the same one everywhere)
+static pg_sharded_graph::SampleBuf* sharded_sample_buffer(pg_sharded_graph* s, int buffer_id) {
+  if (buffer_id < 0 || (size_t)buffer_id >= s->sample_buffers.size() || !s->sample_buffers[buffer_id].held) { set_error(PG_ERR_NOT_FOUND, "Sample buffer with id %d not found", buffer_id); return nullptr; }
+  return &s->sample_buffers[buffer_id];
+}
+static int sharded_buffer_on(pg_sharded_graph* s, pg_sharded_graph::SampleBuf& b, int shard) {   // -> the buffer's id on `shard` (< 0: -PG_ERR_*)
+  if (b.local[shard] < 0) b.local[shard] = pg_graph_add_sample_buffer(s->shards[shard], b.pcm.data(), b.n_frames, &b.desc);
+  return b.local[shard];
+}
+static int sharded_register_voice(pg_sharded_graph* s, int mixer_id, int shard, int local) {
+  if (local < 0) return local;
+  if (mixer_id == 0) s->load[shard] += 1;
+  const int id = (int)s->voice_map.size();
+  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
+  return id;
+}
+int pg_sharded_add_sample_buffer(pg_sharded_graph* s, const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc) {
+  { const int rc = sample_buffer_desc_check(pcm, n_frames, desc); if (rc) return -rc; }
+  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  pg_sharded_graph::SampleBuf b;
+  b.pcm.assign(pcm, pcm + n_frames * desc->channels); b.n_frames = n_frames; b.desc = *desc; b.local.assign(s->shards.size(), -1);
+  s->sample_buffers.push_back(std::move(b));
+  return (int)s->sample_buffers.size() - 1;
+}
+int pg_sharded_release_sample_buffer(pg_sharded_graph* s, int buffer_id) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  int rc = PG_OK;
+  for (size_t i = 0; i < s->shards.size(); ++i) if (b->local[i] >= 0) { const int r = pg_graph_release_sample_buffer(s->shards[i], b->local[i]); if (r) rc = r; }
+  b->held = false;
+  std::vector<float>().swap(b->pcm);
+  return rc;
+}
+int pg_sharded_add_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_voice_options* opt) {
+  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return -PG_ERR_NOT_FOUND;
+  int32_t pk;
+  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
+  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
+  const int lb = sharded_buffer_on(s, *b, shard);
+  if (lb < 0) return lb;
+  return sharded_register_voice(s, mixer_id, shard, pg_graph_add_voice_from_buffer(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), lb, opt));
+}
+int pg_sharded_add_granular_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_granular_params* p, const pg_voice_options* opt) {
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
+  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return -PG_ERR_NOT_FOUND;
+  int32_t pk;
+  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
+  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
+  const int lb = sharded_buffer_on(s, *b, shard);
+  if (lb < 0) return lb;
+  return sharded_register_voice(s, mixer_id, shard, pg_graph_add_granular_voice_from_buffer(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), lb, p, opt));
+}
+int pg_sharded_prepare_granular_buffer(pg_sharded_graph* s, int buffer_id) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  bool any = false;
+  for (size_t i = 0; i < s->shards.size(); ++i) if (b->local[i] >= 0) { any = true; const int rc = pg_graph_prepare_granular_buffer(s->shards[i], b->local[i]); if (rc) return rc; }
+  if (any) return PG_OK;
+  const int lb = sharded_buffer_on(s, *b, 0);
+  return lb < 0 ? -lb : pg_graph_prepare_granular_buffer(s->shards[0], lb);
+}
+int pg_sharded_sample_buffer_info(pg_sharded_graph* s, int buffer_id, pg_sample_buffer_info* out) {
+  if (!s || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return PG_ERR_NOT_FOUND;
+  memset(out, 0, sizeof *out);
+  out->n_frames = b->n_frames; out->channels = b->desc.channels; out->rate = b->desc.rate; out->has_loop_range = b->desc.has_loop_range ? 1 : 0;
+  out->loop_start = b->desc.has_loop_range ? b->desc.loop_start : 0; out->loop_end = b->desc.has_loop_range ? b->desc.loop_end : 0; out->granular_frames = -1;
+  for (size_t i = 0; i < s->shards.size(); ++i) if (b->local[i] >= 0) {
+    pg_sample_buffer_info li;
+    const int rc = pg_graph_sample_buffer_info(s->shards[i], b->local[i], &li);
+    if (rc) return rc;
+    out->use_count += li.use_count;
+    if (li.granular_frames >= 0) out->granular_frames = li.granular_frames;
+  }
+  return PG_OK;
+}
+int64_t pg_sharded_read_granular_buffer(pg_sharded_graph* s, int buffer_id, int shard, float* out, size_t cap_frames) {
+  if (!s || (!out && cap_frames)) return -set_error(PG_ERR_PARAMETER, "graph handle or output is null");
+  pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
+  if (!b) return -PG_ERR_NOT_FOUND;
+  if (shard < -1 || shard >= (int)s->shards.size()) return -set_error(PG_ERR_PARAMETER, "no shard %d", shard);
+  if (shard < 0) { shard = 0; for (size_t i = 0; i < s->shards.size(); ++i) if (b->local[i] >= 0) { shard = (int)i; break; } }
+  const int lb = sharded_buffer_on(s, *b, shard);
+  if (lb < 0) return lb;
+  return pg_graph_read_granular_buffer(s->shards[shard], lb, out, cap_frames);
 }
 int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out) {
   if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");

@@ -43,6 +43,13 @@ class Graph(GraphHandle):
     def stream_voice_consumed(self, voice):
         return self._id(self._lib.pg_graph_stream_voice_consumed(self._h, voice))
 
+    def sample_buffer_times(self, buffer_id):
+        """Measurement hook (pg_debug_sample_buffer_times): hipEvent ms of the buffer's upload and of the two passes of its conversion, taken only
+        in a process with PHONIC_DEBUG_HOOKS=1 in its environment (zeros otherwise)."""
+        out = (C.c_float * 3)()
+        self._check(self._lib.pg_debug_sample_buffer_times(self._h, buffer_id, out))
+        return dict(upload_ms=out[0], sched_ms=out[1], interp_ms=out[2])
+
     def set_max_blocks_per_launch(self, n_blocks):
         """Offline rendering: let one write call render up to `n_blocks` blocks of max_frames per launch sequence (steady state only)."""
         self._check(self._lib.pg_graph_set_max_blocks_per_launch(self._h, int(n_blocks)))
@@ -179,6 +186,39 @@ class ShardedGraph:
         p = params if params is not None else _capi.granular_params()
         o = _capi.default_voice_options(**opts)
         return self._id(self._lib.pg_sharded_add_granular_voice(self._h, mixer_id, mono.ctypes.data_as(C.POINTER(C.c_float)), mono.size, C.byref(p), C.byref(o)))
+
+    # ---- sample buffers (see GraphHandle): a buffer reaches a shard with the first voice placed there; every shard makes its own granular buffer ----
+    def add_sample_buffer(self, pcm, channels, rate, loop_range=None):
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32)
+        d = _capi.sample_buffer_desc(channels, rate, loop_range)
+        return self._id(self._lib.pg_sharded_add_sample_buffer(self._h, pcm.ctypes.data_as(C.POINTER(C.c_float)), pcm.size // channels, C.byref(d)))
+
+    def release_sample_buffer(self, buffer_id):
+        self._check(self._lib.pg_sharded_release_sample_buffer(self._h, buffer_id))
+
+    def add_voice_from_buffer(self, mixer_id, buffer_id, **opts):
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._lib.pg_sharded_add_voice_from_buffer(self._h, mixer_id, buffer_id, C.byref(o)))
+
+    def add_granular_voice_from_buffer(self, mixer_id, buffer_id, params=None, **opts):
+        p = params if params is not None else _capi.granular_params()
+        o = _capi.default_voice_options(**opts)
+        return self._id(self._lib.pg_sharded_add_granular_voice_from_buffer(self._h, mixer_id, buffer_id, C.byref(p), C.byref(o)))
+
+    def prepare_granular_buffer(self, buffer_id):
+        self._check(self._lib.pg_sharded_prepare_granular_buffer(self._h, buffer_id))
+
+    def sample_buffer_info(self, buffer_id):
+        info = _capi.SampleBufferInfo()
+        self._check(self._lib.pg_sharded_sample_buffer_info(self._h, buffer_id, C.byref(info)))
+        return _capi.sample_buffer_info_dict(info)
+
+    def read_granular_buffer(self, buffer_id, shard=-1):
+        """The granular mono buffer as shard `shard` holds it (-1: the first shard that holds the buffer)."""
+        n = self._id(self._lib.pg_sharded_read_granular_buffer(self._h, buffer_id, shard, None, 0))
+        out = np.zeros(n, np.float32)
+        self._id(self._lib.pg_sharded_read_granular_buffer(self._h, buffer_id, shard, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
 
     def voice_grain_state(self, voice):
         st = _capi.GrainState()
