@@ -1558,6 +1558,22 @@ static void meter_collect_chunk(pg_graph* g, uint64_t now, uint64_t chunk_n, uin
   }
 }
 
+// The call budget of nested mixers. A sub-mixer keeps one result bit per call of its parent (PgUnit::call_audible, PG_MAX_CALLS), and every event
+// of a mixer that has sub-mixers is a call boundary of theirs: graph_call_cuts appends the sample times of those events inside (now, now + chunk_n),
+// call_budget_bound ends the chunk at the PG_MAX_CALLS-th distinct one, so that at most PG_MAX_CALLS - 1 boundaries fall inside it. The sharded
+// handle bounds its spans by the cuts of ALL its shards, as the one graph does with all its mixers.
+void graph_call_cuts(const pg_graph* g, uint64_t now, uint64_t chunk_n, std::vector<uint64_t>& cuts) {
+  for (size_t m = 1; m < g->mixers.size(); ++m) {
+    if (g->mixers[m].children.empty()) continue;
+    for (const Event& e : g->mixers[m].events) { if (e.sample_time >= now + chunk_n) break; if (e.sample_time > now) cuts.push_back(e.sample_time); }
+  }
+}
+uint64_t call_budget_bound(std::vector<uint64_t>& cuts, uint64_t now, uint64_t chunk_n) {
+  std::sort(cuts.begin(), cuts.end());
+  cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+  return cuts.size() > (size_t)(PG_MAX_CALLS - 1) ? cuts[PG_MAX_CALLS - 1] - now : chunk_n;
+}
+
 // Renders frames [pos, pos + n_samples / 2) of the write call into d_out. The call is walked in the reference's chunks — min(remaining,
 // PG_MAX_FRAMES) frames from the call's start and from every main-mixer event (mixed.rs:679-712) — whatever max_frames is: a chunk is rendered
 // as pieces of at most max_frames frames, every per-chunk decision taken once per chunk on the device (pg_dev.h: PG_MAX_FRAMES).
@@ -1591,7 +1607,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
   uint64_t done = 0;
   auto fail = [&]() -> size_t { g->failed = true; return 0; };
   // Deferred bus chain: the call leaves ONE `audible` word per piece it emits, in order (a running cursor — a chunk that an event cut short
-  // has pieces of its own, and max_frames need not divide a chunk), and the offsets at which an event restarted the chunk grid:
+  // has pieces of its own, and max_frames need not divide a chunk), and EVERY offset at which the chunk grid restarted (grid_restarts below):
   // process_bus_impl walks the same grid with the same cursor (round-4 advisor finding: the words used to sit at done / max_frames).
   uint64_t word_cursor = 0;
   int* const aud_words = (g->defer_bus && g->d_audible_out) ? g->d_audible_out : g->d_audible;   // where the mixer sum leaves the `audible` words
@@ -1625,6 +1641,10 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
     if (span == 0) continue;
     const bool span_ends_at_event = span < frames - done;   // the grid restarts behind this span
     uint64_t chunk_n = std::min<uint64_t>(span, CH);
+    // Does the chunk grid restart behind the `len` frames just rendered (`done` already counts them)? At the event that ends the span, and behind
+    // every chunk that ended short of the grid's chunk length for another reason: the call budget of nested mixers below. Each restart of a
+    // deferred-bus write is recorded, so that process_bus_impl walks the pieces this write walked and finds one word per piece.
+    auto grid_restarts = [&](uint64_t len) { return g->defer_bus && done < frames && ((span_ends_at_event && len == span) || len % CH != 0); };
     // StopSource messages: processed by process_messages at the start of write (:294-499)
     if (g->messages_due) {
       for (size_t m = 0; m < g->mixers.size(); ++m) {
@@ -1696,7 +1716,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       if (overlap) { HIP_TRY_FAIL(hipEventRecord(g->ev_rows_free, stream)); g->rows_free_fresh = true; }
       if (!g->defer_bus && launch_bus(g, d_out + done * 2, sp, slot, stream)) return fail();
       done += k * mf;
-      if (g->defer_bus && span_ends_at_event && k * mf == span && done < frames) g->defer_cuts.push_back(done);
+      if (grid_restarts(k * mf)) g->defer_cuts.push_back(done);
       continue;
     }
     // ---- one chunk, piece by piece ----
@@ -1704,13 +1724,8 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
     // A sub-mixer keeps one result bit per call of its parent: the chunk is bounded so that at most PG_MAX_CALLS - 1 call boundaries fall inside it
     if (g->levels.size() > 1) {
       std::vector<uint64_t> cuts;
-      for (size_t m = 1; m < g->mixers.size(); ++m) {
-        if (g->mixers[m].children.empty()) continue;
-        for (const Event& e : g->mixers[m].events) { if (e.sample_time >= now + chunk_n) break; if (e.sample_time > now) cuts.push_back(e.sample_time); }
-      }
-      std::sort(cuts.begin(), cuts.end());
-      cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-      if (cuts.size() > (size_t)(PG_MAX_CALLS - 1)) chunk_n = cuts[PG_MAX_CALLS - 1] - now;
+      graph_call_cuts(g, now, chunk_n, cuts);
+      chunk_n = call_budget_bound(cuts, now, chunk_n);
     }
     const uint64_t n_pieces = (chunk_n + mf - 1) / mf, n_full = chunk_n / mf;
     if (g->defer_bus && word_cursor + n_pieces > g->audible_slots) {
@@ -1805,7 +1820,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       }
     }
     done += chunk_n;
-    if (g->defer_bus && span_ends_at_event && chunk_n == span && done < frames) g->defer_cuts.push_back(done);
+    if (grid_restarts(chunk_n)) g->defer_cuts.push_back(done);
   }
   if (done) {  // suffix maxima of the writes' end positions (one entry while the position only moves forward): pg_graph_set_voice_envelope
     g->write_count += 1;
@@ -1881,7 +1896,7 @@ int process_bus_impl(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_i
   uint64_t done = 0;
   HostMixer& main = g->mixers[0];
   // The chunk grid of the write this bus belongs to: it restarts at the bus events (queued below) AND wherever another main-mixer event — a
-  // volume / panning / speed / seek event of a main-mixer source — cut the write; those offsets were recorded by this graph's own deferred write
+  // volume / panning / speed / seek event of a main-mixer source — or the call budget of nested mixers cut the write; those offsets were recorded by this graph's own deferred write
   // of the same position (a root that renders no partial of its own, or ranks whose main-mixer sources take events the root does not see: the
   // caller cuts its calls there, pg_graph_next_main_event). Words are consumed with a running cursor, one per piece, as the write emitted them.
   const std::vector<uint64_t>* cuts = (g->defer_bus && g->defer_pos == pos_in_frames) ? &g->defer_cuts : nullptr;

@@ -469,6 +469,8 @@ bool graph_is_empty(const pg_graph* g);
 uint64_t graph_next_main_event(const pg_graph* g);
 int graph_enqueue_status(pg_graph* g, hipStream_t stream);
 void graph_collect_status(pg_graph* g);
+void graph_call_cuts(const pg_graph* g, uint64_t now, uint64_t chunk_n, std::vector<uint64_t>& cuts);
+uint64_t call_budget_bound(std::vector<uint64_t>& cuts, uint64_t now, uint64_t chunk_n);
 size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t pos, hipStream_t stream, bool begin = true, size_t cap_frames = 0);
 int process_bus_impl(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_in_frames, hipStream_t s, int* bus_audible);
 // level metering (pg_k_meter.hip)

@@ -769,6 +769,7 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
   const uint64_t span_chunks = std::max<uint64_t>(1, std::min<uint64_t>(s->stage_frames / CH, s->flag_stride / per_chunk));
   uint64_t done = 0;
   size_t stage_off = 0;
+  std::vector<uint64_t> cuts;
   while (done < frames) {
     // the segment ends where the next main-mixer event of any shard comes due (events at or before `now` apply at the segment's head)
     const uint64_t now = pos + done;
@@ -777,7 +778,17 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
       for (const Event& e : g->mixers[0].events) { if (e.sample_time > now) { seg = std::min<uint64_t>(seg, e.sample_time - now); break; } }
     uint64_t off = 0;
     while (off < seg) {
-      const uint64_t n = std::min<uint64_t>(seg - off, span_chunks * CH);
+      uint64_t n = std::min<uint64_t>(seg - off, span_chunks * CH);
+      // the call budget of nested mixers ends a chunk early where the one graph would end it: at the PG_MAX_CALLS-th distinct event of the
+      // shards' mixers that have sub-mixers (graph_write_impl). The span ends there and the next begins a new chunk grid on every shard and for
+      // the root's bus chain, so that all of them walk the same pieces and the shards' words line up.
+      for (uint64_t c = 0; c < n; c += CH) {
+        const uint64_t len = std::min<uint64_t>(CH, n - c);
+        cuts.clear();
+        for (const pg_graph* g : s->shards) graph_call_cuts(g, now + off + c, len, cuts);
+        const uint64_t bounded = call_budget_bound(cuts, now + off + c, len);
+        if (bounded < len) { n = c + bounded; break; }
+      }
       if (stage_off + n * 2 > 2 * s->stage_frames) stage_off = 0;   // (the staging is a ring of spans: reuse is ordered by the `summed` event and the shards' own streams)
       float* dst = contiguous ? d_out + (size_t)(done + off) * 2 : d_out;
       if (sharded_render_segment(s, dst, contiguous ? stage_off : 0, (size_t)n * 2, now + off)) { s->failed = true; return 0; }
