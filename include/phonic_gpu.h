@@ -299,9 +299,10 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
  * The granular parameters and the loop range change while the voice plays: pg_graph_set_voice_granular_parameter / _grain_loop_range below.
  * The mono buffer the pool reads is what create_granular_sample_buffer (sampler.rs:908-952) makes of a file: hand it over here as `mono_pcm`, or
  * let the device make it from a sample buffer (pg_graph_add_granular_voice_from_buffer below).
- * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; playback-position status events; the Sampler's
+ * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; the Sampler's
  * base transpose, finetune, volume and panning parameters (pg_graph_set_voice_speed / _volume / _panning carry their effect);
- * AHDSR parameter changes on a running envelope.
+ * AHDSR parameter changes on a running envelope. (The voice's playback-position status events — the start event, a Position per process call,
+ * the two Stopped records — are pg_graph_set_voice_status's, below.)
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
  * 2 Triangle, 3 Tukey, 4 Trapezoid, 5 Exponential, 6 RampUp, 7 RampDown (:61-70); size in ms, density in Hz, playback_direction 0 Forward,
  * 1 Backward, 2 Random (:19-26); plus GrainPool::sample_loop_range (:357, voice.rs:355-360) as has_loop_range / loop_start / loop_end,
@@ -456,8 +457,8 @@ int64_t pg_graph_read_granular_buffer(pg_graph* g, int buffer_id, float* out, si
  * and as UNVERIFIED against the crate). The matrix advances on the frames the voice renders only: not in front of its start time, not after it
  * has ended. A release touches no modulation source (note_off reaches envelope slots, and the sampler has none, sampler/modulation.rs:101-103).
  * In the reference the timed calls below reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
- * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the Sampler's note, voice-allocation and stealing layer;
- * playback-position status events (pg_modulation_state::last[5] is the value they would use, voice.rs:435-446). (The granular parameters
+ * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the Sampler's note, voice-allocation and stealing layer.
+ * (pg_modulation_state::last[5] is the value a granular voice's Position records use, voice.rs:435-446: pg_graph_set_voice_status.) (The granular parameters
  * themselves change through pg_graph_set_voice_granular_parameter above; a route's sum applies to the parameter's value as of its frame.) */
 #define PG_MOD_SOURCES 4
 #define PG_MOD_TARGETS 7
@@ -535,6 +536,66 @@ int pg_graph_set_metering(pg_graph* g, double interval_seconds);
  * or removed mixer; PG_ERR_PARAMETER: null handle or null `out`. With pg_graph_set_defer_bus the main mixer's record is taken at the end of
  * pg_graph_process_bus_device*, with that call's pos_in_frames and samples, not in the write. */
 int pg_graph_mixer_audio_level(pg_graph* g, int mixer_id, pg_audio_level* out);
+
+/* Playback status events: PlaybackStatusEvent::Position / ::Stopped { exhausted } (src/source/status.rs) as every file source and every sampler
+ * voice of the reference sends them — FileSourceImpl::send_playback_position_status / send_playback_stopped_status (src/source/file/common.rs:171-221)
+ * from PreloadedFileSource::write / stop / kill (src/source/file/preloaded.rs:196-239, :396-475) and SamplerVoice::process
+ * (src/generator/sampler/voice.rs:434-467, :488-502). The reference decides them once per Source::write call of the voice — once per chunk of the
+ * voice's mixer, once per segment where the mixer's events (or an ancestor's) cut the chunk, and where the voice's stop time cuts the call
+ * (src/source/mixed.rs:558-624, :679-712) — and so does the device (pg_playback_status_kernel, DESIGN.md "Playback status"): every record equals the
+ * reference's, field by field; the host derives no position.
+ *   sample_time       SourceTime::pos_in_frames of the source write that sent the record (for a stop without a fade-out: the stop's time)
+ *   Position          after every source write that was not skipped as finished, if `elapsed(time.pos_in_frames) >= emit_rate` — elapsed: a saturating
+ *                     subtraction from the clock's start_time, 0 at first (src/utils/time.rs:19-55) — with playback_pos as it stands BEHIND that write,
+ *                     and the clock restarts at time.pos_in_frames (common.rs:171-208). frame_pos = sample_pos / channel_count, position_seconds =
+ *                     frame_pos as f64 / sample_rate as f64 (:195-196), both of the FILE buffer. A file voice sends no start event: `playback_started`
+ *                     is never set to true anywhere in the reference (docs/parity_findings.md).
+ *   Stopped           { exhausted: playback_pos_eof } with the write in which the end of the file was reached or the fade-out completed (preloaded.rs:464-472);
+ *                     at the stop's time when the voice stops without a fade-out (:196-208); for an enveloped voice with the write in which the envelope
+ *                     reached Idle — SamplerVoice::reset -> PreloadedFileSource::reset -> kill, if the source had not finished already (voice.rs:488-495,
+ *                     preloaded.rs:212-239). Position stands before Stopped.
+ *   granular voices   every process call sends Position (under the emit test), the first one as a start event: unconditionally (grain_pool_started,
+ *                     voice.rs:449-467); sample_pos = (GrainPool::playback_position(parameters, pos_mod) * buffer_len as f32) as u64 (granular.rs:446-472),
+ *                     pos_mod = the last frame's GRAIN_POSITION sum (0.0 without a matrix). buffer_len, channel_count and sample_rate are the FILE
+ *                     buffer's for a voice made from a sample buffer; n_frames, 1 and the graph's rate for pg_graph_add_granular_voice. When the voice
+ *                     ends, two Stopped records (voice.rs:488-502): reset()'s kill with exhausted 0 (the file source never played), then
+ *                     { exhausted: pool.is_exhausted() } evaluated behind GrainPool::reset, which re-arms the trigger (granular.rs:442-444, :495-502): 0.
+ *   nothing           from pg_graph_remove_voice, and from a voice pg_graph_stop_all_voices took before it had started.
+ * pg_graph_enable_status: once, before the first write (PG_ERR_STATE otherwise); reserves the ring of `capacity_events` records (>= 1, else
+ *   PG_ERR_PARAMETER) and the tables the kernel works from — writes and polls allocate nothing. The reference sends with try_send on a bounded
+ *   channel and drops what finds it full: a record that finds capacity_events unpolled ones is dropped — the newest goes — and counted
+ *   (pg_graph_status_dropped). The count also holds what the device could not keep, which takes a chunk that a mixer's events cut very often: the
+ *   exact kernel logs 32 source writes of a voice per launch, and a job of the status kernel has three record slots per source write it can see.
+ * pg_graph_set_voice_status: position_emit_seconds = FilePlaybackOptions::playback_pos_emit_rate (<= 0: None, no Position records; > 0: converted as
+ *   SampleTimeClock::duration_to_sample_time does, (secs * rate as f64) as u64, time.rs:28-35); report_stopped != 0: Stopped records. Every voice starts
+ *   with both off, and a graph that never calls this is what it was without it. Only before the voice has rendered a frame (PG_ERR_STATE afterwards;
+ *   PG_ERR_STATE also when status is not enabled on the graph); PG_ERR_NOT_FOUND for an unknown voice; PG_ERR_PARAMETER for a NaN, a null handle, a
+ *   host-fed voice and a voice whose source_rate is not the graph's. Owner thread; waits for earlier writes like every graph-changing call.
+ * pg_graph_poll_status: copies out up to max_events records, oldest first, and returns how many. They cover every write that has returned (on a
+ *   caller's stream, and for pg_graph_set_defer_bus graphs: every write up to the last pg_graph_synchronize / wait for that stream). Order: by
+ *   sample_time; then as the reference's write reaches the voices — a mixer's sub-mixers first, in the order they were added, then its sources in its
+ *   list's order (sorted by start time, a new source in front of those that start at the same time: mixed.rs:324-329, :505-620); then as one source
+ *   write sent them. Owner thread.
+ * While a voice that reports is in the graph, writes are rendered chunk by chunk, piece by piece (no launch of several blocks,
+ * pg_graph_set_max_blocks_per_launch: the result of those is bit-identical to single launches anyway), pg_playback_status_kernel behind every piece.
+ * The audio does not depend on who reports: the same kernels render the same pieces, bit for bit ("Playback status").
+ * OUT OF SCOPE: host-fed and rate-converted voices; PlaybackStatusContext payloads (a binding keeps a map from voice id to context); CPU-load
+ * measurement; the Sampler's note layer (which forwards its voices' events). */
+#define PG_STATUS_POSITION 0
+#define PG_STATUS_STOPPED  1
+typedef struct pg_status_event {
+  int32_t  kind;              /* PG_STATUS_* */
+  int32_t  voice_id;
+  uint64_t sample_time;       /* SourceTime::pos_in_frames of the source write that emitted it */
+  uint64_t frame_pos;         /* Position: sample_pos / channel_count (common.rs:195); Stopped: 0 */
+  double   position_seconds;  /* frame_pos as f64 / sample_rate as f64 (common.rs:196); Stopped: 0 */
+  int32_t  exhausted;         /* Stopped only */
+  int32_t  reserved;
+} pg_status_event;
+int pg_graph_enable_status(pg_graph* g, size_t capacity_events);
+int pg_graph_set_voice_status(pg_graph* g, int voice_id, double position_emit_seconds, int report_stopped);
+int pg_graph_poll_status(pg_graph* g, pg_status_event* out, size_t max_events);
+uint64_t pg_graph_status_dropped(pg_graph* g);
 
 /* Source::write(&mut output, &SourceTime{pos_in_frames}) of the main MixedSource
  * (src/source/mixed.rs:659-719): returns the samples written == n_samples, or 0 when the
@@ -701,6 +762,14 @@ int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modu
  * behind the bus chain, one record per pg_sharded_write* call (src/source/metered.rs:75-143) */
 int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds);
 int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_level* out);
+/* pg_graph_enable_status / _set_voice_status / _poll_status / _status_dropped on the one mixer (src/source/status.rs, src/source/file/common.rs:171-221):
+ * the shard that owns a voice decides its records; every shard keeps a ring of capacity_events records of its own. Voice ids are the handle's; a
+ * poll merges the shards' records into the order of pg_graph_poll_status — the main mixer's sub-mixers in the order they were added, whatever shard
+ * holds them, then its sources in its list's order — and the dropped count is the shards' sum. */
+int pg_sharded_enable_status(pg_sharded_graph* s, size_t capacity_events);
+int pg_sharded_set_voice_status(pg_sharded_graph* s, int voice_id, double position_emit_seconds, int report_stopped);
+int pg_sharded_poll_status(pg_sharded_graph* s, pg_status_event* out, size_t max_events);
+uint64_t pg_sharded_status_dropped(pg_sharded_graph* s);
 /* Source::write: host buffer (waits for the result) / buffer on the root device (asynchronous on the shards' streams, several calls may be
  * enqueued before pg_sharded_synchronize). A call of ANY length is ONE write of the one main mixer — messages processed once on every shard,
  * one call end — walked on the reference's chunk grid (min(remaining, 4096) frames from the call's start and from every main-mixer event of

@@ -83,6 +83,22 @@ class AudioLevel(C.Structure):
     _fields_ = [("peak", C.c_float * 2), ("rms", C.c_float * 2)]
 
 
+class StatusEvent(C.Structure):
+    """pg_status_event: one PlaybackStatusEvent (reference src/source/status.rs) as the device decided it — Position or Stopped { exhausted }."""
+    _fields_ = [("kind", C.c_int32), ("voice_id", C.c_int32), ("sample_time", C.c_uint64), ("frame_pos", C.c_uint64), ("position_seconds", C.c_double),
+                ("exhausted", C.c_int32), ("reserved", C.c_int32)]
+
+
+PG_STATUS_POSITION, PG_STATUS_STOPPED = 0, 1
+
+
+def status_tuple(e):
+    """A pg_status_event as a plain tuple: ("position", voice, sample_time, frame_pos, position_seconds) or ("stopped", voice, sample_time, exhausted)."""
+    if e.kind == PG_STATUS_POSITION:
+        return ("position", int(e.voice_id), int(e.sample_time), int(e.frame_pos), float(e.position_seconds))
+    return ("stopped", int(e.voice_id), int(e.sample_time), bool(e.exhausted))
+
+
 def _db(x):
     import math
 
@@ -516,6 +532,12 @@ def load():
         fn = getattr(lib, prefix + "mixer_audio_level")
         fn.restype = C.c_int
         fn.argtypes = [vp, C.c_int, P(AudioLevel)]
+    for prefix in ("pg_graph_", "pg_sharded_"):
+        for name, res, args in (("enable_status", C.c_int, [C.c_size_t]), ("set_voice_status", C.c_int, [C.c_int, C.c_double, C.c_int]),
+                                ("poll_status", C.c_int, [P(StatusEvent), C.c_size_t]), ("status_dropped", C.c_uint64, [])):
+            fn = getattr(lib, prefix + name)
+            fn.restype = res
+            fn.argtypes = [vp] + args
     lib.pg_granular_params_default.restype = None
     lib.pg_granular_params_default.argtypes = [P(GranularParams)]
     lib.pg_granular_params_check.restype = C.c_int

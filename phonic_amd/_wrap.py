@@ -292,6 +292,24 @@ class GraphHandle:
         self._check(self._fn("graph_mixer_audio_level")(self._h, mixer_id, C.byref(raw)))
         return _capi.Level(raw)
 
+    def enable_status(self, capacity_events=4096):
+        """Playback status events (PlaybackStatusEvent::Position / Stopped): once, before the first write; the ring holds `capacity_events` unpolled records."""
+        self._check(self._fn("graph_enable_status")(self._h, capacity_events))
+
+    def set_voice_status(self, voice, position_emit_seconds=None, report_stopped=True):
+        """FilePlaybackOptions::playback_pos_emit_rate of a voice (None: no Position records) and whether it reports Stopped; before the voice renders."""
+        self._check(self._fn("graph_set_voice_status")(self._h, voice, -1.0 if position_emit_seconds is None else float(position_emit_seconds), 1 if report_stopped else 0))
+
+    def poll_status(self, max_events=4096):
+        """The records of every write that has returned, oldest first, as _capi.status_tuple tuples."""
+        buf = (_capi.StatusEvent * max_events)()
+        n = int(self._fn("graph_poll_status")(self._h, buf, max_events))
+        return [_capi.status_tuple(buf[i]) for i in range(n)]
+
+    def status_dropped(self):
+        """Records dropped because the ring was full (the reference's try_send on a full channel)."""
+        return int(self._fn("graph_status_dropped")(self._h))
+
     def remove_voice(self, voice):
         """MixerMessage::RemoveSource: the source leaves its mixer at the start of the next write, at once (no fade)."""
         self._check(self._fn("graph_remove_voice")(self._h, voice))

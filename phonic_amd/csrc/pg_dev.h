@@ -191,12 +191,15 @@ struct PgVoice {
   float speed_glide_rate;
   uint32_t samples_to_next_speed_update;
   int32_t sched_class, sched_rep;  // resampler schedule cache: class of voices sharing a ratio; 1 = this voice publishes the schedule
-  int32_t sched_hit, pad_sched;    // device: how the last resampling piece got its schedule: 0 serial replay, 1 schedule cache, 2 time-parallel
+  int32_t sched_hit;               // device: how the last resampling piece got its schedule: 0 serial replay, 1 schedule cache, 2 time-parallel
+  uint32_t stop_pos_lo;            // device: playback_pos (low word; stop_pos_hi below) as the source write that reached the voice's stop time left it — the next
+                                   // write begins there with the Stop message (mixed.rs:584-603) and moves playback_pos on; playback status reads it (pg_k_status.hip)
   // ResampledSource around the file source (src/source/resampled.rs:27-98), present when the file source runs at a rate (`out_rate`) other
   // than the mixer's (pg_voice_options::source_rate): cubic interpolator state per channel + the two 512-frame TempBuffers
   int32_t outer_on, outer_pending_stop;
   int32_t outer_init[2];
-  float outer_ratio, pad_outer;
+  float outer_ratio;
+  uint32_t stop_pos_hi;            // (see stop_pos_lo)
   float outer_sub_pos[2];
   float outer_input[2][4];
   uint32_t in_start, in_end, out_start, out_end;  // TempBuffer ranges (samples)
@@ -242,6 +245,7 @@ struct PgEnv {
 // The side table in device memory: this header, then one PgEnv per voice, indexed like PgLaunch::voices. `done`: one word per voice in mapped
 // host memory that the exact kernel sets when an enveloped voice has ended — the host then takes the voice's unit off the exact kernel again.
 struct PgGrainVoice;
+struct PgStatVoice;
 struct PgEnvTable {
   int32_t* done;
   uint64_t cap;         // entries behind the header: the kernel takes no entry at or beyond it
@@ -250,9 +254,74 @@ struct PgEnvTable {
   const int32_t* grain_of_voice;
   PgGrainVoice* grains;
   uint32_t n_grains;    // records `grains` holds: no record at or beyond it is taken
-  uint32_t pad_grains[3];
+  // playback status (pg_graph_set_voice_status): stat_of_voice[v] (v < cap) = index of voice v's record in `stats`, -1 for every other voice;
+  // nullptr: status was never enabled on the graph. The exact kernel logs the source writes of such a voice there (PgStatVoice below).
+  uint32_t n_stats;     // records `stats` holds: no record at or beyond it is taken
+  const int32_t* stat_of_voice;
+  PgStatVoice* stats;
+  uint64_t pad_stats;
 };
-static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 48, "the entries follow the header, 16-byte aligned");
+static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 64, "the entries follow the header, 16-byte aligned");
+
+// ---- playback status events (pg_graph_set_voice_status; pg_k_status.hip) ----
+// PlaybackStatusEvent::Position / Stopped are decided once per Source::write call of the voice (src/source/file/preloaded.rs:396-475,
+// src/source/file/common.rs:171-221, src/generator/sampler/voice.rs:434-502). pg_playback_status_kernel runs behind every launch of a level that holds
+// such a voice and keeps one PgStatVoice per voice: the emit clock, the voice's state as the launch before left it, and the source write in
+// progress. A launch of the time-parallel kernels holds one segment per unit: one source write (or part of one) per voice, or two where the
+// voice's stop time lies inside the launch — the status kernel reads what the last one left in PgVoice, and playback_pos behind the one that
+// ended at the stop time in PgVoice::stop_pos_lo / _hi, which every kernel's voice_process leaves there. The exact kernel can render several source writes of a voice in one launch (a chunk cut
+// by events, a stop time inside the piece): it logs every write that ENDS in the launch here, and stamps the record with the launch's round.
+#define PG_STAT_LOG 32                   // source writes of one voice the exact kernel can log per launch; later ones are counted in `lost`
+enum { PG_SW_EOF = 1,                    // playback_pos_eof behind the write
+       PG_SW_FINISHED = 2,               // playback_finished behind the write (for a sampler voice: the voice was reset, voice.rs:488-495)
+       PG_SW_SKIPPED = 4,                // the source was finished when the write began: it returned at once (preloaded.rs:400-403), nothing is sent
+       PG_SW_KILLED = 8,                 // a stop without a fade-out, taken by process_messages in front of the write: Stopped, then nothing (preloaded.rs:196-208)
+       PG_SW_EOF_BEFORE = 16 };          // playback_pos_eof as the write began (what that Stopped carries)
+struct PgStatWrite {
+  uint64_t time;                         // SourceTime::pos_in_frames of the write
+  uint64_t pos;                          // sample_pos behind it: playback_pos, or the grain pool's (voice.rs:463)
+  int32_t flags, pad;
+};
+enum { PG_SV_POSITION = 1,               // playback_pos_emit_rate is Some(emit_rate)
+       PG_SV_STOPPED = 2,                // Stopped records are wanted
+       PG_SV_GRANULAR = 4,               // a sampler voice in granular mode: start event, position from the pool, two Stopped records
+       PG_SV_STARTED = 8 };              // grain_pool_started (voice.rs:169, :456-457): the next Position is a start event
+struct PgStatVoice {
+  int32_t voice;                         // device index of the voice (PgLaunch::voices)
+  int32_t voice_id;                      // the id the host knows it by (what the records carry)
+  int32_t flags;                         // PG_SV_*
+  uint32_t log_round;                    // PgLaunch::round of the last launch in which the exact kernel rendered the voice's unit
+  uint64_t emit_rate;                    // playback_pos_emit_rate in frames
+  uint64_t clock_start;                  // SampleTimeClock::start_time of playback_pos_sample_time_clock (time.rs:19-55)
+  uint32_t channels, rate;               // channel_count and sample_rate of the FILE buffer (common.rs:195-196)
+  uint64_t buffer_len;                   // granular voices: file_buffer.buffer().len() (voice.rs:463)
+  // the voice as the last launch left it (what the next launch's source write finds)
+  int32_t prev_active, prev_finished, prev_has_stop, prev_pos_eof, prev_chunk_skip, pad_prev;
+  uint64_t prev_stop_time;
+  // the source write in progress: begun in an earlier launch of the chunk, it goes on in the next one
+  int32_t open, open_flags;
+  uint64_t open_time;
+  int32_t n_log, lost;                   // entries of `log` the exact kernel left in the current launch; writes it could not log
+  PgStatWrite log[PG_STAT_LOG];
+};
+static_assert(sizeof(PgStatWrite) == 24 && sizeof(PgStatVoice) % 8 == 0, "host and device agree on the layout");
+// One lane of pg_playback_status_kernel: the record it works on, where the launch sits, and the fixed slots its records go to. The jobs and the slots are
+// mapped host memory: the kernel fills the slots, then `count`; the host compacts the slots after the call (pg_status_host.h).
+struct PgStatJob {
+  int32_t rec;                           // index into the graph's PgStatVoice records
+  int32_t slot0, n_slots;                // the job's record slots
+  int32_t count;                         // device: records written (-1 until the kernel has run), ...
+  int32_t lost;                          // ... records that found no slot + source writes the exact kernel could not log
+  uint32_t round;                        // PgLaunch::round of the launch this job stands behind
+  uint64_t t0;                           // position of the launch's first frame
+  uint32_t n;                            // frames of the launch
+  int32_t first;                         // the launch is the first piece of its chunk of the main mixer
+  uint64_t chunk_end;                    // position at which that chunk ends
+  // host only: where the voice stands in the reference's traversal of that write, and the sub-mixer of the main mixer it sits under (0: none)
+  uint32_t rank;
+  int32_t top;
+};
+static_assert(sizeof(PgStatJob) == 56, "host and device agree on the layout");
 
 // ---- granular voices: GrainPool<100> of a sampler voice (src/generator/sampler/granular.rs), see pg_grain_dev.h / pg_k_grain.hip ----
 #define PG_GRAIN_POOL 100      // Sampler's GrainPool<100>: concurrent grains of one voice
@@ -313,6 +382,8 @@ struct PgGrainVoice {
   uint64_t exhausted_at;       // position of the frame behind which GrainPool::is_exhausted() first held (UINT64_MAX: not yet)
   int32_t voice;               // device index of the voice (PgLaunch::voices)
   int32_t has_env;             // the voice has a volume envelope: CMD_VOICE_RELEASE is its note_off, not a stop
+  float* pos_trace;            // playback status (pg_graph_set_voice_status): PG_MAX_FRAMES floats, GrainPool::playback_position behind every rendered frame of
+                               // the staged chunk (frame f of the chunk in word f); nullptr: the voice reports nothing and pg_grain_kernel leaves it out
   PgGrain grains[PG_GRAIN_POOL];
   PgGrainMod mod;              // the voice's ModulationMatrix (pg_graph_set_voice_modulation_matrix); mod.on == 0: none, every `*_mod` is left out
 };

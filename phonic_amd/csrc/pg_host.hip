@@ -59,7 +59,8 @@ void graph_voice_release(pg_graph* g, HostVoice& hv) {
   if (hv.d_pcm) (void)pg_free(hv.d_pcm);
   if (hv.d_stage) (void)pg_free(hv.d_stage);
   if (hv.h_ring) (void)pg_host_free(hv.h_ring);
-  hv.d_pcm = nullptr; hv.d_stage = nullptr; hv.h_ring = nullptr;
+  if (hv.d_trace) (void)pg_free(hv.d_trace);
+  hv.d_pcm = nullptr; hv.d_stage = nullptr; hv.h_ring = nullptr; hv.d_trace = nullptr;
   if (hv.sbuf >= 0) { sample_buffer_unref(g, hv.sbuf); hv.sbuf = -1; }
 }
 
@@ -437,6 +438,7 @@ void pg_graph_destroy(pg_graph* g) {
   if (g->h_pinned) (void)pg_host_free(g->h_pinned);
   if (g->h_feedback) (void)pg_host_free(g->h_feedback);
   graph_sampler_release(g);
+  graph_pstat_release(g);
   graph_meter_release(g);
   for (auto& e : g->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   for (auto& e : g->ev_bus_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -498,6 +500,7 @@ static void stop_all_voices_now(pg_graph* g) {
     PgCmd c;
     memset(&c, 0, sizeof c);
     c.type = CMD_VOICE_STOP; c.target = g->voices[v].dev_index; c.value64 = 0; c.param = (int)v;
+    g->voices[v].stop_time = 0;
     g->mixers[g->voices[v].mixer].messages.push_back(c);
   }
   for (HostMixer& mx : g->mixers) if (!mx.removed) { mx.remove_pending = true; mx.remove_event_seq = g->event_seq; mx.remove_voice_limit = g->voices.size(); }
@@ -681,6 +684,7 @@ int graph_add_file_voice(pg_graph* g, int mixer_id, const float* pcm, int sbuf, 
   int rc = g->d_voices.push(v, &dev_index);
   if (rc) { release(); return -graph_fail(g, rc); }
   if (sb) { hv.sbuf = sbuf; g->sample_buffers[sbuf].use_count += 1; }
+  hv.file_channels = src_channels; hv.file_rate = src_rate; hv.file_samples = n_samples;
   return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_FILE);
 }
 extern "C" {
@@ -927,7 +931,7 @@ void drain_control_messages(pg_graph* g) {
           g->topo_dirty = true;
           break;
         }
-        if (m.type == pgc::CT_VOICE_STOP) { c.type = CMD_VOICE_STOP; c.value64 = m.sample_time; g->mixers[hv.mixer].messages.push_back(c); break; }
+        if (m.type == pgc::CT_VOICE_STOP) { c.type = CMD_VOICE_STOP; c.value64 = m.sample_time; g->voices[m.id].stop_time = m.sample_time; g->mixers[hv.mixer].messages.push_back(c); break; }
         for (const VoiceEvent& ve : VOICE_EVENTS) if (ve.msg == m.type) {
           c.type = ve.cmd;
           ve.fill(m, g->sample_rate, c);
@@ -1146,6 +1150,9 @@ static bool graph_steady(const pg_graph* g) {
 // chain's per-block decisions block by block (the reference's chunk loop inside one write call, mixed.rs:679-712); the bus unit is
 // rendered by the generic kernel, which needs no steady state of its own.
 static bool graph_super_ok(const pg_graph* g) {
+  // (playback status: a launch of several blocks holds several source writes of a voice — a graph with a voice that reports renders chunk by
+  // chunk, piece by piece, pg_playback_status_kernel behind every piece: DESIGN.md "Playback status")
+  for (int v : g->pstat.voices) if (g->voices[v].mixer >= 0 && g->voices[v].pstat_on) return false;
   return g->max_blocks > 1 && g->staged_mode != 2 && graph_steady(g);
 }
 
@@ -1737,6 +1744,9 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
     if (n_pieces > g->unit_out_blocks) { set_error(PG_ERR_STATE, "per-unit buffers were not reserved for a chunk's pieces"); return fail(); }
     if (g->metering) meter_collect_chunk(g, now, chunk_n, mf);   // (launched behind the chunk's sum)
     std::vector<LaunchSpan> spans((size_t)n_pieces);
+    bool pstat_live = false;   // playback status: some voice of the graph reports (pg_k_status.hip)
+    for (int v : g->pstat.voices) pstat_live |= g->voices[v].mixer >= 0 && g->voices[v].pstat_on;
+    std::vector<std::vector<std::pair<int, int>>> pstat_cmds(pstat_live ? (size_t)n_pieces : 0);
     const uint64_t round0 = g->launch_counter;
     g->launch_counter += n_pieces;
     const bool steady_now = g->levels.size() == 1 && graph_steady(g);
@@ -1749,6 +1759,10 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       std::vector<PgCmd> cmds;
       if (p == 0) cmds = head;
       collect_piece_commands(g, cmds, sp.t0, sp.n, now, now + chunk_n);
+      if (pstat_live) for (const PgCmd& c : cmds) {  // (sorted by unit) how many commands each unit takes in this piece: what the exact kernel may log there
+        if (!pstat_cmds[(size_t)p].empty() && pstat_cmds[(size_t)p].back().first == c.unit) pstat_cmds[(size_t)p].back().second += 1;
+        else pstat_cmds[(size_t)p].emplace_back(c.unit, 1);
+      }
       if (!cmds.empty()) {
         // (a round that will run its decision-scan kernel takes a short list there as the kernel's argument: no copy kernel on the stream)
         sp.n_cmds = (int)cmds.size();
@@ -1778,6 +1792,7 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
       const LaunchSpan& sp = spans[(size_t)p];
       if (launch_grains(g, sp.t0, sp.n, now, sp.d_cmds, sp.n_cmds, stream)) return fail();
     }
+    if (pstat_live && graph_pstat_begin_chunk(g, pstat_cmds, stream)) return fail();
     for (size_t li = 0; li < g->levels.size(); ++li) {
       for (uint64_t p = 0; p < n_pieces; ++p) {
         LaunchSpan sp = spans[(size_t)p];
@@ -1785,8 +1800,11 @@ size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t po
         // average can time every n-th round (pg_graph_set_timing_period)
         sp.timed = li == tl && g->timing_period > 0 && ((sp.round + 1) % (uint64_t)g->timing_period) == 0 && g->ev_used < g->ev_pool.size() && g->n_graph_units > 0;
         if (launch_level(g, li, sp, stream)) return fail();
+        // playback status: what this piece's source writes of the level's voices left, before the next piece moves them on
+        if (pstat_live && graph_pstat_launch(g, li, sp.t0, sp.n, p == 0, now + chunk_n, (uint32_t)sp.round, pstat_cmds[(size_t)p], stream)) return fail();
       }
     }
+    if (pstat_live) graph_pstat_end_chunk(g);
     // the chunk's sum and bus chain: its full pieces in one launch each, a shorter last piece in launches of its own
     const int slot0 = g->defer_bus ? (int)word_cursor : 0;
     if (g->defer_bus) { word_cursor += n_pieces; g->defer_words = (int)word_cursor; }

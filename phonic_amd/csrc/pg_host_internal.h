@@ -24,6 +24,7 @@
 #include "pg_meter.h"
 #include "pg_dsp_dev.h"
 #include "pg_params.h"
+#include "pg_status_host.h"
 
 using namespace pgd;
 using namespace pgh;
@@ -253,6 +254,12 @@ struct HostVoice {
   bool gran_live = false;          // ... and pg_grain_kernel has not reported the voice ended: it renders the voice, the exact kernel its unit
   bool mod = false;                // ... with a modulation matrix (pg_graph_set_voice_modulation_matrix): PgGrainVoice::mod of its record
   int sbuf = -1;                   // the voice plays pg_graph::sample_buffers[sbuf] (pg_graph_add_*_voice_from_buffer): d_pcm stays null — the PCM is the buffer's
+  uint64_t stop_time = UINT64_MAX; // the last StopSource time sent for the voice (pg_graph_stop_voice): what a voice that begins to report may find pending (pg_k_status.hip)
+  int pstat = -1;                  // playback status (pg_graph_set_voice_status): its record in pg_graph::pstat.d_recs ...
+  bool pstat_on = false;           // ... and whether the voice reports anything (Position records, Stopped records or both)
+  float* d_trace = nullptr;        // ... of a granular voice: PgGrainVoice::pos_trace (owned by the voice)
+  uint32_t file_channels = 0, file_rate = 0;   // the FILE buffer behind the voice: what a Position record divides by (common.rs:195-196) ...
+  uint64_t file_samples = 0;                   // ... and its buffer().len() (voice.rs:463)
 };
 // A sample buffer on the device (pg_graph_add_sample_buffer): AudioFileBuffer behind an Arc (src/source/file/buffer.rs). The host holds one
 // reference until pg_graph_release_sample_buffer, every voice made from it one until its memory is released (graph_voice_release).
@@ -286,6 +293,35 @@ struct HostMixer {
 // Launch level: the units of one depth of the mixer tree. A mixer reads its sub-mixers' output rows, so the levels are launched
 // deepest first, in stream order; the sub-mixers of the main mixer and its sources form the last level (summed by the mix kernels).
 struct Level { int off = 0, cnt = 0, n_staged = 0, n_staged_wide = 0, n_staged_adapt = 0, n_static_defer = 0; };
+
+// Playback status events (pg_k_status.hip). The launch tables of pg_playback_status_kernel — its jobs and the record slots they fill — are
+// mapped host memory in two halves, like the meter's; a chunk of the main mixer reserves what its launches need before the first one is issued,
+// so a chunk's records never straddle a half. A half is reused once the event recorded behind its last launch has passed and its records
+// have been compacted into the ring.
+struct PstatLaunch { size_t job0 = 0, n_jobs = 0; bool closes = false; };   // one launch; `closes`: the last one of its chunk
+struct PstatState {
+  bool on = false;
+  pgs::StatusRing ring;
+  std::vector<pgs::StatusRec> gather;      // the chunk being compacted (capacity kept)
+  uint64_t lost = 0;                       // records the device could not place (added to the ring's dropped count)
+  PgStatVoice* d_recs = nullptr; size_t n_recs = 0, cap_recs = 0;
+  int32_t* d_of_voice = nullptr;           // PgEnvTable::stat_of_voice: one entry per entry of the envelope table
+  std::vector<int> voices;                 // ids of the voices that report, in the order they were enabled
+  PgStatJob* h_jobs = nullptr; PgStatJob* d_jobs = nullptr;
+  pg_status_event* h_slots = nullptr; pg_status_event* d_slots = nullptr;
+  size_t half_jobs = 0, half_slots = 0, nj = 0, ns = 0;   // entries per half / used in the current half
+  int turn = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool in_flight[2] = {false, false};
+  std::vector<PstatLaunch> pending;        // launches whose records have not been compacted yet, oldest first (capacity kept)
+  size_t pending_head = 0;
+  // the chunk being issued: the voices that report, in traversal order, and what the chunk's launches may still take of the current half
+  struct Walk { int voice; int level; uint32_t rank; int top; int unit; };
+  std::vector<Walk> walk;
+  size_t chunk_jobs_left = 0, chunk_slots_left = 0;
+  bool chunk_min_slots = false;            // the chunk's launches would not fit a half with room for everything the exact kernel may log: every job
+                                           // takes the slots of one source write, what finds none is counted as dropped
+};
 
 struct pg_graph {
   int device = 0;
@@ -444,6 +480,7 @@ struct pg_graph {
   DeviceTable<int32_t> d_gran_live;      // their records
   std::vector<int32_t> gran_live;        // ... as the next upload puts them together (capacity kept across writes)
   bool gran_live_dirty = false;
+  PstatState pstat;                      // playback status events (pg_graph_enable_status)
   std::vector<SampleBuffer> sample_buffers;   // by buffer id (ids are never reused)
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
@@ -478,9 +515,20 @@ int graph_meter_reserve(pg_graph* g);    // mutating calls, graph quiescent: may
 void graph_meter_release(pg_graph* g);
 int graph_meter_launch(pg_graph* g, hipStream_t stream);   // g->meter_jobs / g->meter_spans -> one pg_meter_kernel launch
 int graph_meter_main(pg_graph* g, const float* d_ptr, uint64_t frames, uint64_t time, bool end_of_record, hipStream_t stream);
+// playback status events (pg_k_status.hip)
+void graph_pstat_release(pg_graph* g);
+// One chunk of the main mixer rendered as pieces, one launch per level and piece. piece_cmds[p] = (unit slot, commands addressed to it) of piece p,
+// sorted by unit. begin: the voices that report, in traversal order, and room in the launch tables for all of the chunk's launches.
+// launch: pg_playback_status_kernel behind the launch of level `li` that rendered frames [t0, t0 + n) (`first`: the chunk's first piece).
+int graph_pstat_begin_chunk(pg_graph* g, const std::vector<std::vector<std::pair<int, int>>>& piece_cmds, hipStream_t stream);
+int graph_pstat_launch(pg_graph* g, size_t li, uint64_t t0, uint32_t n, bool first, uint64_t chunk_end, uint32_t round, const std::vector<std::pair<int, int>>& unit_cmds, hipStream_t stream);
+void graph_pstat_end_chunk(pg_graph* g);
+void graph_pstat_collect(pg_graph* g, bool wait);   // completed chunks -> the ring (wait: for every launch issued so far)
+bool voice_has_rendered(const pg_graph* g, const HostVoice& hv);
 // sampler voices (pg_sampler.hip)
 int pg_ahdsr_params_check(const pg_ahdsr_params* p);   // the reference's parameter errors (PG_OK / PG_ERR_PARAMETER): no graph, no device
 int graph_env_reserve(pg_graph* g, size_t n);          // mutating calls, graph quiescent: may allocate
+int graph_env_head_refresh(pg_graph* g);               // ... the table's header again, behind a change of a table it names
 void graph_sampler_release(pg_graph* g);
 void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel
 int graph_gran_upload_live(pg_graph* g, hipStream_t stream);

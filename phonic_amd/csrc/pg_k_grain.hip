@@ -91,6 +91,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   const float* const pcm = V->pcm;
   const uint64_t len = V->n_frames;
   float* const staged = V->staged + stage_off * 2;
+  float* const pos_trace = V->pos_trace ? V->pos_trace + stage_off : nullptr;   // playback status: the playhead behind every frame (PgGrainVoice::pos_trace)
   const int window = V->params.window & (PG_GRAIN_WINDOWS - 1);
 
   for (int i = tid; i < PG_GRAIN_LUT_N; i += 256) s_lut[i] = L.lut[window * PG_GRAIN_LUT_N + i];
@@ -241,6 +242,8 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
         else grain_sched_frame<false>(S, s_end, f, a, m);
         if (a.slot >= 0) { s_act[f] = a; s_touched[a.slot] = 1; }
         else s_act[f].slot = -1;
+        // GrainPool::playback_position(parameters, pos_mod) as a process call that ends behind this frame finds it (voice.rs:434-453)
+        if (pos_trace) pos_trace[lf] = has_mod ? grain_playback_position<true>(S, m.position()) : grain_playback_position<false>(S, 0.0f);
         if (!S.pool.trigger_new_grains && exhausted_at == UINT64_MAX) {
           if (max_end < 0) { max_end = 0; for (int s = 0; s < PG_GRAIN_POOL; ++s) max_end = s_end[s] > max_end ? s_end[s] : max_end; }
           if (max_end <= f + 1) exhausted_at = t;   // nothing is active behind this frame and nothing will be triggered: is_exhausted (:442-444)

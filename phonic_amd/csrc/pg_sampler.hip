@@ -40,12 +40,19 @@ void graph_sampler_poll(pg_graph* g) {
 }
 
 // The header of envelope table `tab` — its words, its grain_of_voice list, the granular records as the graph holds them now (the graph is quiescent)
-static hipError_t env_head_upload(const pg_graph* g, PgEnvTable* tab, const MappedWords& done, const int32_t* grain_of_voice) {
+static hipError_t env_head_upload(const pg_graph* g, PgEnvTable* tab, const MappedWords& done, const int32_t* grain_of_voice, const int32_t* stat_of_voice) {
   PgEnvTable head;
   memset(&head, 0, sizeof head);
   head.done = done.d; head.cap = done.cap;
   head.grain_of_voice = grain_of_voice; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
+  head.stat_of_voice = stat_of_voice; head.stats = g->pstat.d_recs; head.n_stats = (uint32_t)g->pstat.n_recs;   // (playback status: pg_k_status.hip)
   return pg_memcpy(tab, &head, sizeof head, hipMemcpyHostToDevice);
+}
+// The header again, for the tables as the graph holds them now (a table behind it grew: pg_k_status.hip). The graph is quiescent.
+int graph_env_head_refresh(pg_graph* g) {
+  if (!g->d_env_tab) return PG_OK;
+  HIP_TRY(env_head_upload(g, g->d_env_tab, g->env_done, g->d_grain_of_voice, g->pstat.d_of_voice));
+  return PG_OK;
 }
 // The envelope side table and its `ended` words for `n` voices (grow-by-doubling; the graph is quiescent: nothing in flight reads the old ones).
 int graph_env_reserve(pg_graph* g, size_t n) {
@@ -53,20 +60,24 @@ int graph_env_reserve(pg_graph* g, size_t n) {
   const size_t cap = std::max<size_t>(next_pow2(n), 64), bytes = sizeof(PgEnvTable) + cap * sizeof(PgEnv);
   PgEnvTable* nt = nullptr;
   int32_t* ngv = nullptr;   // PgEnvTable::grain_of_voice: -1 for every voice that is not granular
+  int32_t* nsv = nullptr;   // PgEnvTable::stat_of_voice: -1 for every voice that reports no playback status
   MappedWords done;
   HIP_TRY(pg_malloc((void**)&nt, bytes));
   PgEnv* const nd = (PgEnv*)(nt + 1);
-  auto fail = [&](const char* what) { (void)pg_free(nt); if (ngv) (void)pg_free(ngv); done.release(); return set_error(PG_ERR_DEVICE, "envelope table %s failed", what); };
+  auto fail = [&](const char* what) { (void)pg_free(nt); if (ngv) (void)pg_free(ngv); if (nsv) (void)pg_free(nsv); done.release(); return set_error(PG_ERR_DEVICE, "envelope table %s failed", what); };
   if (pg_memset(nt, 0, bytes) != hipSuccess || done.reserve(cap, g->env_done) || pg_malloc((void**)&ngv, cap * sizeof(int32_t)) != hipSuccess ||
-      pg_memset(ngv, 0xff, cap * sizeof(int32_t)) != hipSuccess) return fail("allocation");
-  if (env_head_upload(g, nt, done, ngv) != hipSuccess) return fail("upload");
+      pg_memset(ngv, 0xff, cap * sizeof(int32_t)) != hipSuccess || pg_malloc((void**)&nsv, cap * sizeof(int32_t)) != hipSuccess ||
+      pg_memset(nsv, 0xff, cap * sizeof(int32_t)) != hipSuccess) return fail("allocation");
+  if (env_head_upload(g, nt, done, ngv, nsv) != hipSuccess) return fail("upload");
   if (g->d_env && (pg_memcpy(nd, g->d_env, g->env_done.cap * sizeof(PgEnv), hipMemcpyDeviceToDevice) != hipSuccess ||
-                   pg_memcpy(ngv, g->d_grain_of_voice, g->env_done.cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess)) return fail("copy");
+                   pg_memcpy(ngv, g->d_grain_of_voice, g->env_done.cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
+                   pg_memcpy(nsv, g->pstat.d_of_voice, g->env_done.cap * sizeof(int32_t), hipMemcpyDeviceToDevice) != hipSuccess)) return fail("copy");
   // (the new table is complete: let go of the old one and swap — a failure above leaves the graph on its old table)
   if (g->d_env_tab) (void)pg_free(g->d_env_tab);
   if (g->d_grain_of_voice) (void)pg_free(g->d_grain_of_voice);
+  if (g->pstat.d_of_voice) (void)pg_free(g->pstat.d_of_voice);
   g->env_done.release();
-  g->d_env_tab = nt; g->d_env = nd; g->env_done = done; g->d_grain_of_voice = ngv;
+  g->d_env_tab = nt; g->d_env = nd; g->env_done = done; g->d_grain_of_voice = ngv; g->pstat.d_of_voice = nsv;
   return PG_OK;
 }
 // Room for `n` granular records, their `ended` words and their launch list; the window tables with the first one. The graph is quiescent.
@@ -122,7 +133,7 @@ void graph_sampler_release(pg_graph* g) {
 // note_on belongs to a voice's start (voice.rs:181-184): neither an envelope nor a matrix for a voice that has rendered frames already.
 // A voice renders in every write that ends behind its start time — a start time at or before a write's position starts it at once,
 // voice_process — so it has rendered iff a write issued since it was added ended behind its start time, wherever the earlier ones stood.
-static bool voice_has_rendered(const pg_graph* g, const HostVoice& hv) {
+bool voice_has_rendered(const pg_graph* g, const HostVoice& hv) {
   for (const auto& w : g->write_end_max) if (w.first > hv.added_at_write) return w.second > hv.start_time;
   return false;
 }
@@ -293,8 +304,10 @@ static int graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono
       pg_memcpy(g->d_grain_of_voice + dev_index, &rec, sizeof rec, hipMemcpyHostToDevice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
   g->gran_ended[(size_t)rec] = 0;
   g->gran_n += 1;
-  if (env_head_upload(g, g->d_env_tab, g->env_done, g->d_grain_of_voice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
+  if (env_head_upload(g, g->d_env_tab, g->env_done, g->d_grain_of_voice, g->pstat.d_of_voice) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice upload failed")); }
   hv.gran = rec; hv.gran_live = true;
+  if (sbuf >= 0) { const SampleBuffer& b = g->sample_buffers[sbuf]; hv.file_channels = b.channels; hv.file_rate = b.rate; hv.file_samples = (uint64_t)b.n_frames * b.channels; }
+  else { hv.file_channels = 1; hv.file_rate = g->sample_rate; hv.file_samples = n_frames; }
   if (sbuf >= 0) { hv.sbuf = sbuf; g->sample_buffers[sbuf].use_count += 1; }   // (nothing fails behind this that would release the voice)
   return graph_register_voice(g, mixer_id, dev_index, opt, hv, VOICE_GRANULAR);
 }

@@ -163,6 +163,12 @@ struct pg_sharded_graph {
   // voice that uses it is placed there
   struct SampleBuf { std::vector<float> pcm; size_t n_frames = 0; pg_sample_buffer_desc desc; std::vector<int> local; bool held = true; };
   std::vector<SampleBuf> sample_buffers;
+  // playback status (pg_sharded_poll_status): a shard's ids back to the handle's, and every voice's start time — what puts the records of
+  // several shards into the one mixer's order; brought up to date from the id maps when a poll needs them
+  std::vector<std::vector<int>> rev_voice, rev_mixer;   // [shard][local id] -> global id (-1: none)
+  std::vector<uint64_t> voice_start;                    // [global voice id]
+  size_t noted_voices = 0, noted_mixers = 0;
+  std::vector<pgs::StatusRing*> status_rings;           // the shards' rings (pg_sharded_enable_status): what a poll merges
 };
 static inline int shard_of(int32_t packed) { return (int)((uint32_t)packed >> 24); }
 static inline int local_of(int32_t packed) { return (int)((uint32_t)packed & 0xffffffu); }
@@ -637,6 +643,75 @@ int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_lev
   if (mixer_id < 0 || (size_t)mixer_id >= s->mixer_map.size()) return set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
   const int32_t pk = s->mixer_map.get((size_t)mixer_id);
   return pg_graph_mixer_audio_level(s->shards[shard_of(pk)], local_of(pk), out);
+}
+// pg_graph_enable_status / _set_voice_status / _poll_status / _status_dropped on the one mixer (src/source/status.rs, src/source/file/common.rs:171-221):
+// every shard decides the records of its voices and keeps a ring of `capacity_events` of its own; a poll merges the shards' rings into the
+// order of pg_graph_poll_status — by sample_time, then as the one main mixer's write reaches the voices: its sub-mixers in the order they were
+// added (each with everything under it: one shard), then its sources in its list's order (sorted by start time, a new source in front of those
+// that start at the same time, mixed.rs:324-329) — and hands out the handle's voice ids. The dropped count is the shards' sum.
+int pg_sharded_enable_status(pg_sharded_graph* s, size_t capacity_events) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (capacity_events == 0) return set_error(PG_ERR_PARAMETER, "the status ring needs room for one record at least");
+  for (pg_graph* g : s->shards) if (g->pstat.on) return set_error(PG_ERR_STATE, "playback status is enabled already");
+  for (size_t i = 0; i < s->shards.size(); ++i) {
+    const int rc = pg_graph_enable_status(s->shards[i], capacity_events);
+    if (rc) { for (size_t k = 0; k < i; ++k) s->shards[k]->pstat.on = false; return rc; }   // (all shards or none: the call may be made again)
+  }
+  s->status_rings.clear();
+  for (pg_graph* g : s->shards) s->status_rings.push_back(&g->pstat.ring);
+  return PG_OK;
+}
+int pg_sharded_set_voice_status(pg_sharded_graph* s, int voice_id, double position_emit_seconds, int report_stopped) {
+  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (std::isnan(position_emit_seconds)) return set_error(PG_ERR_PARAMETER, "Invalid position emit rate: %g", position_emit_seconds);
+  SHARDED_VOICE(s, voice_id, pk);
+  return pg_graph_set_voice_status(s->shards[shard_of(pk)], local_of(pk), position_emit_seconds, report_stopped);
+}
+static void sharded_status_note_ids(pg_sharded_graph* s) {
+  const size_t n = s->shards.size();
+  s->rev_voice.resize(n); s->rev_mixer.resize(n);
+  for (; s->noted_mixers < s->mixer_map.size(); ++s->noted_mixers) {
+    if (s->noted_mixers == 0) continue;   // (the main mixer is every shard's mixer 0)
+    const int32_t pk = s->mixer_map.get(s->noted_mixers);
+    std::vector<int>& rv = s->rev_mixer[(size_t)shard_of(pk)];
+    if (rv.size() <= (size_t)local_of(pk)) rv.resize((size_t)local_of(pk) + 1, -1);
+    rv[(size_t)local_of(pk)] = (int)s->noted_mixers;
+  }
+  for (; s->noted_voices < s->voice_map.size(); ++s->noted_voices) {
+    const int32_t pk = s->voice_map.get(s->noted_voices);
+    std::vector<int>& rv = s->rev_voice[(size_t)shard_of(pk)];
+    if (rv.size() <= (size_t)local_of(pk)) rv.resize((size_t)local_of(pk) + 1, -1);
+    rv[(size_t)local_of(pk)] = (int)s->noted_voices;
+    const pg_graph* g = s->shards[(size_t)shard_of(pk)];
+    s->voice_start.push_back((size_t)local_of(pk) < g->voices.size() ? g->voices[(size_t)local_of(pk)].start_time : 0);
+  }
+}
+int pg_sharded_poll_status(pg_sharded_graph* s, pg_status_event* out, size_t max_events) {
+  if (!s || (!out && max_events)) return 0;
+  if (s->status_rings.size() != s->shards.size()) return 0;   // (not enabled)
+  sharded_status_note_ids(s);   // (grows the id maps by what was added since the last poll: nothing when nothing was)
+  for (pg_graph* g : s->shards) graph_pstat_collect(g, false);
+  struct Key { uint64_t group, a, b; bool operator<(const Key& o) const { return group != o.group ? group < o.group : (a != o.a ? a < o.a : b < o.b); } };
+  auto global_voice = [&](size_t shard, int local) { return local >= 0 && (size_t)local < s->rev_voice[shard].size() ? s->rev_voice[shard][(size_t)local] : -1; };
+  auto key = [&](size_t shard, const pgs::StatusRec& r) {
+    Key k;
+    if (r.top > 0) {  // under a sub-mixer of the main mixer: the sub-mixers in the order they were added, then the shard's own walk below it
+      const int gm = (size_t)r.top < s->rev_mixer[shard].size() ? s->rev_mixer[shard][(size_t)r.top] : -1;
+      k.group = gm >= 0 ? (uint64_t)gm : 0x7fffffffull; k.a = r.rank; k.b = 0;
+    } else {          // a source of the main mixer: by start time, the one added later first
+      const int gv = global_voice(shard, r.ev.voice_id);
+      k.group = UINT64_MAX; k.a = gv >= 0 ? s->voice_start[(size_t)gv] : UINT64_MAX; k.b = gv >= 0 ? (uint64_t)(0x7fffffff - gv) : UINT64_MAX;
+    }
+    return k;
+  };
+  auto remap = [&](size_t shard, const pgs::StatusRec& r) { pg_status_event e = r.ev; e.voice_id = global_voice(shard, r.ev.voice_id); return e; };
+  return (int)pgs::status_merge(s->status_rings.data(), s->status_rings.size(), key, remap, out, std::min<size_t>(max_events, 0x7fffffffu));
+}
+uint64_t pg_sharded_status_dropped(pg_sharded_graph* s) {
+  if (!s) return 0;
+  uint64_t n = 0;
+  for (pg_graph* g : s->shards) n += pg_graph_status_dropped(g);
+  return n;
 }
 int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id) {
   if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return 0;

@@ -1178,7 +1178,8 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
 template <bool GLIDE, int ADAPTERS = 2, bool ENV = false>
 DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp, int frames, uint64_t pos, const SrcScratch& S0,
                        const PgSchedEntry* sched, int sched_bank, bool have_word = false, uint32_t word = 0, uint64_t call_end = 0, bool chunk_first = true,
-                       uint64_t chunk_end = 0, bool in_lds = false, PgEnv* env = nullptr, int32_t* env_done = nullptr, const PgGrainVoice* gr = nullptr) {
+                       uint64_t chunk_end = 0, bool in_lds = false, PgEnv* env = nullptr, int32_t* env_done = nullptr, const PgGrainVoice* gr = nullptr,
+                       PgStatVoice* sv = nullptr, uint32_t round = 0) {
   SrcScratch S = S0;
   const int tid = pg_tid(), nt = blockDim.x;
   static_assert(sizeof(PgVoice) / 4 <= 256, "one dword per lane");
@@ -1192,6 +1193,8 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
   __syncthreads();
   S.sched_rd = (sched && lv->sched_class >= 0) ? sched + (size_t)lv->sched_class * 2 + sched_bank : nullptr;
   PG_STAMP(S.diag, 16);
+  // playback status (the exact kernel only): this launch's source writes of the voice are logged — pg_playback_status_kernel takes them from there
+  if (ENV && sv != nullptr && tid == 0) sv->log_round = round;
   // A source that broke out of its chunk's loop (nothing written, or exhausted: mixed.rs:612-620) is left alone until the mixer's next chunk
   const bool skip = lv->chunk_skip != 0 && !chunk_first;
   if (lv->chunk_skip != 0 && chunk_first) { __syncthreads(); if (tid == 0) { lv->chunk_skip = 0; gv->chunk_skip = 0; } __syncthreads(); }
@@ -1223,7 +1226,7 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
     if (samples_until_stop == 0) {
       pending_stop = 1;
       __syncthreads();
-      if (tid == 0) lv->has_stop = 0;
+      if (tid == 0) { lv->has_stop = 0; lv->stop_pos_lo = (uint32_t)lv->playback_pos; lv->stop_pos_hi = (uint32_t)(lv->playback_pos >> 32); }   // (the write in front of the stop has returned: where it left the file)
       samples_until_stop = PG_USIZE_MAX;
     }
     uint64_t remaining = (uint64_t)(out_len - total_written);
@@ -1232,6 +1235,11 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
     // (a call that reaches the end of this piece without reaching a stop time or the end of the chunk goes on in the next piece)
     const bool ask_ends = pos + (uint64_t)frames >= chunk_end || samples_until_stop <= (uint64_t)(out_len - total_written);
     int added;
+    if (ENV && sv != nullptr && tid == 0 && !sv->open) {  // a source write begins here (one that goes on from an earlier launch of the chunk keeps what it began with)
+      const int killed = pending_stop && !lv->finished && gr == nullptr && !(lv->fade_out_seconds > 0.0f);   // preloaded.rs:196-208
+      sv->open = 1; sv->open_time = source_time;
+      sv->open_flags = (lv->finished ? PG_SW_SKIPPED : 0) | (killed ? PG_SW_KILLED : 0) | (lv->pos_eof ? PG_SW_EOF_BEFORE : 0);
+    }
     int written = voice_write<GLIDE, ADAPTERS, ENV>(lv, tmp, to_write / 2, pending_stop, S, sig + total_written, &added, ask_ends, env, gr, source_time);
     if (!added) for (int i = tid; i < written; i += nt) sig[total_written + i] = sig[total_written + i] + tmp[i];  // add_buffers
     __syncthreads();
@@ -1243,6 +1251,22 @@ DEVO int voice_process(PgVoice* gv, PgVoice* lv /*LDS*/, float* sig, float* tmp,
       // the call filled this piece and goes on in the chunk's next one: the mixer looks at the source (is_exhausted, written == 0) when the
       // call returns, not here — a ResampledSource whose staging buffers happen to be empty at this frame refills them inside the same call
     } else {
+      if (ENV && sv != nullptr && tid == 0) {  // the source write has returned: what it left, for the status kernel behind this launch
+        uint64_t sample_pos = lv->playback_pos;
+        if (gr != nullptr) {  // (GrainPool::playback_position * buffer.len() as f32) as u64 behind the write's last frame (voice.rs:449-466)
+          const uint64_t last = source_time + (uint64_t)(written / 2) - gr->stage_pos - 1;
+          const float ph = (gr->pos_trace != nullptr && written > 0 && source_time >= gr->stage_pos && last < (uint64_t)PG_MAX_FRAMES) ? gr->pos_trace[last] : 0.0f;
+          sample_pos = f2u64(ph * (float)sv->buffer_len);
+        }
+        const int n = sv->n_log;
+        if (n < PG_STAT_LOG) {
+          PgStatWrite w;
+          w.time = sv->open_time; w.pos = sample_pos; w.pad = 0;
+          w.flags = sv->open_flags | (lv->pos_eof ? PG_SW_EOF : 0) | (lv->finished ? PG_SW_FINISHED : 0);
+          sv->log[n] = w; sv->n_log = n + 1;
+        } else sv->lost += 1;
+        sv->open = 0;
+      }
       // an enveloped voice that is finished — its envelope went Idle, or its file ran out — is finished for good (seeks leave a finished source
       // alone): the host takes the unit off this kernel, also for a source the mixer keeps in its list (non_transient)
       if (ENV && env != nullptr && env_done != nullptr && exhausted && tid == 0) { *(volatile int32_t*)env_done = 1; __threadfence_system(); }

@@ -620,8 +620,14 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
           const int gi = envs->grain_of_voice[gv - L.voices];
           if (gi >= 0 && (uint32_t)gi < envs->n_grains) gr = envs->grains + gi;
         }
+        // (playback status: the record of a voice that reports sits behind the same table; this kernel logs its source writes there)
+        PgStatVoice* sv = nullptr;
+        if (!FAST_ONLY && envs && envs->stat_of_voice && (uint64_t)(gv - L.voices) < envs->cap) {
+          const int si_ = envs->stat_of_voice[gv - L.voices];
+          if (si_ >= 0 && (uint32_t)si_ < envs->n_stats) sv = envs->stats + si_;
+        }
         const int r = voice_process<!FAST_ONLY, (FAST_ONLY && KMASK == (0x7ff & ~((1 << 5) | (1 << 7)))) ? 1 : 2, !FAST_ONLY>(gv, lv, sseg, tmp, seg, pos, S, L.sched, L.sched_bank, tables && vi == 0, voice_word, call_end_pos, seg_first, seg_chunk_end,
-                                                                                                                      resident && vi == 0, env, (!FAST_ONLY && env) ? envs->done + (gv - L.voices) : nullptr, gr);
+                                                                                                                      resident && vi == 0, env, (!FAST_ONLY && env) ? envs->done + (gv - L.voices) : nullptr, gr, sv, L.round);
         audible_input |= (r & 1) != 0;
         later |= r & 2;
       }

@@ -324,6 +324,22 @@ class ShardedGraph:
         self._check(self._lib.pg_sharded_mixer_audio_level(self._h, mixer_id, C.byref(raw)))
         return _capi.Level(raw)
 
+    def enable_status(self, capacity_events=4096):
+        """Playback status events on every shard (each keeps a ring of `capacity_events` records); once, before the first write."""
+        self._check(self._lib.pg_sharded_enable_status(self._h, capacity_events))
+
+    def set_voice_status(self, voice, position_emit_seconds=None, report_stopped=True):
+        self._check(self._lib.pg_sharded_set_voice_status(self._h, voice, -1.0 if position_emit_seconds is None else float(position_emit_seconds), 1 if report_stopped else 0))
+
+    def poll_status(self, max_events=4096):
+        """The shards' records merged into the one mixer's order, voice ids the handle's (_capi.status_tuple tuples)."""
+        buf = (_capi.StatusEvent * max_events)()
+        n = int(self._lib.pg_sharded_poll_status(self._h, buf, max_events))
+        return [_capi.status_tuple(buf[i]) for i in range(n)]
+
+    def status_dropped(self):
+        return int(self._lib.pg_sharded_status_dropped(self._h))
+
     def set_voice_speed(self, voice, speed, sample_time, glide=None):
         self._check(self._lib.pg_sharded_set_voice_speed(self._h, voice, float(speed), float(glide) if glide else 0.0, sample_time))
 
