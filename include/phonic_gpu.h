@@ -679,7 +679,9 @@ int pg_graph_synchronize(pg_graph* g);
  * mixer would (mixed.rs:679-712); the bus chain gets one `audible_input` per chunk, OR-ed over the shards (mixed.rs:696-706); write
  * returns 0 exactly when pg_graph_write would (mixed.rs:664-670). Threading as for pg_graph: add_* / remove_* / move_* / write from the
  * owner thread, the control calls (schedule_*, set_voice_*, seek, stop_*) from any thread. A device may be listed more than once
- * (several shards on one GPU: how the single-GPU test-suite exercises this path; not with PG_REDUCE_RCCL). bench.py's measured multi-GPU
+ * (several shards on one GPU: how the single-GPU test-suite exercises this path; not with PG_REDUCE_RCCL). Every call that takes the handle
+ * answers a null one with PG_ERR_PARAMETER in its own way of reporting an error ("graph handle is null"; pg_sharded_destroy does nothing),
+ * behind the argument checks that need no graph. bench.py's measured multi-GPU
  * path is one process per GPU with an RCCL reduce through torch.distributed (phonic_amd/parallel.py); both sit on the same kernels and
  * per-graph host code. */
 typedef struct pg_sharded_graph pg_sharded_graph;

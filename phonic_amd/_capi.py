@@ -362,42 +362,159 @@ def default_voice_options(**kw):
     return o
 
 
-def declare(lib, prefix):
-    """Declare argtypes/restypes of the API shared by the product (pg_) and, in tests, the oracle (po_)."""
-    P = C.POINTER
-    f = lambda name: getattr(lib, prefix + name)
-    vp = C.c_void_p
-    sigs = {
-        "effect_initialize": (C.c_int, [vp, C.c_uint32, C.c_size_t, C.c_size_t]),
-        "effect_process": (C.c_int, [vp, P(C.c_float), C.c_size_t, C.c_uint64]),
-        "effect_tail": (C.c_int64, [vp]),
-        "effect_set_parameter": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_int]),
-        "effect_message_reset": (C.c_int, [vp]),
-        "effect_destroy": (None, [vp]),
-        "graph_create": (vp, [C.c_uint32, C.c_uint32, C.c_size_t, C.c_int]),
-        "graph_destroy": (None, [vp]),
-        "graph_add_mixer": (C.c_int, [vp]),
-        "graph_add_mixer_to": (C.c_int, [vp, C.c_int]),
-        "graph_add_effect": (C.c_int, [vp, C.c_int, C.c_int, P(EffectInit)]),
-        "graph_add_voice": (C.c_int, [vp, C.c_int, P(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32, P(VoiceOptions)]),
-        "graph_schedule_param": (C.c_int, [vp, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64]),
-        "graph_schedule_reset": (C.c_int, [vp, C.c_int, C.c_uint64]),
-        "graph_remove_effect": (C.c_int, [vp, C.c_int]),
-        "graph_remove_mixer": (C.c_int, [vp, C.c_int]),
-        "graph_stop_all_voices": (C.c_int, [vp]),
-        "graph_move_effect": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
-        "graph_set_voice_volume": (C.c_int, [vp, C.c_int, C.c_float, C.c_uint64]),
-        "graph_set_voice_panning": (C.c_int, [vp, C.c_int, C.c_float, C.c_uint64]),
-        "graph_stop_voice": (C.c_int, [vp, C.c_int, C.c_uint64]),
-        "graph_remove_voice": (C.c_int, [vp, C.c_int]),
-        "graph_set_voice_speed": (C.c_int, [vp, C.c_int, C.c_double, C.c_float, C.c_uint64]),
-        "graph_seek_voice": (C.c_int, [vp, C.c_int, C.c_double, C.c_uint64]),
-        "graph_write": (C.c_size_t, [vp, P(C.c_float), C.c_size_t, C.c_uint64]),
-    }
-    for name, (res, args) in sigs.items():
-        fn = f(name)
+_P, _vp, _int, _u32, _u64, _sz, _f32, _f64 = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float, C.c_double
+
+# `dyn Effect`: (name behind "<prefix>effect_", restype, argument types behind the handle)
+EFFECT_CALLS = (
+    ("initialize", _int, [_u32, _sz, _sz]),
+    ("process", _int, [_P(_f32), _sz, _u64]),
+    ("tail", C.c_int64, []),
+    ("set_parameter", _int, [_u32, _f32, _int]),
+    ("message_reset", _int, []),
+    ("destroy", None, []),
+)
+
+# The main mixer's calls, the same on every handle: (name, restype, argument types behind the handle) of pg_graph_<name> and pg_sharded_<name>
+# (and, through declare(), of the test oracle's graph calls of the same names, for the ones it has). A call that exists on both handles is
+# declared here and nowhere else.
+MIXER_CALLS = (
+    ("add_mixer", _int, []),
+    ("add_mixer_to", _int, [_int]),
+    ("add_effect", _int, [_int, _int, _P(EffectInit)]),
+    ("add_voice", _int, [_int, _P(_f32), _sz, _u32, _u32, _P(VoiceOptions)]),
+    ("schedule_param", _int, [_int, _u32, _f32, _int, _u64]),
+    ("schedule_reset", _int, [_int, _u64]),
+    ("remove_effect", _int, [_int]),
+    ("remove_mixer", _int, [_int]),
+    ("stop_all_voices", _int, []),
+    ("move_effect", _int, [_int, _int, _int, _int]),
+    ("set_voice_volume", _int, [_int, _f32, _u64]),
+    ("set_voice_panning", _int, [_int, _f32, _u64]),
+    ("stop_voice", _int, [_int, _u64]),
+    ("remove_voice", _int, [_int]),
+    ("set_voice_speed", _int, [_int, _f64, _f32, _u64]),
+    ("seek_voice", _int, [_int, _f64, _u64]),
+    ("write", _sz, [_P(_f32), _sz, _u64]),
+    ("is_voice_playing", _int, [_int]),
+    ("synchronize", _int, []),
+    ("device_errors", _int, []),
+    ("set_max_blocks_per_launch", _int, [_int]),
+    # host-fed sources
+    ("add_stream_voice", _int, [_int, _u32, _u32, _sz, _P(VoiceOptions)]),
+    ("feed_voice", _int, [_int, _P(_f32), _sz]),
+    ("end_stream_voice", _int, [_int]),
+    ("stream_voice_consumed", C.c_int64, [_int]),
+    # envelopes
+    ("set_voice_envelope", _int, [_int, _P(AhdsrParams)]),
+    ("release_voice", _int, [_int, _u64]),
+    ("voice_envelope_stage", _int, [_int]),
+    # metering
+    ("set_metering", _int, [_f64]),
+    ("mixer_audio_level", _int, [_int, _P(AudioLevel)]),
+    # playback status
+    ("enable_status", _int, [_sz]),
+    ("set_voice_status", _int, [_int, _f64, _int]),
+    ("poll_status", _int, [_P(StatusEvent), _sz]),
+    ("status_dropped", _u64, []),
+    # granular voices, their parameters and their modulation matrix
+    ("add_granular_voice", _int, [_int, _P(_f32), _sz, _P(GranularParams), _P(VoiceOptions)]),
+    ("voice_grain_state", _int, [_int, _P(GrainState)]),
+    ("set_voice_granular_parameter", _int, [_int, _u32, _f32, _int, _u64]),
+    ("set_voice_grain_loop_range", _int, [_int, _int, _f32, _f32, _u64]),
+    ("voice_granular_params", _int, [_int, _P(GranularParams)]),
+    ("set_voice_modulation_matrix", _int, [_int, _P(ModulationParams)]),
+    ("set_voice_modulation", _int, [_int, _int, _int, _f32, _int, _u64]),
+    ("clear_voice_modulation", _int, [_int, _int, _int, _u64]),
+    ("set_voice_lfo_rate", _int, [_int, _int, _f32, _u64]),
+    ("set_voice_lfo_waveform", _int, [_int, _int, _int, _u64]),
+    ("voice_modulation_state", _int, [_int, _P(ModulationState)]),
+    # sample buffers (read_granular_buffer: below, the one call whose arguments differ between the handles)
+    ("add_sample_buffer", _int, [_P(_f32), _sz, _P(SampleBufferDesc)]),
+    ("release_sample_buffer", _int, [_int]),
+    ("add_voice_from_buffer", _int, [_int, _int, _P(VoiceOptions)]),
+    ("add_granular_voice_from_buffer", _int, [_int, _int, _P(GranularParams), _P(VoiceOptions)]),
+    ("prepare_granular_buffer", _int, [_int]),
+    ("sample_buffer_info", _int, [_int, _P(SampleBufferInfo)]),
+)
+
+# what only the plain graph has (argument types behind the handle)
+GRAPH_ONLY_CALLS = (
+    ("read_granular_buffer", C.c_int64, [_int, _P(_f32), _sz]),
+    ("write_device", _sz, [_vp, _sz, _u64, _vp]),
+    ("set_defer_bus", _int, [_int]),
+    ("process_bus_device", _int, [_vp, _sz, _u64, _vp]),
+    ("process_bus_device_flags", _int, [_vp, _sz, _u64, _vp, _vp, _int]),
+    ("export_audible", _int, [_vp, _int, _vp]),
+    ("audible_words", _int, []),
+    ("next_main_event", _u64, [_u64]),
+    ("voice_count", _int, []),
+    ("deferred_units", _int, []),
+    ("kernel_ms", _f64, [_int, _P(_u64)]),
+    ("kernel_stats", _int, [_int, _P(_f64), _P(_u64), _P(_u64)]),
+    ("bus_kernel_stats", _int, [_int, _P(_f64), _P(_u64), _P(_u64)]),
+    ("dynamic_stats", _int, [_int, _P(_u64), _P(_f64), _P(_u64)]),
+    ("bus_kernel", C.c_char_p, []),
+    ("dominant_kernel", C.c_char_p, []),
+    ("set_fast_math", _int, [_int]),
+    ("set_timing_period", _int, [_int]),
+    ("set_staged", _int, [_int]),
+)
+
+# what only the sharded handle has (pg_sharded_create and _destroy: in load)
+SHARDED_ONLY_CALLS = (
+    ("read_granular_buffer", C.c_int64, [_int, _int, _P(_f32), _sz]),   # (buffer, shard, out, capacity)
+    ("write_device", _sz, [_vp, _sz, _u64]),
+    ("shard_count", _int, []),
+    ("shard_of_mixer", _int, [_int]),
+    ("set_reduce", _int, [_int]),
+    ("reduce_mode", _int, []),
+)
+
+# calls without a handle: (full name, restype, argument types)
+PLAIN_CALLS = (
+    ("pg_last_error_message", C.c_char_p, []),
+    ("pg_device_count", _int, []),
+    ("pg_effect_create", _vp, [_int, _P(EffectInit), _int]),
+    ("pg_effect_debug_index_log", _int, [_vp, _P(C.c_int32), _sz]),
+    ("pg_effect_process_started", _int, [_vp]),
+    ("pg_effect_process_stopped", _int, [_vp]),
+    ("pg_effect_kind_name", C.c_char_p, [_int]),
+    ("pg_effect_kind_weight", _int, [_int]),
+    ("pg_effect_kind_param_count", _int, [_int]),
+    ("pg_effect_kind_param", _int, [_int, _int, _P(ParamDesc)]),
+    ("pg_voice_options_default", None, [_P(VoiceOptions)]),
+    ("pg_ahdsr_params_default", None, [_P(AhdsrParams)]),
+    ("pg_granular_params_default", None, [_P(GranularParams)]),
+    ("pg_granular_params_check", _int, [_P(GranularParams)]),
+    ("pg_granular_param_count", _int, []),
+    ("pg_granular_param", _int, [_int, _P(ParamDesc)]),
+    ("pg_modulation_params_default", None, [_P(ModulationParams)]),
+    ("pg_modulation_params_check", _int, [_P(ModulationParams)]),
+    ("pg_debug_sample_buffer_times", _int, [_vp, _int, _P(_f32)]),
+    ("pg_debug_fail_launch_round", None, [_int]),
+    ("pg_debug_hip_calls", None, [_P(_u64)]),
+    ("pg_sharded_create", _vp, [_u32, _u32, _sz, _P(_int), _int]),
+    ("pg_sharded_destroy", None, [_vp]),
+)
+
+
+def _declare(lib, prefix, calls, present_only=False):
+    for name, res, args in calls:
+        if present_only and not hasattr(lib, prefix + name):
+            continue
+        fn = getattr(lib, prefix + name)
         fn.restype = res
-        fn.argtypes = args
+        fn.argtypes = [_vp] + args
+
+
+def declare(lib, prefix):
+    """Declare argtypes/restypes of the API shared by the product (pg_) and, in tests, the oracle (po_): the effect handle, graph_create /
+    graph_destroy and the mixer's calls — all of them for the product, for the oracle the ones it has."""
+    _declare(lib, prefix + "effect_", EFFECT_CALLS)
+    create = getattr(lib, prefix + "graph_create")
+    create.restype, create.argtypes = _vp, [_u32, _u32, _sz, _int]
+    _declare(lib, prefix + "graph_", (("destroy", None, []),))
+    _declare(lib, prefix + "graph_", MIXER_CALLS, present_only=prefix != "pg_")
     return lib
 
 
@@ -481,180 +598,11 @@ def load():
     _preload_hip_runtime()
     lib = C.CDLL(path)
     declare(lib, "pg_")
-    P = C.POINTER
-    vp = C.c_void_p
-    lib.pg_last_error_message.restype = C.c_char_p
-    lib.pg_last_error_message.argtypes = []
-    lib.pg_device_count.restype = C.c_int
-    lib.pg_effect_create.restype = vp
-    lib.pg_effect_create.argtypes = [C.c_int, P(EffectInit), C.c_int]
-    lib.pg_effect_debug_index_log.restype = C.c_int
-    lib.pg_effect_debug_index_log.argtypes = [vp, P(C.c_int32), C.c_size_t]
-    lib.pg_effect_process_started.restype = C.c_int
-    lib.pg_effect_process_started.argtypes = [vp]
-    lib.pg_effect_process_stopped.restype = C.c_int
-    lib.pg_effect_process_stopped.argtypes = [vp]
-    lib.pg_effect_kind_name.restype = C.c_char_p
-    lib.pg_effect_kind_name.argtypes = [C.c_int]
-    lib.pg_effect_kind_weight.restype = C.c_int
-    lib.pg_effect_kind_weight.argtypes = [C.c_int]
-    lib.pg_effect_kind_param_count.restype = C.c_int
-    lib.pg_effect_kind_param_count.argtypes = [C.c_int]
-    lib.pg_effect_kind_param.restype = C.c_int
-    lib.pg_effect_kind_param.argtypes = [C.c_int, C.c_int, P(ParamDesc)]
-    lib.pg_voice_options_default.restype = None
-    lib.pg_voice_options_default.argtypes = [P(VoiceOptions)]
-    lib.pg_graph_write_device.restype = C.c_size_t
-    lib.pg_graph_write_device.argtypes = [vp, vp, C.c_size_t, C.c_uint64, vp]
-    lib.pg_graph_set_defer_bus.restype = C.c_int
-    lib.pg_graph_set_defer_bus.argtypes = [vp, C.c_int]
-    lib.pg_graph_process_bus_device.restype = C.c_int
-    lib.pg_graph_process_bus_device.argtypes = [vp, vp, C.c_size_t, C.c_uint64, vp]
-    lib.pg_graph_synchronize.restype = C.c_int
-    lib.pg_graph_synchronize.argtypes = [vp]
-    lib.pg_graph_voice_count.restype = C.c_int
-    lib.pg_graph_voice_count.argtypes = [vp]
-    lib.pg_graph_deferred_units.restype = C.c_int
-    lib.pg_graph_deferred_units.argtypes = [vp]
-    lib.pg_graph_is_voice_playing.restype = C.c_int
-    lib.pg_graph_is_voice_playing.argtypes = [vp, C.c_int]
-    lib.pg_ahdsr_params_default.restype = None
-    lib.pg_ahdsr_params_default.argtypes = [P(AhdsrParams)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        for name, args in (("set_voice_envelope", [C.c_int, P(AhdsrParams)]), ("release_voice", [C.c_int, C.c_uint64]), ("voice_envelope_stage", [C.c_int])):
-            fn = getattr(lib, prefix + name)
-            fn.restype = C.c_int
-            fn.argtypes = [vp] + args
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        fn = getattr(lib, prefix + "set_metering")
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_double]
-        fn = getattr(lib, prefix + "mixer_audio_level")
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int, P(AudioLevel)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        for name, res, args in (("enable_status", C.c_int, [C.c_size_t]), ("set_voice_status", C.c_int, [C.c_int, C.c_double, C.c_int]),
-                                ("poll_status", C.c_int, [P(StatusEvent), C.c_size_t]), ("status_dropped", C.c_uint64, [])):
-            fn = getattr(lib, prefix + name)
-            fn.restype = res
-            fn.argtypes = [vp] + args
-    lib.pg_granular_params_default.restype = None
-    lib.pg_granular_params_default.argtypes = [P(GranularParams)]
-    lib.pg_granular_params_check.restype = C.c_int
-    lib.pg_granular_params_check.argtypes = [P(GranularParams)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        fn = getattr(lib, prefix + "add_granular_voice")
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int, P(C.c_float), C.c_size_t, P(GranularParams), P(VoiceOptions)]
-        fn = getattr(lib, prefix + "voice_grain_state")
-        fn.restype = C.c_int
-        fn.argtypes = [vp, C.c_int, P(GrainState)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        for name, res, args in (("add_sample_buffer", C.c_int, [P(C.c_float), C.c_size_t, P(SampleBufferDesc)]),
-                                ("release_sample_buffer", C.c_int, [C.c_int]),
-                                ("add_voice_from_buffer", C.c_int, [C.c_int, C.c_int, P(VoiceOptions)]),
-                                ("add_granular_voice_from_buffer", C.c_int, [C.c_int, C.c_int, P(GranularParams), P(VoiceOptions)]),
-                                ("prepare_granular_buffer", C.c_int, [C.c_int]),
-                                ("sample_buffer_info", C.c_int, [C.c_int, P(SampleBufferInfo)]),
-                                ("read_granular_buffer", C.c_int64, [C.c_int] + ([C.c_int] if prefix == "pg_sharded_" else []) + [P(C.c_float), C.c_size_t])):
-            fn = getattr(lib, prefix + name)
-            fn.restype = res
-            fn.argtypes = [vp] + args
-    lib.pg_debug_sample_buffer_times.restype = C.c_int
-    lib.pg_debug_sample_buffer_times.argtypes = [vp, C.c_int, P(C.c_float)]
-    lib.pg_granular_param_count.restype = C.c_int
-    lib.pg_granular_param_count.argtypes = []
-    lib.pg_granular_param.restype = C.c_int
-    lib.pg_granular_param.argtypes = [C.c_int, P(ParamDesc)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        for name, args in (("set_voice_granular_parameter", [C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64]),
-                           ("set_voice_grain_loop_range", [C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64]),
-                           ("voice_granular_params", [C.c_int, P(GranularParams)])):
-            fn = getattr(lib, prefix + name)
-            fn.restype = C.c_int
-            fn.argtypes = [vp] + args
-    lib.pg_modulation_params_default.restype = None
-    lib.pg_modulation_params_default.argtypes = [P(ModulationParams)]
-    lib.pg_modulation_params_check.restype = C.c_int
-    lib.pg_modulation_params_check.argtypes = [P(ModulationParams)]
-    for prefix in ("pg_graph_", "pg_sharded_"):
-        for name, args in (("set_voice_modulation_matrix", [C.c_int, P(ModulationParams)]),
-                           ("set_voice_modulation", [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64]),
-                           ("clear_voice_modulation", [C.c_int, C.c_int, C.c_int, C.c_uint64]),
-                           ("set_voice_lfo_rate", [C.c_int, C.c_int, C.c_float, C.c_uint64]),
-                           ("set_voice_lfo_waveform", [C.c_int, C.c_int, C.c_int, C.c_uint64]),
-                           ("voice_modulation_state", [C.c_int, P(ModulationState)])):
-            fn = getattr(lib, prefix + name)
-            fn.restype = C.c_int
-            fn.argtypes = [vp] + args
-    lib.pg_graph_kernel_ms.restype = C.c_double
-    lib.pg_graph_kernel_ms.argtypes = [vp, C.c_int, P(C.c_uint64)]
-    lib.pg_graph_kernel_stats.restype = C.c_int
-    lib.pg_graph_kernel_stats.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_uint64), P(C.c_uint64)]
-    lib.pg_graph_export_audible.restype = C.c_int
-    lib.pg_graph_export_audible.argtypes = [vp, vp, C.c_int, vp]
-    lib.pg_graph_audible_words.restype = C.c_int
-    lib.pg_graph_audible_words.argtypes = [vp]
-    lib.pg_graph_next_main_event.restype = C.c_uint64
-    lib.pg_graph_next_main_event.argtypes = [vp, C.c_uint64]
-    lib.pg_graph_process_bus_device_flags.restype = C.c_int
-    lib.pg_graph_process_bus_device_flags.argtypes = [vp, vp, C.c_size_t, C.c_uint64, vp, vp, C.c_int]
-    lib.pg_graph_dynamic_stats.restype = C.c_int
-    lib.pg_graph_dynamic_stats.argtypes = [vp, C.c_int, P(C.c_uint64), P(C.c_double), P(C.c_uint64)]
-    lib.pg_graph_bus_kernel_stats.restype = C.c_int
-    lib.pg_graph_bus_kernel_stats.argtypes = [vp, C.c_int, P(C.c_double), P(C.c_uint64), P(C.c_uint64)]
-    lib.pg_graph_bus_kernel.restype = C.c_char_p
-    lib.pg_graph_bus_kernel.argtypes = [vp]
-    lib.pg_graph_set_max_blocks_per_launch.restype = C.c_int
-    lib.pg_graph_set_max_blocks_per_launch.argtypes = [vp, C.c_int]
-    lib.pg_sharded_create.restype = vp
-    lib.pg_sharded_create.argtypes = [C.c_uint32, C.c_uint32, C.c_size_t, P(C.c_int), C.c_int]
-    lib.pg_sharded_destroy.restype = None
-    lib.pg_sharded_destroy.argtypes = [vp]
-    for name, args in (("shard_count", []), ("set_max_blocks_per_launch", [C.c_int]), ("add_mixer", []), ("add_mixer_to", [C.c_int]),
-                       ("add_effect", [C.c_int, C.c_int, P(EffectInit)]), ("add_voice", [C.c_int, P(C.c_float), C.c_size_t, C.c_uint32, C.c_uint32, P(VoiceOptions)]),
-                       ("shard_of_mixer", [C.c_int]), ("schedule_param", [C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64]), ("schedule_reset", [C.c_int, C.c_uint64]),
-                       ("set_voice_volume", [C.c_int, C.c_float, C.c_uint64]), ("set_voice_panning", [C.c_int, C.c_float, C.c_uint64]),
-                       ("set_voice_speed", [C.c_int, C.c_double, C.c_float, C.c_uint64]), ("seek_voice", [C.c_int, C.c_double, C.c_uint64]),
-                       ("remove_mixer", [C.c_int]), ("remove_effect", [C.c_int]), ("move_effect", [C.c_int, C.c_int, C.c_int, C.c_int]),
-                       ("set_reduce", [C.c_int]), ("reduce_mode", []), ("is_voice_playing", [C.c_int]),
-                       ("stop_voice", [C.c_int, C.c_uint64]), ("remove_voice", [C.c_int]), ("stop_all_voices", []), ("synchronize", []), ("device_errors", [])):
-        fn = getattr(lib, "pg_sharded_" + name)
-        fn.restype = C.c_int
-        fn.argtypes = [vp] + args
-    lib.pg_sharded_add_stream_voice.restype = C.c_int
-    lib.pg_sharded_add_stream_voice.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, P(VoiceOptions)]
-    lib.pg_sharded_feed_voice.restype = C.c_int
-    lib.pg_sharded_feed_voice.argtypes = [vp, C.c_int, P(C.c_float), C.c_size_t]
-    lib.pg_sharded_end_stream_voice.restype = C.c_int
-    lib.pg_sharded_end_stream_voice.argtypes = [vp, C.c_int]
-    lib.pg_sharded_stream_voice_consumed.restype = C.c_int64
-    lib.pg_sharded_stream_voice_consumed.argtypes = [vp, C.c_int]
-    lib.pg_sharded_write.restype = C.c_size_t
-    lib.pg_sharded_write.argtypes = [vp, P(C.c_float), C.c_size_t, C.c_uint64]
-    lib.pg_sharded_write_device.restype = C.c_size_t
-    lib.pg_sharded_write_device.argtypes = [vp, vp, C.c_size_t, C.c_uint64]
-    lib.pg_graph_add_stream_voice.restype = C.c_int
-    lib.pg_graph_add_stream_voice.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, C.c_size_t, P(VoiceOptions)]
-    lib.pg_graph_feed_voice.restype = C.c_int
-    lib.pg_graph_feed_voice.argtypes = [vp, C.c_int, P(C.c_float), C.c_size_t]
-    lib.pg_graph_end_stream_voice.restype = C.c_int
-    lib.pg_graph_end_stream_voice.argtypes = [vp, C.c_int]
-    lib.pg_graph_stream_voice_consumed.restype = C.c_int64
-    lib.pg_graph_stream_voice_consumed.argtypes = [vp, C.c_int]
-    lib.pg_debug_fail_launch_round.restype = None
-    lib.pg_debug_fail_launch_round.argtypes = [C.c_int]
-    lib.pg_debug_hip_calls.restype = None
-    lib.pg_debug_hip_calls.argtypes = [P(C.c_uint64)]
-    lib.pg_graph_device_errors.restype = C.c_int
-    lib.pg_graph_device_errors.argtypes = [vp]
-    lib.pg_graph_set_fast_math.restype = C.c_int
-    lib.pg_graph_set_fast_math.argtypes = [vp, C.c_int]
-    lib.pg_graph_set_timing_period.restype = C.c_int
-    lib.pg_graph_set_timing_period.argtypes = [vp, C.c_int]
-    lib.pg_graph_dominant_kernel.restype = C.c_char_p
-    lib.pg_graph_dominant_kernel.argtypes = [vp]
-    lib.pg_graph_set_staged.restype = C.c_int
-    lib.pg_graph_set_staged.argtypes = [vp, C.c_int]
+    _declare(lib, "pg_graph_", GRAPH_ONLY_CALLS)
+    _declare(lib, "pg_sharded_", MIXER_CALLS)
+    _declare(lib, "pg_sharded_", SHARDED_ONLY_CALLS)
+    for name, res, args in PLAIN_CALLS:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = res, args
     _LIB = lib
     return lib

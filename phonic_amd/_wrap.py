@@ -236,6 +236,31 @@ class GraphHandle:
         self._check(self._fn("graph_voice_modulation_state")(self._h, voice, C.byref(st)))
         return _capi.modulation_state_dict(st)
 
+    # ---- host-fed sources (any `dyn Source` the host pulls itself) ----
+    def add_stream_voice(self, mixer_id, channels, rate, capacity_frames, **opts):
+        o = _capi.default_voice_options(**opts)
+        v = self._id(self._fn("graph_add_stream_voice")(self._h, mixer_id, channels, rate, capacity_frames, C.byref(o)))
+        if not hasattr(self, "_stream_channels"):
+            self._stream_channels = {}
+        self._stream_channels[v] = channels
+        return v
+
+    def feed_voice(self, voice, frames):
+        """Interleaved float32 frames of the host's source; raises SendError (PG_ERR_QUEUE_FULL) when the ring has no room for all of them."""
+        frames = np.ascontiguousarray(frames, dtype=np.float32)
+        ch = self._stream_channels.get(voice) if hasattr(self, "_stream_channels") else None
+        n = frames.size // (ch or 1)
+        self._check(self._fn("graph_feed_voice")(self._h, voice, _f32p(frames), n))
+
+    def end_stream_voice(self, voice):
+        self._check(self._fn("graph_end_stream_voice")(self._h, voice))
+
+    def stream_voice_consumed(self, voice):
+        return self._id(self._fn("graph_stream_voice_consumed")(self._h, voice))
+
+    def is_voice_playing(self, voice):
+        return bool(self._fn("graph_is_voice_playing")(self._h, voice))
+
     def stop_all_voices(self):
         """Player::stop_all_sources (src/player.rs:1012-1045)."""
         self._check(self._fn("graph_stop_all_voices")(self._h))

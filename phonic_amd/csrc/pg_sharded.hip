@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <functional>
 #include <thread>
+#include <type_traits>
 
 #include <rccl/rccl.h>  // types and enums only: the entry points are looked up at run time (pg_sharded_set_reduce), the library does not link RCCL
 
@@ -197,6 +198,7 @@ static void sharded_drop_comms(pg_sharded_graph* s) {
   for (ncclComm_t c : s->comms) if (c && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(c);
   s->comms.clear();
 }
+static int sharded_null() { return set_error(PG_ERR_PARAMETER, "graph handle is null"); }   // every entry point's answer to a null handle, in its own way of reporting an error
 static int sharded_wait_all(pg_sharded_graph* s) {
   for (pg_graph* g : s->shards) { (void)hipSetDevice(g->device); HIP_TRY(pg_stream_sync(g->stream)); g->cmds_since_sync = 0; }
   return PG_OK;
@@ -278,8 +280,9 @@ void pg_sharded_destroy(pg_sharded_graph* s) {
   for (pg_graph* g : s->shards) pg_graph_destroy(g);
   delete s;
 }
-int pg_sharded_shard_count(pg_sharded_graph* s) { return (int)s->shards.size(); }
+int pg_sharded_shard_count(pg_sharded_graph* s) { return s ? (int)s->shards.size() : -sharded_null(); }
 int pg_sharded_set_max_blocks_per_launch(pg_sharded_graph* s, int n_blocks) {
+  if (!s) return sharded_null();
   { int rc = sharded_wait_all(s); if (rc) return rc; }
   for (pg_graph* g : s->shards) { int rc = pg_graph_set_max_blocks_per_launch(g, n_blocks); if (rc) return rc; }
   s->max_blocks = (size_t)n_blocks;
@@ -290,6 +293,7 @@ int pg_sharded_set_max_blocks_per_launch(pg_sharded_graph* s, int n_blocks) {
 // stays what it was; there is no silent fallback.
 int pg_sharded_set_reduce(pg_sharded_graph* s, int mode) {
   if (mode != PG_REDUCE_PEER_COPY && mode != PG_REDUCE_RCCL) return set_error(PG_ERR_PARAMETER, "unknown reduce mode %d", mode);
+  if (!s) return sharded_null();
   if (mode == s->reduce_mode) return PG_OK;
   { int rc = sharded_wait_all(s); if (rc) return rc; }
   if (mode == PG_REDUCE_PEER_COPY) { sharded_drop_comms(s); s->reduce_mode = mode; return PG_OK; }
@@ -305,77 +309,99 @@ int pg_sharded_set_reduce(pg_sharded_graph* s, int mode) {
   s->reduce_mode = mode;
   return PG_OK;
 }
-int pg_sharded_reduce_mode(pg_sharded_graph* s) { return s->reduce_mode; }
+int pg_sharded_reduce_mode(pg_sharded_graph* s) { return s ? s->reduce_mode : -sharded_null(); }
 
-static int sharded_least_loaded(const pg_sharded_graph* s) {
-  int best = 0;
-  for (size_t i = 1; i < s->load.size(); ++i) if (s->load[i] < s->load[best]) best = (int)i;
-  return best;
+}  // extern "C"
+
+// ---- routing: every call the plain graph takes, on the shard that owns its target --------------------------------------------------
+// A global id indexes one of the handle's append-only maps (shard << 24 | local id). One RESOLVER per id kind turns it into the owning
+// shard's graph and the id there, and is the one place that says "not found" for its kind; sharded_place is the one place that picks a
+// shard for something new and gives it a global id; sharded_forward is every call that does no more than resolve an id and call the
+// pg_graph_* function of the same name with the same trailing arguments. A null handle is PG_ERR_PARAMETER in the entry point's own way of
+// reporting an error (ErrorAs), behind the argument checks that need no graph.
+struct ShardTarget {
+  pg_graph* g = nullptr;   // null: no such id
+  int shard = 0, local = 0;
+};
+static ShardTarget sharded_unpack(pg_sharded_graph* s, int32_t packed) {
+  ShardTarget t;
+  t.shard = shard_of(packed); t.local = local_of(packed); t.g = s->shards[(size_t)t.shard];
+  return t;
 }
-static bool sharded_mixer(pg_sharded_graph* s, int mixer_id, int32_t& packed) {
-  if (mixer_id < 0 || (size_t)mixer_id >= s->mixer_map.size()) { set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id); return false; }
-  packed = s->mixer_map.get((size_t)mixer_id);
-  return true;
+static ShardTarget sharded_voice(pg_sharded_graph* s, int voice_id, bool quiet) {
+  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) { if (!quiet) set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id); return ShardTarget(); }
+  return sharded_unpack(s, s->voice_map.get((size_t)voice_id));
 }
-int pg_sharded_add_mixer_to(pg_sharded_graph* s, int parent_mixer_id) {
-  int32_t pk;
-  if (!sharded_mixer(s, parent_mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = parent_mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);  // a nested sub-mixer lives with its parent
-  const int local = pg_graph_add_mixer_to(s->shards[shard], parent_mixer_id == 0 ? 0 : local_of(pk));
+static ShardTarget sharded_fx(pg_sharded_graph* s, int effect_id, bool quiet) {
+  if (effect_id < 0 || (size_t)effect_id >= s->fx_map.size()) { if (!quiet) set_error(PG_ERR_NOT_FOUND, "Effect with id %d not found", effect_id); return ShardTarget(); }
+  return sharded_unpack(s, s->fx_map.get((size_t)effect_id));
+}
+static ShardTarget sharded_mixer(pg_sharded_graph* s, int mixer_id, bool quiet) {   // (mixer 0: the root's — its effect chain and its level live there)
+  if (mixer_id < 0 || (size_t)mixer_id >= s->mixer_map.size()) { if (!quiet) set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id); return ShardTarget(); }
+  return sharded_unpack(s, s->mixer_map.get((size_t)mixer_id));
+}
+
+// Something new under `mixer_id`: with its parent — or, for a sub-mixer or a source of the main mixer (`spread`), on the least loaded shard,
+// whose load it adds to. add(target) makes it on that shard's graph under target.local and returns its id there (< 0: -PG_ERR_*, passed on).
+// Returns the new global id in the map `ids`.
+template <class Add>
+static int sharded_place(pg_sharded_graph* s, int mixer_id, pgc::ChunkTable<int32_t> pg_sharded_graph::*ids, const char* what, bool spread, Add add) {
+  if (!s) return -sharded_null();
+  ShardTarget m = sharded_mixer(s, mixer_id, false);
+  if (!m.g) return -PG_ERR_NOT_FOUND;
+  const bool balance = spread && mixer_id == 0;
+  if (balance) {
+    for (size_t i = 1; i < s->load.size(); ++i) if (s->load[i] < s->load[(size_t)m.shard]) m.shard = (int)i;
+    m.g = s->shards[(size_t)m.shard];
+  }
+  const int local = add(m);
   if (local < 0) return local;
-  if (parent_mixer_id == 0) s->load[shard] += 1;
-  const int id = (int)s->mixer_map.size();
-  if (local > 0xffffff || !s->mixer_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many mixers");
+  if (balance) s->load[(size_t)m.shard] += 1;
+  pgc::ChunkTable<int32_t>& map = s->*ids;
+  const int id = (int)map.size();
+  if (local > 0xffffff || !map.append((int32_t)(((uint32_t)m.shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many %s", what);
   return id;
+}
+
+// How an entry point reports PG_ERR_* `code`: as it is; negated (the calls that return an id or a count); as -1 behind the message
+// (pg_sharded_stream_voice_consumed); as -1 or as 0 without touching the thread's error message (the plain read-outs)
+enum ErrorAs { AS_STATUS, AS_NEGATIVE, AS_MINUS_ONE, AS_QUIET_MINUS_ONE, AS_QUIET_ZERO };
+template <ErrorAs E, class R, class... A>
+static R sharded_forward(pg_sharded_graph* s, ShardTarget (*resolve)(pg_sharded_graph*, int, bool), int id, R (*fn)(pg_graph*, int, A...), std::common_type_t<A>... args) {
+  constexpr bool quiet = E == AS_QUIET_MINUS_ONE || E == AS_QUIET_ZERO;
+  auto fail = [](int code) -> R { return (R)(E == AS_STATUS ? code : E == AS_NEGATIVE ? -code : E == AS_QUIET_ZERO ? 0 : -1); };
+  if (!s) { if (!quiet) sharded_null(); return fail(PG_ERR_PARAMETER); }
+  const ShardTarget t = resolve(s, id, quiet);
+  if (!t.g) return fail(PG_ERR_NOT_FOUND);
+  return fn(t.g, t.local, args...);
+}
+
+extern "C" {
+
+int pg_sharded_add_mixer_to(pg_sharded_graph* s, int parent_mixer_id) {   // (a nested sub-mixer lives with its parent)
+  return sharded_place(s, parent_mixer_id, &pg_sharded_graph::mixer_map, "mixers", true, [](const ShardTarget& m) { return pg_graph_add_mixer_to(m.g, m.local); });
 }
 int pg_sharded_add_mixer(pg_sharded_graph* s) { return pg_sharded_add_mixer_to(s, 0); }
-int pg_sharded_add_effect(pg_sharded_graph* s, int mixer_id, int kind, const pg_effect_init* init) {
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? 0 : shard_of(pk);  // main-mixer effects: the bus chain on the root
-  const int local = pg_graph_add_effect(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), kind, init);
-  if (local < 0) return local;
-  const int id = (int)s->fx_map.size();
-  if (local > 0xffffff || !s->fx_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many effects");
-  return id;
+int pg_sharded_add_effect(pg_sharded_graph* s, int mixer_id, int kind, const pg_effect_init* init) {   // (main-mixer effects: the bus chain on the root, no load)
+  return sharded_place(s, mixer_id, &pg_sharded_graph::fx_map, "effects", false, [=](const ShardTarget& m) { return pg_graph_add_effect(m.g, m.local, kind, init); });
 }
 int pg_sharded_add_voice(pg_sharded_graph* s, int mixer_id, const float* pcm, size_t n_frames, uint32_t src_channels, uint32_t src_rate, const pg_voice_options* opt) {
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
-  const int local = pg_graph_add_voice(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), pcm, n_frames, src_channels, src_rate, opt);
-  if (local < 0) return local;
-  if (mixer_id == 0) s->load[shard] += 1;
-  const int id = (int)s->voice_map.size();
-  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
-  return id;
+  return sharded_place(s, mixer_id, &pg_sharded_graph::voice_map, "voices", true, [=](const ShardTarget& m) { return pg_graph_add_voice(m.g, m.local, pcm, n_frames, src_channels, src_rate, opt); });
 }
 // host-fed sources (pg_graph_add_stream_voice): placed like any other source, fed through the shard that owns them
 int pg_sharded_add_stream_voice(pg_sharded_graph* s, int mixer_id, uint32_t channels, uint32_t rate, size_t capacity_frames, const pg_voice_options* opt) {
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
-  const int local = pg_graph_add_stream_voice(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), channels, rate, capacity_frames, opt);
-  if (local < 0) return local;
-  if (mixer_id == 0) s->load[shard] += 1;
-  const int id = (int)s->voice_map.size();
-  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
-  return id;
+  return sharded_place(s, mixer_id, &pg_sharded_graph::voice_map, "voices", true, [=](const ShardTarget& m) { return pg_graph_add_stream_voice(m.g, m.local, channels, rate, capacity_frames, opt); });
 }
+int pg_sharded_feed_voice(pg_sharded_graph* s, int voice_id, const float* frames, size_t n_frames) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_feed_voice, frames, n_frames); }
+int pg_sharded_end_stream_voice(pg_sharded_graph* s, int voice_id) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_end_stream_voice); }
+int64_t pg_sharded_stream_voice_consumed(pg_sharded_graph* s, int voice_id) { return sharded_forward<AS_MINUS_ONE>(s, sharded_voice, voice_id, pg_graph_stream_voice_consumed); }
 // granular voices (pg_graph_add_granular_voice): placed like any other source; the shard that owns the voice runs its pg_grain_kernel
 int pg_sharded_add_granular_voice(pg_sharded_graph* s, int mixer_id, const float* mono_pcm, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
-  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }   // (before the id: parameter errors never depend on the graph)
-  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
-  const int local = pg_graph_add_granular_voice(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), mono_pcm, n_frames, p, opt);
-  if (local < 0) return local;
-  if (mixer_id == 0) s->load[shard] += 1;
-  const int id = (int)s->voice_map.size();
-  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
-  return id;
+  { const int rc = pg_granular_params_check(p); if (rc) return -rc; }   // (before the handle and the id: parameter errors never depend on the graph)
+  return sharded_place(s, mixer_id, &pg_sharded_graph::voice_map, "voices", true, [=](const ShardTarget& m) { return pg_graph_add_granular_voice(m.g, m.local, mono_pcm, n_frames, p, opt); });
 }
+int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_voice_grain_state, out); }
+
 // sample buffers: one host copy, one upload per shard that plays the buffer, one granular mono buffer per shard (the same one everywhere)
 static pg_sharded_graph::SampleBuf* sharded_sample_buffer(pg_sharded_graph* s, int buffer_id) {
   if (buffer_id < 0 || (size_t)buffer_id >= s->sample_buffers.size() || !s->sample_buffers[buffer_id].held) { set_error(PG_ERR_NOT_FOUND, "Sample buffer with id %d not found", buffer_id); return nullptr; }
@@ -385,23 +411,16 @@ static int sharded_buffer_on(pg_sharded_graph* s, pg_sharded_graph::SampleBuf& b
   if (b.local[shard] < 0) b.local[shard] = pg_graph_add_sample_buffer(s->shards[shard], b.pcm.data(), b.n_frames, &b.desc);
   return b.local[shard];
 }
-static int sharded_register_voice(pg_sharded_graph* s, int mixer_id, int shard, int local) {
-  if (local < 0) return local;
-  if (mixer_id == 0) s->load[shard] += 1;
-  const int id = (int)s->voice_map.size();
-  if (local > 0xffffff || !s->voice_map.append((int32_t)(((uint32_t)shard << 24) | (uint32_t)local))) return -set_error(PG_ERR_STATE, "too many voices");
-  return id;
-}
 int pg_sharded_add_sample_buffer(pg_sharded_graph* s, const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc) {
   { const int rc = sample_buffer_desc_check(pcm, n_frames, desc); if (rc) return -rc; }
-  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return -sharded_null();
   pg_sharded_graph::SampleBuf b;
   b.pcm.assign(pcm, pcm + n_frames * desc->channels); b.n_frames = n_frames; b.desc = *desc; b.local.assign(s->shards.size(), -1);
   s->sample_buffers.push_back(std::move(b));
   return (int)s->sample_buffers.size() - 1;
 }
 int pg_sharded_release_sample_buffer(pg_sharded_graph* s, int buffer_id) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
   if (!b) return PG_ERR_NOT_FOUND;
   int rc = PG_OK;
@@ -411,30 +430,26 @@ int pg_sharded_release_sample_buffer(pg_sharded_graph* s, int buffer_id) {
   return rc;
 }
 int pg_sharded_add_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_voice_options* opt) {
-  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return -sharded_null();
   pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
   if (!b) return -PG_ERR_NOT_FOUND;
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
-  const int lb = sharded_buffer_on(s, *b, shard);
-  if (lb < 0) return lb;
-  return sharded_register_voice(s, mixer_id, shard, pg_graph_add_voice_from_buffer(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), lb, opt));
+  return sharded_place(s, mixer_id, &pg_sharded_graph::voice_map, "voices", true, [=](const ShardTarget& m) {
+    const int lb = sharded_buffer_on(s, *b, m.shard);
+    return lb < 0 ? lb : pg_graph_add_voice_from_buffer(m.g, m.local, lb, opt);
+  });
 }
 int pg_sharded_add_granular_voice_from_buffer(pg_sharded_graph* s, int mixer_id, int buffer_id, const pg_granular_params* p, const pg_voice_options* opt) {
   { const int rc = pg_granular_params_check(p); if (rc) return -rc; }
-  if (!s) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return -sharded_null();
   pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
   if (!b) return -PG_ERR_NOT_FOUND;
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  const int shard = mixer_id == 0 ? sharded_least_loaded(s) : shard_of(pk);
-  const int lb = sharded_buffer_on(s, *b, shard);
-  if (lb < 0) return lb;
-  return sharded_register_voice(s, mixer_id, shard, pg_graph_add_granular_voice_from_buffer(s->shards[shard], mixer_id == 0 ? 0 : local_of(pk), lb, p, opt));
+  return sharded_place(s, mixer_id, &pg_sharded_graph::voice_map, "voices", true, [=](const ShardTarget& m) {
+    const int lb = sharded_buffer_on(s, *b, m.shard);
+    return lb < 0 ? lb : pg_graph_add_granular_voice_from_buffer(m.g, m.local, lb, p, opt);
+  });
 }
 int pg_sharded_prepare_granular_buffer(pg_sharded_graph* s, int buffer_id) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   pg_sharded_graph::SampleBuf* b = sharded_sample_buffer(s, buffer_id);
   if (!b) return PG_ERR_NOT_FOUND;
   bool any = false;
@@ -469,180 +484,107 @@ int64_t pg_sharded_read_granular_buffer(pg_sharded_graph* s, int buffer_id, int 
   if (lb < 0) return lb;
   return pg_graph_read_granular_buffer(s->shards[shard], lb, out, cap_frames);
 }
-int pg_sharded_voice_grain_state(pg_sharded_graph* s, int voice_id, pg_grain_state* out) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_voice_grain_state(s->shards[shard_of(pk)], local_of(pk), out);
-}
-int pg_sharded_feed_voice(pg_sharded_graph* s, int voice_id, const float* frames, size_t n_frames) {
-  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_feed_voice(s->shards[shard_of(pk)], local_of(pk), frames, n_frames);
-}
-int pg_sharded_end_stream_voice(pg_sharded_graph* s, int voice_id) {
-  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id);
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_end_stream_voice(s->shards[shard_of(pk)], local_of(pk));
-}
-int64_t pg_sharded_stream_voice_consumed(pg_sharded_graph* s, int voice_id) {
-  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) { set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", voice_id); return -1; }
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_stream_voice_consumed(s->shards[shard_of(pk)], local_of(pk));
-}
+
 int pg_sharded_shard_of_mixer(pg_sharded_graph* s, int mixer_id) {
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return -PG_ERR_NOT_FOUND;
-  return mixer_id == 0 ? 0 : shard_of(pk);
+  if (!s) return -sharded_null();
+  const ShardTarget m = sharded_mixer(s, mixer_id, false);
+  return m.g ? m.shard : -PG_ERR_NOT_FOUND;
 }
 // Player::remove_mixer / remove_effect / move_effect (src/player.rs:825-867,942-990 -> MixerMessage::RemoveMixer / RemoveEffect / MoveEffect,
 // src/source/mixed.rs:422-462) on the shard that owns the target; ids stay global and are never reused.
 int pg_sharded_remove_mixer(pg_sharded_graph* s, int mixer_id) {
   if (mixer_id == 0) return set_error(PG_ERR_PARAMETER, "Cannot remove the main mixer");
-  int32_t pk;
-  if (!sharded_mixer(s, mixer_id, pk)) return PG_ERR_NOT_FOUND;
-  pg_graph* g = s->shards[shard_of(pk)];
-  const int local = local_of(pk);
-  const bool top_level = local > 0 && local < (int)g->mixers.size() && !g->mixers[local].removed && g->mixers[local].parent == 0;
-  const int rc = pg_graph_remove_mixer(g, local);
-  if (rc == PG_OK && top_level && s->load[shard_of(pk)] > 0) s->load[shard_of(pk)] -= 1;  // the shard has room for the next sub-mixer again
+  if (!s) return sharded_null();
+  const ShardTarget m = sharded_mixer(s, mixer_id, false);
+  if (!m.g) return PG_ERR_NOT_FOUND;
+  const bool top_level = m.local > 0 && m.local < (int)m.g->mixers.size() && !m.g->mixers[m.local].removed && m.g->mixers[m.local].parent == 0;
+  const int rc = pg_graph_remove_mixer(m.g, m.local);
+  if (rc == PG_OK && top_level && s->load[(size_t)m.shard] > 0) s->load[(size_t)m.shard] -= 1;  // the shard has room for the next sub-mixer again
   return rc;
 }
-int pg_sharded_remove_effect(pg_sharded_graph* s, int effect_id) {
-  if (effect_id < 0 || (size_t)effect_id >= s->fx_map.size()) return set_error(PG_ERR_NOT_FOUND, "Effect with id %d not found", effect_id);
-  const int32_t pk = s->fx_map.get((size_t)effect_id);
-  return pg_graph_remove_effect(s->shards[shard_of(pk)], local_of(pk));
-}
+int pg_sharded_remove_effect(pg_sharded_graph* s, int effect_id) { return sharded_forward<AS_STATUS>(s, sharded_fx, effect_id, pg_graph_remove_effect); }
 int pg_sharded_move_effect(pg_sharded_graph* s, int effect_id, int mixer_id, int movement, int offset) {
-  if (effect_id < 0 || (size_t)effect_id >= s->fx_map.size()) return set_error(PG_ERR_NOT_FOUND, "Effect with id %d not found", effect_id);
-  int32_t mk;
-  if (!sharded_mixer(s, mixer_id, mk)) return PG_ERR_NOT_FOUND;
-  const int32_t pk = s->fx_map.get((size_t)effect_id);
-  const int m_shard = mixer_id == 0 ? 0 : shard_of(mk), m_local = mixer_id == 0 ? 0 : local_of(mk);
-  if (m_shard != shard_of(pk)) return set_error(PG_ERR_PARAMETER, "Effect %d does not belong to mixer %d", effect_id, mixer_id);
-  return pg_graph_move_effect(s->shards[m_shard], local_of(pk), m_local, movement, offset);
+  if (!s) return sharded_null();
+  const ShardTarget e = sharded_fx(s, effect_id, false);
+  if (!e.g) return PG_ERR_NOT_FOUND;
+  const ShardTarget m = sharded_mixer(s, mixer_id, false);
+  if (!m.g) return PG_ERR_NOT_FOUND;
+  if (m.shard != e.shard) return set_error(PG_ERR_PARAMETER, "Effect %d does not belong to mixer %d", effect_id, mixer_id);
+  return pg_graph_move_effect(m.g, e.local, m.local, movement, offset);
 }
 // control calls (any thread): routed to the owning shard's message ring
-#define SHARDED_FX(s, effect_id, pk) \
-  if ((effect_id) < 0 || (size_t)(effect_id) >= (s)->fx_map.size()) return set_error(PG_ERR_NOT_FOUND, "Effect with id %d not found", (effect_id)); \
-  const int32_t pk = (s)->fx_map.get((size_t)(effect_id))
-#define SHARDED_VOICE(s, voice_id, pk) \
-  if ((voice_id) < 0 || (size_t)(voice_id) >= (s)->voice_map.size()) return set_error(PG_ERR_NOT_FOUND, "Source with id %d not found", (voice_id)); \
-  const int32_t pk = (s)->voice_map.get((size_t)(voice_id))
 int pg_sharded_schedule_param(pg_sharded_graph* s, int effect_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
-  SHARDED_FX(s, effect_id, pk);
-  return pg_graph_schedule_param(s->shards[shard_of(pk)], local_of(pk), fourcc, value, is_normalized, sample_time);
+  return sharded_forward<AS_STATUS>(s, sharded_fx, effect_id, pg_graph_schedule_param, fourcc, value, is_normalized, sample_time);
 }
-int pg_sharded_schedule_reset(pg_sharded_graph* s, int effect_id, uint64_t sample_time) {
-  SHARDED_FX(s, effect_id, pk);
-  return pg_graph_schedule_reset(s->shards[shard_of(pk)], local_of(pk), sample_time);
-}
-int pg_sharded_set_voice_volume(pg_sharded_graph* s, int voice_id, float volume, uint64_t sample_time) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_volume(s->shards[shard_of(pk)], local_of(pk), volume, sample_time);
-}
-int pg_sharded_set_voice_panning(pg_sharded_graph* s, int voice_id, float panning, uint64_t sample_time) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_panning(s->shards[shard_of(pk)], local_of(pk), panning, sample_time);
-}
+int pg_sharded_schedule_reset(pg_sharded_graph* s, int effect_id, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_fx, effect_id, pg_graph_schedule_reset, sample_time); }
+int pg_sharded_set_voice_volume(pg_sharded_graph* s, int voice_id, float volume, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_volume, volume, sample_time); }
+int pg_sharded_set_voice_panning(pg_sharded_graph* s, int voice_id, float panning, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_panning, panning, sample_time); }
 int pg_sharded_set_voice_speed(pg_sharded_graph* s, int voice_id, double speed, float glide_semitones_per_second, uint64_t sample_time) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_speed(s->shards[shard_of(pk)], local_of(pk), speed, glide_semitones_per_second, sample_time);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_speed, speed, glide_semitones_per_second, sample_time);
 }
-int pg_sharded_seek_voice(pg_sharded_graph* s, int voice_id, double position_seconds, uint64_t sample_time) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_seek_voice(s->shards[shard_of(pk)], local_of(pk), position_seconds, sample_time);
-}
-int pg_sharded_stop_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_stop_voice(s->shards[shard_of(pk)], local_of(pk), sample_time);
-}
-int pg_sharded_remove_voice(pg_sharded_graph* s, int voice_id) {
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_remove_voice(s->shards[shard_of(pk)], local_of(pk));
-}
+int pg_sharded_seek_voice(pg_sharded_graph* s, int voice_id, double position_seconds, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_seek_voice, position_seconds, sample_time); }
+int pg_sharded_stop_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_stop_voice, sample_time); }
+int pg_sharded_remove_voice(pg_sharded_graph* s, int voice_id) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_remove_voice); }
+int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id) { return sharded_forward<AS_QUIET_ZERO>(s, sharded_voice, voice_id, pg_graph_is_voice_playing); }
 int pg_sharded_stop_all_voices(pg_sharded_graph* s) {
+  if (!s) return sharded_null();
   for (pg_graph* g : s->shards) { int rc = pg_graph_stop_all_voices(g); if (rc) return rc; }
   return PG_OK;
 }
+// envelopes (pg_graph_set_voice_envelope / _release_voice / _voice_envelope_stage): on the voice's shard
 int pg_sharded_set_voice_envelope(pg_sharded_graph* s, int voice_id, const pg_ahdsr_params* p) {
-  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }   // (before the id: parameter errors never depend on the graph)
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_envelope(s->shards[shard_of(pk)], local_of(pk), p);
+  { const int rc = pg_ahdsr_params_check(p); if (rc) return rc; }   // (before the handle and the id: parameter errors never depend on the graph)
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_envelope, p);
 }
-int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_release_voice(s->shards[shard_of(pk)], local_of(pk), sample_time);
-}
-// the modulation matrix of a granular voice (pg_graph_set_voice_modulation_matrix and its timed calls): on the voice's shard
+int pg_sharded_release_voice(pg_sharded_graph* s, int voice_id, uint64_t sample_time) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_release_voice, sample_time); }
+int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) { return sharded_forward<AS_QUIET_MINUS_ONE>(s, sharded_voice, voice_id, pg_graph_voice_envelope_stage); }
+// the modulation matrix of a granular voice (pg_graph_set_voice_modulation_matrix and its timed calls): on the voice's shard. The timed calls
+// leave their argument checks to the plain graph's: a null handle goes there as a null graph and comes back as the parameter error, or its own.
 int pg_sharded_set_voice_modulation_matrix(pg_sharded_graph* s, int voice_id, const pg_modulation_params* p) {
-  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }   // (before the id: parameter errors never depend on the graph)
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_modulation_matrix(s->shards[shard_of(pk)], local_of(pk), p);
+  { const int rc = pg_modulation_params_check(p); if (rc) return rc; }
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_modulation_matrix, p);
 }
 int pg_sharded_set_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
-  if (!s) return pg_graph_set_voice_modulation(nullptr, 0, source, target, amount, bipolar, 0);   // (the parameter error, or the null handle's)
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_modulation(s->shards[shard_of(pk)], local_of(pk), source, target, amount, bipolar, sample_time);
+  if (!s) return pg_graph_set_voice_modulation(nullptr, 0, source, target, amount, bipolar, 0);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_modulation, source, target, amount, bipolar, sample_time);
 }
 int pg_sharded_clear_voice_modulation(pg_sharded_graph* s, int voice_id, int source, int target, uint64_t sample_time) {
   return pg_sharded_set_voice_modulation(s, voice_id, source, target, 0.0f, 0, sample_time);
 }
 int pg_sharded_set_voice_lfo_rate(pg_sharded_graph* s, int voice_id, int lfo, float rate_hz, uint64_t sample_time) {
-  if (!s) return pg_graph_set_voice_lfo_rate(nullptr, 0, lfo, rate_hz, 0);   // (the parameter error, or the null handle's)
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_lfo_rate(s->shards[shard_of(pk)], local_of(pk), lfo, rate_hz, sample_time);
+  if (!s) return pg_graph_set_voice_lfo_rate(nullptr, 0, lfo, rate_hz, 0);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_lfo_rate, lfo, rate_hz, sample_time);
 }
 int pg_sharded_set_voice_lfo_waveform(pg_sharded_graph* s, int voice_id, int lfo, int waveform, uint64_t sample_time) {
   if (!s) return pg_graph_set_voice_lfo_waveform(nullptr, 0, lfo, waveform, 0);
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_lfo_waveform(s->shards[shard_of(pk)], local_of(pk), lfo, waveform, sample_time);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_lfo_waveform, lfo, waveform, sample_time);
 }
-int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modulation_state* out) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_voice_modulation_state(s->shards[shard_of(pk)], local_of(pk), out);
-}
+int pg_sharded_voice_modulation_state(pg_sharded_graph* s, int voice_id, pg_modulation_state* out) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_voice_modulation_state, out); }
 // the granular parameters and loop range of a granular voice (pg_graph_set_voice_granular_parameter / _grain_loop_range): on the voice's shard
 int pg_sharded_set_voice_granular_parameter(pg_sharded_graph* s, int voice_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
-  if (!s) return pg_graph_set_voice_granular_parameter(nullptr, 0, fourcc, value, is_normalized, 0);   // (the parameter error, or the null handle's)
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_granular_parameter(s->shards[shard_of(pk)], local_of(pk), fourcc, value, is_normalized, sample_time);
+  if (!s) return pg_graph_set_voice_granular_parameter(nullptr, 0, fourcc, value, is_normalized, 0);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_granular_parameter, fourcc, value, is_normalized, sample_time);
 }
 int pg_sharded_set_voice_grain_loop_range(pg_sharded_graph* s, int voice_id, int has_loop_range, float loop_start, float loop_end, uint64_t sample_time) {
   if (!s) return pg_graph_set_voice_grain_loop_range(nullptr, 0, has_loop_range, loop_start, loop_end, 0);
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_grain_loop_range(s->shards[shard_of(pk)], local_of(pk), has_loop_range, loop_start, loop_end, sample_time);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_grain_loop_range, has_loop_range, loop_start, loop_end, sample_time);
 }
-int pg_sharded_voice_granular_params(pg_sharded_graph* s, int voice_id, pg_granular_params* out) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_voice_granular_params(s->shards[shard_of(pk)], local_of(pk), out);
-}
-int pg_sharded_voice_envelope_stage(pg_sharded_graph* s, int voice_id) {
-  if (!s || voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return -1;
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_voice_envelope_stage(s->shards[shard_of(pk)], local_of(pk));
-}
+int pg_sharded_voice_granular_params(pg_sharded_graph* s, int voice_id, pg_granular_params* out) { return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_voice_granular_params, out); }
 // PlayerConfig::metering_interval for the one mixer: every shard meters its sub-mixers, the root the main mixer (pg_graph_set_metering)
 int pg_sharded_set_metering(pg_sharded_graph* s, double interval_seconds) {
   if (std::isnan(interval_seconds) || (std::isinf(interval_seconds) && interval_seconds > 0)) return set_error(PG_ERR_PARAMETER, "Invalid metering interval: %g", interval_seconds);
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   for (pg_graph* g : s->shards) { const int rc = pg_graph_set_metering(g, interval_seconds); if (rc) return rc; }
   return PG_OK;
 }
 // A sub-mixer's level comes from its shard, mixer 0's from the root. Any thread, no HIP call (pg_graph_mixer_audio_level).
 int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_level* out) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   if (!out) return set_error(PG_ERR_PARAMETER, "`out` must not be null");
   if (mixer_id == 0) return pg_graph_mixer_audio_level(s->shards[0], 0, out);
   if (!s->shards[0]->meter_on.load(std::memory_order_acquire)) return set_error(PG_ERR_STATE, "metering is off (pg_sharded_set_metering)");
-  if (mixer_id < 0 || (size_t)mixer_id >= s->mixer_map.size()) return set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
-  const int32_t pk = s->mixer_map.get((size_t)mixer_id);
-  return pg_graph_mixer_audio_level(s->shards[shard_of(pk)], local_of(pk), out);
+  const ShardTarget m = sharded_mixer(s, mixer_id, false);
+  return m.g ? pg_graph_mixer_audio_level(m.g, m.local, out) : PG_ERR_NOT_FOUND;
 }
 // pg_graph_enable_status / _set_voice_status / _poll_status / _status_dropped on the one mixer (src/source/status.rs, src/source/file/common.rs:171-221):
 // every shard decides the records of its voices and keeps a ring of `capacity_events` of its own; a poll merges the shards' rings into the
@@ -650,7 +592,7 @@ int pg_sharded_mixer_audio_level(pg_sharded_graph* s, int mixer_id, pg_audio_lev
 // added (each with everything under it: one shard), then its sources in its list's order (sorted by start time, a new source in front of those
 // that start at the same time, mixed.rs:324-329) — and hands out the handle's voice ids. The dropped count is the shards' sum.
 int pg_sharded_enable_status(pg_sharded_graph* s, size_t capacity_events) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   if (capacity_events == 0) return set_error(PG_ERR_PARAMETER, "the status ring needs room for one record at least");
   for (pg_graph* g : s->shards) if (g->pstat.on) return set_error(PG_ERR_STATE, "playback status is enabled already");
   for (size_t i = 0; i < s->shards.size(); ++i) {
@@ -662,10 +604,9 @@ int pg_sharded_enable_status(pg_sharded_graph* s, size_t capacity_events) {
   return PG_OK;
 }
 int pg_sharded_set_voice_status(pg_sharded_graph* s, int voice_id, double position_emit_seconds, int report_stopped) {
-  if (!s) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (!s) return sharded_null();
   if (std::isnan(position_emit_seconds)) return set_error(PG_ERR_PARAMETER, "Invalid position emit rate: %g", position_emit_seconds);
-  SHARDED_VOICE(s, voice_id, pk);
-  return pg_graph_set_voice_status(s->shards[shard_of(pk)], local_of(pk), position_emit_seconds, report_stopped);
+  return sharded_forward<AS_STATUS>(s, sharded_voice, voice_id, pg_graph_set_voice_status, position_emit_seconds, report_stopped);
 }
 static void sharded_status_note_ids(pg_sharded_graph* s) {
   const size_t n = s->shards.size();
@@ -712,11 +653,6 @@ uint64_t pg_sharded_status_dropped(pg_sharded_graph* s) {
   uint64_t n = 0;
   for (pg_graph* g : s->shards) n += pg_graph_status_dropped(g);
   return n;
-}
-int pg_sharded_is_voice_playing(pg_sharded_graph* s, int voice_id) {
-  if (voice_id < 0 || (size_t)voice_id >= s->voice_map.size()) return 0;
-  const int32_t pk = s->voice_map.get((size_t)voice_id);
-  return pg_graph_is_voice_playing(s->shards[shard_of(pk)], local_of(pk));
 }
 
 }  // extern "C"
@@ -827,6 +763,7 @@ static int sharded_render_segment(pg_sharded_graph* s, float* d_dst, size_t stag
 // `span_done(offset, samples)` takes it away. Returns the samples written, 0 when the one main mixer would return 0: no playing source, no
 // sub-mixer and no pending event on any shard, and no effect on mixer 0.
 static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contiguous, size_t n_samples, uint64_t pos, const std::function<int(size_t, size_t)>& span_done) {
+  if (!s) { sharded_null(); return 0; }
   if (s->failed) return 0;
   if (n_samples % 2 != 0) { set_error(PG_ERR_PARAMETER, "n_samples must be a multiple of the channel count"); return 0; }
   // process_messages of the one mixer: every shard takes its messages now, none later in this call
@@ -881,7 +818,7 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
 extern "C" {
 
 size_t pg_sharded_write_device(pg_sharded_graph* s, float* d_out, size_t n_samples, uint64_t pos_in_frames) { return sharded_write_walk(s, d_out, true, n_samples, pos_in_frames, nullptr); }
-int pg_sharded_synchronize(pg_sharded_graph* s) { return sharded_wait_all(s); }
+int pg_sharded_synchronize(pg_sharded_graph* s) { return s ? sharded_wait_all(s) : sharded_null(); }
 size_t pg_sharded_write(pg_sharded_graph* s, float* out, size_t n_samples, uint64_t pos_in_frames) {
   // every span: the status words of every shard, the span's samples to the pinned staging, one wait, then out of the way for the next span
   auto span_done = [s, out](size_t off, size_t n) -> int {
@@ -894,9 +831,10 @@ size_t pg_sharded_write(pg_sharded_graph* s, float* out, size_t n_samples, uint6
     memcpy(out + off, s->h_pinned, n * sizeof(float));
     return PG_OK;
   };
-  return sharded_write_walk(s, s->d_bus, false, n_samples, pos_in_frames, span_done);
+  return sharded_write_walk(s, s ? s->d_bus : nullptr, false, n_samples, pos_in_frames, span_done);
 }
 int pg_sharded_device_errors(pg_sharded_graph* s) {
+  if (!s) return -sharded_null();
   int e = 0;
   for (pg_graph* g : s->shards) { const int r = pg_graph_device_errors(g); if (r < 0) return r; e |= r; }
   return e;

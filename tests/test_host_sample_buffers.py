@@ -1,43 +1,15 @@
 """The host side of the sample buffers under AddressSanitizer + UndefinedBehaviorSanitizer + LeakSanitizer, without a GPU: the library's
-translation units compiled host-only against the stub HIP runtime (tests/host/hip_stub.cpp, as tests/test_sanitizers.py does for
+translation units compiled host-only against the stub HIP runtime (tests/host_build.py, the recipe tests/test_sanitizers.py uses for
 host_fuzz.cpp) and linked with the stand-alone program tests/host/sample_buffer_host.cpp, which walks the reference counts of both handles —
 release while voices play, voices and mixers removed, destroy with buffers still held — and checks that the library's allocation and release
 counters balance."""
-import glob
 import os
 import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import host_build
 
 
 def test_sample_buffer_reference_counts_under_asan_and_ubsan(tmp_path):
-    if not (os.path.exists(HIPCC) and os.path.exists(CLANG)):
-        pytest.skip("hipcc not available")
-    csrc = os.path.join(ROOT, "phonic_amd", "csrc")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    flags = ["--cuda-host-only", "-std=c++17", "-O1", "-g", "-fPIC", "-ffp-contract=off", "-fno-omit-frame-pointer", "-DPG_FAST_WAVES=2", "-Wno-unused", "-Wno-unused-command-line-argument"] + san
-    units = ["pg_host", "pg_sampler", "pg_fxstate", "pg_effect", "pg_sharded", "pg_kernels"] + sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(csrc, "pg_k_*.hip")))
-    objs, jobs = [], []
-    for tu in units:
-        objs.append(str(tmp_path / (tu + ".o")))
-        jobs.append(subprocess.Popen([HIPCC] + flags + ["-c", os.path.join(csrc, tu + ".hip"), "-o", objs[-1]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    stub = str(tmp_path / "hip_stub.o")
-    jobs.append(subprocess.Popen([HIPCC] + flags + ["-c", os.path.join(ROOT, "tests", "host", "hip_stub.cpp"), "-x", "hip", "-o", stub], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
-    for j in jobs:
-        out, _ = j.communicate(timeout=900)
-        assert j.returncode == 0, out[-3000:]
-    # the module constructors name the (absent) device code objects of their translation units: define those symbols, empty
-    undefined = subprocess.run(["nm", "-u"] + objs, capture_output=True, text=True).stdout.split()
-    fat = tmp_path / "fatbins.cpp"
-    fat.write_text("".join(f"extern \"C\" const char {s}[16] = {{0}};\n" for s in sorted(set(u for u in undefined if u.startswith("__hip_fatbin_")))))
-    exe = str(tmp_path / "sample_buffer_host")
-    link = subprocess.run([CLANG, "-std=c++17", "-O1", "-g"] + san + [os.path.join(ROOT, "tests", "host", "sample_buffer_host.cpp"), str(fat), stub] + objs + ["-o", exe, "-lpthread", "-ldl"],
-                          capture_output=True, text=True, timeout=600)
-    assert link.returncode == 0, link.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    exe = host_build.build_host_program(tmp_path, "sample_buffer_host")
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=dict(os.environ, **host_build.SANITIZER_ENV))
     assert run.returncode == 0 and "ok" in run.stdout, (run.stdout[-1000:], run.stderr[-4000:])
