@@ -442,6 +442,40 @@ int pg_graph_prepare_granular_buffer(pg_graph* g, int buffer_id);
 int pg_graph_sample_buffer_info(pg_graph* g, int buffer_id, pg_sample_buffer_info* out);
 int64_t pg_graph_read_granular_buffer(pg_graph* g, int buffer_id, float* out, size_t cap_frames);
 
+/* Waveform overviews of a sample buffer: phonic::utils::waveform::mixed_down / multi_channel (src/utils/waveform.rs:95-199) over the copy the
+ * device already holds — min / max pairs per display column, so that a host that draws a sample keeps no second copy of its PCM and reads none
+ * back. A display helper, NOT a real-time call: it runs on the owner thread, waits for the work of earlier writes, allocates its staging memory,
+ * launches (pg_waveform_*_kernel, DESIGN.md "Waveform overviews"), waits for the result and frees the memory again. It may be called between
+ * writes while voices play the buffer: it reads immutable memory and changes nothing a later write renders.
+ * The slice is frames [first_frame, first_frame + n_frames) of the source — the `&buffer[a * ch .. b * ch]` a caller of the reference passes
+ * when it zooms; `frame` and `time` count from the slice's start. PG_WAVEFORM_OF_FILE: the buffer as uploaded (AudioFileBuffer::buffer(), the
+ * decoder's extra zero frame included), with the buffer's channel count and rate. PG_WAVEFORM_OF_GRANULAR: the buffer's granular mono buffer
+ * (made if it is not there, as pg_graph_read_granular_buffer does — a graph-changing step), one channel at the graph's rate.
+ * Returns the number of points per channel, P = min(n_frames, resolution), or -PG_ERR_*. PG_WAVEFORM_MIXED_DOWN writes P points;
+ * PG_WAVEFORM_MULTI_CHANNEL writes channels * P points, channel-major: out[c * P + i]. Every value is the reference's, operation for operation
+ * (the sign of a zero aside): n_frames <= resolution gives one point per frame with min == max; otherwise step = n_frames as f32 / resolution
+ * as f32 and point i covers frames [b(i), b(i + 1)), b(i) = min((i as f32 * step) as usize, n_frames) — one rounded f32 product, truncated —
+ * with frame = b(i) before the clamp; a point that covers no frame, or only NaN samples, keeps min = FLT_MAX, max = -FLT_MAX (f32::MAX,
+ * f32::MIN); the mono value of a frame is the fold 0.0 + l / ch + r / ch in channel order, each sample divided first; a NaN sample is skipped.
+ * -PG_ERR_PARAMETER, answered before the handle and before anything touches the device: a null `out`, resolution == 0, n_frames == 0, a `source`
+ * or `mode` outside the two values, cap_points < P. Then: a null handle (-PG_ERR_PARAMETER, "graph handle is null"), an unknown or released
+ * buffer (-PG_ERR_NOT_FOUND), a slice that leaves the source, or cap_points < channels * P for PG_WAVEFORM_MULTI_CHANNEL (-PG_ERR_PARAMETER;
+ * 2 * P always suffices, P does for a mono source). Nothing is written to `out` when the call fails.
+ * The sharded handle has no such call on purpose: a host that holds one takes overviews from a single-device graph (pg_graph_create) to which it
+ * has added the buffer. */
+#define PG_WAVEFORM_MIXED_DOWN    0   /* waveform::mixed_down    (waveform.rs:95-140)  */
+#define PG_WAVEFORM_MULTI_CHANNEL 1   /* waveform::multi_channel (waveform.rs:149-199) */
+#define PG_WAVEFORM_OF_FILE       0   /* the buffer as uploaded: AudioFileBuffer::buffer(), the decoder's extra zero frame included */
+#define PG_WAVEFORM_OF_GRANULAR   1   /* the buffer's granular mono buffer at the graph's rate (made if it is not there, as pg_graph_read_granular_buffer does) */
+typedef struct pg_waveform_point {   /* waveform::Point; 24 bytes */
+  uint64_t frame;   /* frame_index inside the slice this point starts at */
+  float time;       /* frame as f32 / rate as f32, seconds: the argument the reference gives Duration::from_secs_f32 (the binding converts) */
+  float min, max;
+  uint32_t reserved;  /* 0 */
+} pg_waveform_point;
+int64_t pg_graph_sample_buffer_waveform(pg_graph* g, int buffer_id, int source, int mode, uint64_t first_frame, uint64_t n_frames, uint32_t resolution,
+                                        pg_waveform_point* out, size_t cap_points);
+
 /* The modulation matrix of a granular voice: the ModulationMatrix every granular sampler voice owns (src/generator/sampler/voice.rs:341-373,
  * src/modulation/matrix.rs, src/generator/sampler/modulation.rs), run in front of the grain engine (voice.rs:412-427) — on the device as phase 0
  * of pg_grain_kernel ("Granular voices", Modulation). Sources in the matrix's slot order (sampler.rs:362-416): 0 LFO 1 (`LFO1`,
@@ -629,6 +663,9 @@ void pg_debug_hip_calls(uint64_t out[4]);
  * (interpolation and down-mix) of its conversion; 0 where none ran. The events exist only in a process with PHONIC_DEBUG_HOOKS=1 in its
  * environment: without it pg_graph_add_sample_buffer and the conversion create and record none, and this reads zeros. */
 int pg_debug_sample_buffer_times(pg_graph* g, int buffer_id, float out_ms[3]);
+/* Measurement hook (tools/waveform_cost.py): hipEvent time in ms of the kernels of the buffer's last pg_graph_sample_buffer_waveform call (without
+ * the waits, the allocation and the copy to the host); 0 if none ran. Like the hook above it exists only with PHONIC_DEBUG_HOOKS=1. */
+int pg_debug_sample_buffer_waveform_time(pg_graph* g, int buffer_id, float* out_ms);
 /* Test hook: the nth launch round from now (process-wide, any graph) fails the way a HIP launch failure does — the graph it hits becomes
  * silent for good: write returns 0, like the reference's GuardedSource after a panic (src/source/guarded.rs:87-107). 0 disarms. Armed only in
  * a process with PHONIC_DEBUG_HOOKS=1 in its environment; a no-op otherwise. */

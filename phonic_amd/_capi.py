@@ -297,6 +297,15 @@ class SampleBufferInfo(C.Structure):
                 ("loop_start", C.c_uint64), ("loop_end", C.c_uint64), ("granular_frames", C.c_int64)]
 
 
+class WaveformPoint(C.Structure):
+    """pg_waveform_point: waveform::Point (reference src/utils/waveform.rs:73-81) — `frame` inside the slice, `time` = frame as f32 / rate as f32."""
+    _fields_ = [("frame", C.c_uint64), ("time", C.c_float), ("min", C.c_float), ("max", C.c_float), ("reserved", C.c_uint32)]
+
+
+PG_WAVEFORM_MIXED_DOWN, PG_WAVEFORM_MULTI_CHANNEL = 0, 1   # waveform::mixed_down / multi_channel
+PG_WAVEFORM_OF_FILE, PG_WAVEFORM_OF_GRANULAR = 0, 1        # the buffer as uploaded / its granular mono buffer at the graph's rate
+
+
 def sample_buffer_desc(channels, rate, loop_range=None):
     """loop_range = (start, end) in source frames: the file's embedded loop, or None."""
     d = SampleBufferDesc(channels=channels, rate=rate)
@@ -440,6 +449,7 @@ MIXER_CALLS = (
 # what only the plain graph has (argument types behind the handle)
 GRAPH_ONLY_CALLS = (
     ("read_granular_buffer", C.c_int64, [_int, _P(_f32), _sz]),
+    ("sample_buffer_waveform", C.c_int64, [_int, _int, _int, _u64, _u64, _u32, _P(WaveformPoint), _sz]),   # (buffer, source, mode, first frame, frames, resolution, out, capacity)
     ("write_device", _sz, [_vp, _sz, _u64, _vp]),
     ("set_defer_bus", _int, [_int]),
     ("process_bus_device", _int, [_vp, _sz, _u64, _vp]),
@@ -491,6 +501,7 @@ PLAIN_CALLS = (
     ("pg_modulation_params_default", None, [_P(ModulationParams)]),
     ("pg_modulation_params_check", _int, [_P(ModulationParams)]),
     ("pg_debug_sample_buffer_times", _int, [_vp, _int, _P(_f32)]),
+    ("pg_debug_sample_buffer_waveform_time", _int, [_vp, _int, _P(_f32)]),
     ("pg_debug_fail_launch_round", None, [_int]),
     ("pg_debug_hip_calls", None, [_P(_u64)]),
     ("pg_sharded_create", _vp, [_u32, _u32, _sz, _P(_int), _int]),

@@ -189,6 +189,34 @@ class GraphHandle:
         self._id(self._fn("graph_read_granular_buffer")(self._h, buffer_id, _f32p(out), out.size))
         return out
 
+    def sample_buffer_waveform(self, buffer_id, resolution, mode="mixed_down", source="file", first_frame=0, n_frames=None):
+        """waveform::mixed_down / multi_channel (reference src/utils/waveform.rs) of frames [first_frame, first_frame + n_frames) of the buffer
+        (source="file": the PCM as uploaded) or of its granular mono buffer (source="granular"), computed on the device. n_frames=None: up to the
+        source's end. Returns a dict of numpy arrays frame (uint64), time (float32 seconds), min, max (float32), counted from the slice's start:
+        shape (P,) for mode="mixed_down", (channels, P) for mode="multi_channel", P = min(n_frames, resolution). A display helper, not a
+        real-time call: it waits for the device."""
+        modes = {"mixed_down": _capi.PG_WAVEFORM_MIXED_DOWN, "multi_channel": _capi.PG_WAVEFORM_MULTI_CHANNEL}
+        sources = {"file": _capi.PG_WAVEFORM_OF_FILE, "granular": _capi.PG_WAVEFORM_OF_GRANULAR}
+        if mode not in modes or source not in sources:
+            raise ValueError(f"mode must be one of {sorted(modes)}, source one of {sorted(sources)}")
+        info = self.sample_buffer_info(buffer_id)
+        if source == "granular":
+            if info["granular_frames"] < 0:
+                self.prepare_granular_buffer(buffer_id)
+                info = self.sample_buffer_info(buffer_id)
+            total, channels = info["granular_frames"], 1
+        else:
+            total, channels = info["n_frames"], info["channels"]
+        if n_frames is None:
+            n_frames = max(total - int(first_frame), 0)
+        rows = channels if mode == "multi_channel" else 1
+        cap = rows * min(int(n_frames), int(resolution))
+        buf = (_capi.WaveformPoint * max(cap, 1))()
+        p = self._id(self._fn("graph_sample_buffer_waveform")(self._h, buffer_id, sources[source], modes[mode], int(first_frame), int(n_frames), int(resolution), buf, cap))
+        pts = np.frombuffer(buf, dtype=np.dtype([("frame", "<u8"), ("time", "<f4"), ("min", "<f4"), ("max", "<f4"), ("reserved", "<u4")]), count=rows * p)
+        shape = (rows, p) if mode == "multi_channel" else (p,)
+        return {k: pts[k].reshape(shape).copy() for k in ("frame", "time", "min", "max")}
+
     def voice_grain_state(self, voice):
         """The voice's GrainPool and its 100 grains as a dict (debug read-back: waits for the graph's stream)."""
         st = _capi.GrainState()

@@ -274,6 +274,7 @@ struct SampleBuffer {
   int use_count = 0;               // voices holding a reference
   bool held = true;                // the host's reference
   float upload_ms = 0.0f, sched_ms = 0.0f, interp_ms = 0.0f;   // pg_debug_sample_buffer_times: taken only while sample_buffer_timing()
+  float waveform_ms = 0.0f;        // pg_debug_sample_buffer_waveform_time: the kernels of the buffer's last overview (pg_k_waveform.hip), likewise
 };
 struct HostMixer {
   int unit_slot = -1;              // sub-mixer unit; for the main mixer: the bus unit

@@ -28,6 +28,13 @@ class Graph(GraphHandle):
         self._check(self._lib.pg_debug_sample_buffer_times(self._h, buffer_id, out))
         return dict(upload_ms=out[0], sched_ms=out[1], interp_ms=out[2])
 
+    def sample_buffer_waveform_time(self, buffer_id):
+        """Measurement hook (pg_debug_sample_buffer_waveform_time): hipEvent ms of the kernels of the buffer's last sample_buffer_waveform call, taken
+        only in a process with PHONIC_DEBUG_HOOKS=1 in its environment (zero otherwise)."""
+        out = C.c_float(0.0)
+        self._check(self._lib.pg_debug_sample_buffer_waveform_time(self._h, buffer_id, C.byref(out)))
+        return float(out.value)
+
     def set_max_blocks_per_launch(self, n_blocks):
         """Offline rendering: let one write call render up to `n_blocks` blocks of max_frames per launch sequence (steady state only)."""
         self._check(self._lib.pg_graph_set_max_blocks_per_launch(self._h, int(n_blocks)))
@@ -155,6 +162,9 @@ class ShardedGraph(GraphHandle):
         out = np.zeros(n, np.float32)
         self._id(self._lib.pg_sharded_read_granular_buffer(self._h, buffer_id, shard, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
         return out
+
+    def sample_buffer_waveform(self, *args, **kwargs):
+        raise NotImplementedError("the sharded handle takes no waveform overviews: take them from a single-device Graph that holds the buffer")
 
     def write_device(self, d_out_ptr, n_samples, pos_in_frames):
         return self._lib.pg_sharded_write_device(self._h, C.c_void_p(d_out_ptr), n_samples, pos_in_frames)
