@@ -99,7 +99,7 @@ typedef struct pg_effect_init {
 } pg_effect_init;
 
 /* ---- parameter descriptors: `Effect::parameters()` (src/effect.rs:105-111) -------------- */
-typedef enum pg_param_type { PG_PARAM_FLOAT = 0, PG_PARAM_ENUM = 1, PG_PARAM_BOOL = 2 } pg_param_type;
+typedef enum pg_param_type { PG_PARAM_FLOAT = 0, PG_PARAM_ENUM = 1, PG_PARAM_BOOL = 2, PG_PARAM_INTEGER = 3 /* IntegerParameter (src/parameter/integer.rs): min / max / default hold integers */ } pg_param_type;
 typedef enum pg_param_scaling {
   PG_SCALE_LINEAR = 0,
   PG_SCALE_EXPONENTIAL = 1, /* src/parameter/scaling.rs:21  arg0 = factor          */
@@ -299,8 +299,9 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
  * The granular parameters and the loop range change while the voice plays: pg_graph_set_voice_granular_parameter / _grain_loop_range below.
  * The mono buffer the pool reads is what create_granular_sample_buffer (sampler.rs:908-952) makes of a file: hand it over here as `mono_pcm`, or
  * let the device make it from a sample buffer (pg_graph_add_granular_voice_from_buffer below).
- * OUT OF SCOPE: the note, voice-allocation and voice-stealing layer of Sampler; the Sampler's
- * base transpose, finetune, volume and panning parameters (pg_graph_set_voice_speed / _volume / _panning carry their effect);
+ * OUT OF SCOPE for granular voices: the note, voice-allocation and voice-stealing layer of Sampler and the Sampler's
+ * base transpose, finetune, volume and panning parameters — they exist for FILE-playback samplers (pg_graph_add_sampler, below); a binding drives
+ * granular voices one by one, as before (pg_graph_set_voice_speed / _volume / _panning carry the base parameters' effect);
  * AHDSR parameter changes on a running envelope. (The voice's playback-position status events — the start event, a Position per process call,
  * the two Stopped records — are pg_graph_set_voice_status's, below.)
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
@@ -491,7 +492,7 @@ int64_t pg_graph_sample_buffer_waveform(pg_graph* g, int buffer_id, int source, 
  * and as UNVERIFIED against the crate). The matrix advances on the frames the voice renders only: not in front of its start time, not after it
  * has ended. A release touches no modulation source (note_off reaches envelope slots, and the sampler has none, sampler/modulation.rs:101-103).
  * In the reference the timed calls below reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
- * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the Sampler's note, voice-allocation and stealing layer.
+ * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the note layer of a granular-mode Sampler (pg_graph_add_sampler plays files).
  * (pg_modulation_state::last[5] is the value a granular voice's Position records use, voice.rs:435-446: pg_graph_set_voice_status.) (The granular parameters
  * themselves change through pg_graph_set_voice_granular_parameter above; a route's sum applies to the parameter's value as of its frame.) */
 #define PG_MOD_SOURCES 4
@@ -539,6 +540,106 @@ typedef struct pg_modulation_state {
   int32_t reserved;
 } pg_modulation_state;
 int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_state* out);
+
+/* The Sampler generator's note layer: notes, voice allocation and voice stealing (src/generator/sampler.rs, src/generator/sampler/voice.rs) for
+ * file-playback samplers. A sampler is a fixed pool of voice_count file voices of ONE sample buffer in a SUB-mixer; it takes note_on / note_off
+ * and the other GeneratorPlaybackEvents at sample times, picks a free voice or steals one, restarts it and composes the note's pitch, volume and
+ * panning with its base parameters. The layer runs on the device (pg_sampler_dev.h, DESIGN.md "Sampler"): which slot a note gets depends on which
+ * voices still play and which release at exactly the note's frame, and that is decided by the kernel that renders them.
+ *   messages     are applied at the top of the Sampler::write that follows them (process_playback_messages, sampler.rs:656-731); the owning mixer
+ *                cuts its chunk at the message's sample time (mixed.rs:679-712, :902-918), so each acts in front of exactly that frame
+ *                (sample_time 0: the next write's first frame, as for pg_graph_release_voice). Several at one frame: in the order of the calls.
+ *   allocation   next_free_voice_index (sampler.rs:826-860): the first slot that is not active; else, with an envelope, the slot in Release with the
+ *                smallest release_start_frame; else the active slot with the smallest note id. A voice that fades out after a note-off WITHOUT
+ *                an envelope is not "releasing" under this rule. Ties go to the lower slot.
+ *   start        SamplerVoice::start (voice.rs:122-193): an active slot's file source is killed without a fade (preloaded.rs:212-230); speed =
+ *                speed_from_note(note) * 2^(transpose / 12 + finetune / 1200) in f64 (utils.rs:67-78), no glide; volume target = base_volume *
+ *                volume, panning target = clamp(base_panning + panning, -1, 1) — set_target calls on the two exponential smoothers, which are NOT
+ *                reset: a reused slot ramps from what the previous note left, a fresh one from 1.0 / 0.0 (voice.rs:60-65, amplified.rs:60-62);
+ *                AhdsrEnvelope::note_on(params, 1.0) (ahdsr.rs:402-419) with an envelope.
+ *   stop         SamplerVoice::stop (voice.rs:196-219), on an active slot only: release_start_frame = the current frame (also when the slot
+ *                releases already); with an envelope note_off, which restarts the release from the current level; without one the file source's
+ *                stop(): the 50 ms fade-out every sampler voice is built with (sampler.rs:513-514).
+ *   free         a slot becomes free in the source write in which its file is exhausted, its fade-out arrives or its envelope is Idle
+ *                (voice.rs:488-502), not earlier and not later.
+ *   sum          the active voices in slot order (sampler.rs:989-1006).
+ * pg_sampler_options: voice_count 1..=64, default 8 (generator.rs:48-72; the cap of 64 is THIS implementation's: one wave lane per slot);
+ * has_envelope + envelope: Sampler::with_ahdsr, checked like pg_graph_set_voice_envelope's; has_loop_range + loop_start / loop_end (source
+ * frames): Sampler::set_loop_range before playback, every voice then repeats forever (voice.rs:313-328) — without it the buffer's embedded loop
+ * range applies as for pg_graph_add_voice_from_buffer; transient: 1 = Player::play_generator (player.rs:708-718), 0 = add_generator; start_time.
+ * pg_sampler_options_default / _check touch no graph and no device; _check: PG_OK or PG_ERR_PARAMETER with a message (null options, voice_count
+ * outside 1..=64, envelope errors, loop_start >= loop_end).
+ * pg_graph_add_sampler: returns a sampler id >= 0. -PG_ERR_PARAMETER for mixer_id == PG_MAIN_MIXER (see OUT OF SCOPE) and a loop range outside the
+ * buffer; -PG_ERR_NOT_FOUND for an unknown mixer or buffer. Every pool voice holds a reference on the sample buffer, like any voice made from it.
+ * The pool's voices carry no public voice id. Owner thread; waits for earlier writes like every graph-changing call.
+ * pg_graph_remove_sampler: MixerMessage::RemoveSource — the pool leaves the mixer at the start of the next write, at once; its buffer references
+ * return like those of removed voices; queued messages for it are dropped when they come due. Any thread.
+ * The timed messages (any thread, through the control ring: PG_ERR_QUEUE_FULL applies instead of the reference's 54-entry queue with force_push):
+ *   pg_graph_sampler_note_on       returns the note id: positive, strictly increasing per graph (unique_note_id, generator.rs:32), below 2^31
+ *                                  (-PG_ERR_STATE beyond). -PG_ERR_PARAMETER: a negative or non-finite volume, a non-finite panning, a null handle.
+ *   pg_graph_sampler_note_off / _set_note_speed / _set_note_volume / _set_note_panning   reach the FIRST slot in index order that plays the note
+ *                                  (sampler.rs:776-822); an unknown or ended note id is ignored. speed > 0 and finite, composed with the base pitch
+ *                                  (voice.rs:239-254); glide_semitones_per_second <= 0: none. Volume >= 0, panning finite (composed and clamped).
+ *   pg_graph_sampler_all_notes_off stops every active slot.
+ *   pg_graph_sampler_set_parameter the base parameters, sampler.rs:1076-1120: STRN Transpose (integer -48..48, 0), SFTN Finetune (integer -100..100,
+ *                                  0), SVOL Volume (0.000001..15.848932, 1.0, Decibel(-60, 24)), SPAN Panning (-1..1, 0.0). The host resolves the
+ *                                  value as parameter_update_value / _integer do (sampler.rs:862-906): raw values are clamped (integers truncated
+ *                                  first), normalized ones denormalized (integers rounded, integer.rs:121-126). The stored base value changes and
+ *                                  every ACTIVE voice is recomputed; a pitch change ends a glide. PG_ERR_PARAMETER: an unknown FourCC, a NaN, a
+ *                                  normalized value outside [0, 1] (player/handles/generator.rs:342-348).
+ *   pg_graph_sampler_stop          Sampler::stop (sampler.rs:733-738): all notes off; a transient sampler is `stopping` from then on, drops every
+ *                                  later message, becomes `stopped` in the first write that ends with no active slot (:1011-1024) and leaves the
+ *                                  mixer (its id returns PG_ERR_NOT_FOUND once the host has seen that, at the top of a later write).
+ * pg_sampler_param_count / pg_sampler_param: the four descriptors in Sampler::base_parameters() order (PG_PARAM_INTEGER for the first two).
+ * pg_graph_sampler_state: debug read-back; waits for the graph's work like pg_graph_voice_envelope_stage. Per slot: note_id (0 = free), and note,
+ * note_volume, note_panning of the slot's last note; envelope_stage (-1 without an envelope); release_start_frame (UINT64_MAX = none).
+ * An id of a removed or never-created sampler: PG_ERR_NOT_FOUND. A null handle: PG_ERR_PARAMETER ("graph handle is null"), after the argument checks.
+ * A unit that holds a sampler is rendered by the exact kernel for as long as the sampler lives.
+ * The sharded handle has NO sampler entry points yet (tests/test_host_sharded_routing.py counts the header's handle-taking pg_sharded_* functions
+ * against its fixed program): they follow in a change that may touch that program.
+ * OUT OF SCOPE: samplers on the main mixer (its sources are one unit, one workgroup, each; the pool needs one workgroup that sees every slot — a
+ * multi-voice source unit is the follow-up); granular-mode samplers (Sampler::with_granular_playback: their start runs through GrainPool::start
+ * and the modulation state, built on the host today); AMP_* envelope-parameter changes while playing; playback status events of sampler voices
+ * and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101). */
+#define PG_SAMPLER_MAX_VOICES 64
+typedef struct pg_sampler_options {
+  uint32_t voice_count;      /* 1..=64, default 8 */
+  uint32_t has_envelope;     /* Sampler::with_ahdsr */
+  pg_ahdsr_params envelope;
+  uint32_t has_loop_range;   /* Sampler::set_loop_range before playback, source frames */
+  uint32_t transient;        /* 1 = play_generator, 0 = add_generator (default) */
+  uint64_t loop_start, loop_end;
+  uint64_t start_time;
+} pg_sampler_options;
+typedef struct pg_sampler_slot_state {
+  int64_t note_id;               /* 0 = free */
+  uint64_t release_start_frame;  /* UINT64_MAX = none */
+  float note_volume, note_panning;
+  int32_t note;
+  int32_t envelope_stage;        /* AhdsrStage 0..5, -1 without an envelope */
+} pg_sampler_slot_state;
+typedef struct pg_sampler_state {
+  int32_t voice_count, active_voices;
+  int32_t stopping, stopped;
+  int32_t transpose, finetune;
+  float volume, panning;
+  pg_sampler_slot_state slots[PG_SAMPLER_MAX_VOICES];
+} pg_sampler_state;
+void pg_sampler_options_default(pg_sampler_options* opt);
+int pg_sampler_options_check(const pg_sampler_options* opt);
+int pg_sampler_param_count(void);
+int pg_sampler_param(int index, pg_param_desc* out);
+int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt);
+int pg_graph_remove_sampler(pg_graph* g, int sampler_id);
+int64_t pg_graph_sampler_note_on(pg_graph* g, int sampler_id, uint8_t note, float volume, float panning, uint64_t sample_time);
+int pg_graph_sampler_note_off(pg_graph* g, int sampler_id, int64_t note_id, uint64_t sample_time);
+int pg_graph_sampler_all_notes_off(pg_graph* g, int sampler_id, uint64_t sample_time);
+int pg_graph_sampler_set_note_speed(pg_graph* g, int sampler_id, int64_t note_id, double speed, float glide_semitones_per_second, uint64_t sample_time);
+int pg_graph_sampler_set_note_volume(pg_graph* g, int sampler_id, int64_t note_id, float volume, uint64_t sample_time);
+int pg_graph_sampler_set_note_panning(pg_graph* g, int sampler_id, int64_t note_id, float panning, uint64_t sample_time);
+int pg_graph_sampler_set_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
+int pg_graph_sampler_stop(pg_graph* g, int sampler_id, uint64_t sample_time);
+int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out);
 
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and
@@ -614,7 +715,7 @@ int pg_graph_mixer_audio_level(pg_graph* g, int mixer_id, pg_audio_level* out);
  * pg_graph_set_max_blocks_per_launch: the result of those is bit-identical to single launches anyway), pg_playback_status_kernel behind every piece.
  * The audio does not depend on who reports: the same kernels render the same pieces, bit for bit ("Playback status").
  * OUT OF SCOPE: host-fed and rate-converted voices; PlaybackStatusContext payloads (a binding keeps a map from voice id to context); CPU-load
- * measurement; the Sampler's note layer (which forwards its voices' events). */
+ * measurement; the voices of a sampler (pg_graph_add_sampler: its note layer would forward their events). */
 #define PG_STATUS_POSITION 0
 #define PG_STATUS_STOPPED  1
 typedef struct pg_status_event {

@@ -333,6 +333,57 @@ def mono_downmix(pcm, channels):
     return (acc / np.float32(channels)).astype(np.float32)
 
 
+PG_SAMPLER_MAX_VOICES = 64
+SAMPLER_PARAM_IDS = ("STRN", "SFTN", "SVOL", "SPAN")   # Sampler::base_parameters() order (reference src/generator/sampler.rs:120-127)
+UINT64_MAX = 2**64 - 1
+
+
+class SamplerOptions(C.Structure):
+    """pg_sampler_options: voice count, Sampler::with_ahdsr, Sampler::set_loop_range before playback, play_generator / add_generator, start time."""
+    _fields_ = [("voice_count", C.c_uint32), ("has_envelope", C.c_uint32), ("envelope", AhdsrParams), ("has_loop_range", C.c_uint32), ("transient", C.c_uint32),
+                ("loop_start", C.c_uint64), ("loop_end", C.c_uint64), ("start_time", C.c_uint64)]
+
+
+class SamplerSlotState(C.Structure):
+    """pg_sampler_slot_state"""
+    _fields_ = [("note_id", C.c_int64), ("release_start_frame", C.c_uint64), ("note_volume", C.c_float), ("note_panning", C.c_float), ("note", C.c_int32),
+                ("envelope_stage", C.c_int32)]
+
+
+class SamplerState(C.Structure):
+    """pg_sampler_state"""
+    _fields_ = [("voice_count", C.c_int32), ("active_voices", C.c_int32), ("stopping", C.c_int32), ("stopped", C.c_int32), ("transpose", C.c_int32),
+                ("finetune", C.c_int32), ("volume", C.c_float), ("panning", C.c_float), ("slots", SamplerSlotState * PG_SAMPLER_MAX_VOICES)]
+
+
+def sampler_options(voice_count=8, envelope=None, loop_range=None, transient=False, start_time=0):
+    """pg_sampler_options_default with overrides. envelope: an AhdsrParams, a dict of overrides of AhdsrParameters::default(), or None; loop_range:
+    (start, end) in source frames, or None."""
+    o = SamplerOptions(voice_count=int(voice_count), transient=1 if transient else 0, start_time=int(start_time))
+    o.envelope = ahdsr_params()
+    if envelope is not None:
+        o.has_envelope = 1
+        o.envelope = envelope if isinstance(envelope, AhdsrParams) else ahdsr_params(**envelope)
+    if loop_range is not None:
+        o.has_loop_range, o.loop_start, o.loop_end = 1, int(loop_range[0]), int(loop_range[1])
+    return o
+
+
+def sampler_state_dict(st):
+    """A pg_sampler_state as plain values: the sampler's fields and `slots`, one dict per slot of the pool (release_start_frame None = none)."""
+    slots = []
+    for k in range(st.voice_count):
+        s = st.slots[k]
+        import numpy as np
+
+        slots.append(dict(note_id=int(s.note_id), note=int(s.note), note_volume=np.float32(s.note_volume), note_panning=np.float32(s.note_panning),
+                          envelope_stage=int(s.envelope_stage), release_start_frame=None if s.release_start_frame == UINT64_MAX else int(s.release_start_frame)))
+    import numpy as np
+
+    return dict(voice_count=int(st.voice_count), active_voices=int(st.active_voices), stopping=bool(st.stopping), stopped=bool(st.stopped), transpose=int(st.transpose),
+                finetune=int(st.finetune), volume=np.float32(st.volume), panning=np.float32(st.panning), slots=slots)
+
+
 def make_init(params=None, reverb_seeds=None, lfo_seed=None):
     """Build a pg_effect_init. params: dict {fourcc-str: raw value}; reverb_seeds: (fpd_l, fpd_r, [16 phases]); lfo_seed: the four u64 of the
     Delay LFO's Xoshiro256++ state (Random / Smooth Random shapes)."""
@@ -468,6 +519,18 @@ GRAPH_ONLY_CALLS = (
     ("set_fast_math", _int, [_int]),
     ("set_timing_period", _int, [_int]),
     ("set_staged", _int, [_int]),
+    # samplers: the note layer (the sharded handle has none yet)
+    ("add_sampler", _int, [_int, _int, _P(SamplerOptions)]),
+    ("remove_sampler", _int, [_int]),
+    ("sampler_note_on", C.c_int64, [_int, C.c_uint8, _f32, _f32, _u64]),
+    ("sampler_note_off", _int, [_int, C.c_int64, _u64]),
+    ("sampler_all_notes_off", _int, [_int, _u64]),
+    ("sampler_set_note_speed", _int, [_int, C.c_int64, _f64, _f32, _u64]),
+    ("sampler_set_note_volume", _int, [_int, C.c_int64, _f32, _u64]),
+    ("sampler_set_note_panning", _int, [_int, C.c_int64, _f32, _u64]),
+    ("sampler_set_parameter", _int, [_int, _u32, _f32, _int, _u64]),
+    ("sampler_stop", _int, [_int, _u64]),
+    ("sampler_state", _int, [_int, _P(SamplerState)]),
 )
 
 # what only the sharded handle has (pg_sharded_create and _destroy: in load)
@@ -498,6 +561,10 @@ PLAIN_CALLS = (
     ("pg_granular_params_check", _int, [_P(GranularParams)]),
     ("pg_granular_param_count", _int, []),
     ("pg_granular_param", _int, [_int, _P(ParamDesc)]),
+    ("pg_sampler_options_default", None, [_P(SamplerOptions)]),
+    ("pg_sampler_options_check", _int, [_P(SamplerOptions)]),
+    ("pg_sampler_param_count", _int, []),
+    ("pg_sampler_param", _int, [_int, _P(ParamDesc)]),
     ("pg_modulation_params_default", None, [_P(ModulationParams)]),
     ("pg_modulation_params_check", _int, [_P(ModulationParams)]),
     ("pg_debug_sample_buffer_times", _int, [_vp, _int, _P(_f32)]),

@@ -34,6 +34,16 @@ enum CtrlType : int32_t {
   // the granular parameters and loop range of a granular voice, events (GeneratorPlaybackHandle::set_parameter(GOVM .. GSTP), SamplerMessage::SetLoopRange)
   CT_VOICE_GRAIN_PARAM = 13,  // param = index in Sampler::granular_parameters() order, value = resolved raw value
   CT_VOICE_GRAIN_LOOP = 14,   // param = has_loop_range, value = loop_start, value2 = loop_end
+  // a sampler's messages (GeneratorPlaybackHandle, player/handles/generator.rs): id = sampler id, param = note id where there is one; events, but for the removal
+  CT_SAMPLER_NOTE_ON = 15,        // value = volume, value2 = panning, dvalue = note
+  CT_SAMPLER_NOTE_OFF = 16,
+  CT_SAMPLER_ALL_NOTES_OFF = 17,
+  CT_SAMPLER_NOTE_SPEED = 18,     // dvalue = speed, value = glide
+  CT_SAMPLER_NOTE_VOLUME = 19,    // value
+  CT_SAMPLER_NOTE_PAN = 20,       // value
+  CT_SAMPLER_PARAM = 21,          // param = index in Sampler::base_parameters() order, value = resolved raw value
+  CT_SAMPLER_STOP = 22,
+  CT_SAMPLER_REMOVE = 23,         // RemoveSource: a message, not an event
 };
 
 struct CtrlMsg {

@@ -246,6 +246,7 @@ struct PgEnv {
 // host memory that the exact kernel sets when an enveloped voice has ended — the host then takes the voice's unit off the exact kernel again.
 struct PgGrainVoice;
 struct PgStatVoice;
+struct PgSamplerTab;
 struct PgEnvTable {
   int32_t* done;
   uint64_t cap;         // entries behind the header: the kernel takes no entry at or beyond it
@@ -259,9 +260,42 @@ struct PgEnvTable {
   uint32_t n_stats;     // records `stats` holds: no record at or beyond it is taken
   const int32_t* stat_of_voice;
   PgStatVoice* stats;
-  uint64_t pad_stats;
+  // samplers (pg_graph_add_sampler): the records of the note layer (PgSamplerTab below) travel behind the same word; nullptr: the graph never had one
+  PgSamplerTab* samplers;
 };
 static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 64, "the entries follow the header, 16-byte aligned");
+
+// ---- the Sampler's note layer (pg_graph_add_sampler; pg_sampler_dev.h): notes, voice allocation and stealing (src/generator/sampler.rs) ----
+// A sampler is a pool of n_voices file voices (ordinary PgVoice records, device indices voice0 .. voice0 + n_voices - 1, + a PgEnv each when it has
+// an envelope) in ONE sub-mixer unit: the exact kernel's workgroup of that unit applies the sampler's commands in front of their frames, from the
+// state its source stage left in the pool's voices. Slot i is ACTIVE (SamplerVoice::is_active, voice.rs:100-102) iff its voice is `active` and
+// not `finished`: voice_process marks the voice finished in the source write that exhausts the file, lets the fader arrive or finds the
+// envelope Idle — the write in which SamplerVoice::process resets the voice (voice.rs:488-502).
+#define PG_SAMPLER_MAX_VOICES 64   // one wave lane per slot (the reference takes any count, generator.rs:48-72)
+struct PgSamplerSlot {             // the per-note part of SamplerVoice (voice.rs:28-60)
+  uint64_t note_id;                // of the last note the slot was started with (0: none yet); what the voice holds says whether it still plays
+  uint64_t release_start_frame;    // Some(frame) of SamplerVoice::stop (voice.rs:202), UINT64_MAX: None
+  float note_volume, note_panning;
+  int32_t note, pad;
+};
+struct PgSamplerRec {
+  int32_t unit;                    // unit slot of the owning sub-mixer
+  int32_t voice0, n_voices;
+  int32_t has_envelope, transient;
+  int32_t stopping, stopped;       // sampler.rs:733-738, :1011-1024
+  int32_t transpose, finetune;     // base parameters (sampler.rs:1076-1120) ...
+  float base_volume, base_panning;
+  int32_t pad;
+  double pitch_factor;             // ... and 2^(transpose / 12 + finetune / 1200) as the host's libm gives it (voice.rs:146-147)
+  PgSamplerSlot slots[PG_SAMPLER_MAX_VOICES];
+};
+struct PgSamplerTab {
+  uint32_t n, pad;                 // records behind the header: no record at or beyond it is taken
+  const double* speed_tab;         // speed_from_note(0 .. 255) (utils.rs:67-78), host-computed
+  int32_t* stopped;                // mapped host memory, one word per record: set with PgSamplerRec::stopped
+  uint64_t pad_tab;
+};
+static_assert(sizeof(PgSamplerSlot) == 32 && sizeof(PgSamplerRec) == 56 + 32 * PG_SAMPLER_MAX_VOICES && sizeof(PgSamplerTab) == 32, "host and device agree on the layout");
 
 // ---- playback status events (pg_graph_set_voice_status; pg_k_status.hip) ----
 // PlaybackStatusEvent::Position / Stopped are decided once per Source::write call of the voice (src/source/file/preloaded.rs:396-475,
@@ -475,7 +509,18 @@ enum PgCmdType {
   // kernels ignore them):
   CMD_VOICE_GRAIN_PARAM = 15,   // value = the raw value (an enum's index as a float), value64 = index in Sampler::granular_parameters() order   (Sampler::set_granular_parameter)
   CMD_VOICE_GRAIN_LOOP = 16,    // value = loop_start, value64 = has_loop | f32 bits of loop_end << 32                          (GrainPool::set_loop_range)
+  // the messages of a sampler (target = index of its PgSamplerRec; pg_sampler_dev.h applies them in pg_unit_kernel, in front of `frame`). A note id
+  // travels in `param`: the host hands out ids below 2^31.
+  CMD_SAMPLER_NOTE_ON = 17,       // param = note id, value = volume, value64 = note | f32 bits of panning << 32                (Sampler::trigger_note_on)
+  CMD_SAMPLER_NOTE_OFF = 18,      // param = note id                                                                            (trigger_note_off)
+  CMD_SAMPLER_ALL_NOTES_OFF = 19, //                                                                                            (trigger_all_notes_off)
+  CMD_SAMPLER_NOTE_SPEED = 20,    // param = note id, value = glide (semitones/s, <= 0: none), value64 = f64 bits of the speed  (trigger_set_speed)
+  CMD_SAMPLER_NOTE_VOLUME = 21,   // param = note id, value                                                                     (trigger_set_volume)
+  CMD_SAMPLER_NOTE_PAN = 22,      // param = note id, value                                                                     (trigger_set_panning)
+  CMD_SAMPLER_PARAM = 23,         // param = PG_SP_*, value = the resolved raw value, value64 = f64 bits of the new pitch factor (TRANSPOSE / FINETUNE)
+  CMD_SAMPLER_STOP = 24,          //                                                                                            (Sampler::stop)
 };
+enum { PG_SP_TRANSPOSE = 0, PG_SP_FINETUNE, PG_SP_VOLUME, PG_SP_PANNING, PG_SP_COUNT };   // CMD_SAMPLER_PARAM's index: Sampler::base_parameters() (sampler.rs:120-127)
 // CMD_VOICE_GRAIN_PARAM's index: Sampler::granular_parameters() (sampler.rs:283-296)
 enum { PG_GP_OVERLAP_MODE = 0, PG_GP_WINDOW, PG_GP_SIZE, PG_GP_DENSITY, PG_GP_VARIATION, PG_GP_SPRAY, PG_GP_PAN_SPREAD, PG_GP_DIRECTION, PG_GP_POSITION, PG_GP_STEP, PG_GP_COUNT };
 #define PG_MAX_CALLS 64  // calls of one sub-mixer per launch round (bits of PgUnit::call_audible); the host bounds the round accordingly

@@ -121,7 +121,8 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
     }
     // a living voice with a volume envelope: the exact kernel renders it (pg_graph_set_voice_envelope); the mixer's other units keep their kernels
     // (a living granular voice too: the exact kernel's source stage takes what pg_grain_kernel rendered)
-    if (m != 0) for (int v : mx.voices) if (g->voices[v].env_live || g->voices[v].gran_live) u.static_defer = 1;
+    // (a sampler's pool too, for as long as the sampler lives: its note layer runs in the exact kernel's command loop, pg_sampler_dev.h)
+    if (m != 0) for (int v : mx.voices) if (g->voices[v].env_live || g->voices[v].gran_live || g->voices[v].sampler >= 0) u.static_defer = 1;
     // staged pipeline: a sub-mixer whose chain is [Gain (no DC filter) | Panning]* -> Reverb
     u.staged = 0;
     if (m != 0 && !u.static_defer && !mx.fx.empty() && g->fx[mx.fx.back()]->kind == PG_FX_REVERB) {
@@ -553,6 +554,7 @@ int pg_graph_remove_mixer(pg_graph* g, int mixer_id) {
     mx.removed = true;
     g->mixer_alive_tab.set((size_t)gone[i], 0);
   }
+  samplers_of_removed_mixers(g);
   g->topo_dirty = true;
   return PG_OK;
 }
@@ -869,7 +871,7 @@ static bool cmd_is_voice_event(int cmd_type) {
   return false;
 }
 
-static void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd) {
+void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd) {
   HostMixer& mx = g->mixers[mixer];
   Event e{sample_time, g->event_seq++, cmd, mixer};
   size_t pos = mx.events.size();  // partition_point(|e| e.sample_time <= sample_time); automation usually arrives in time order: search from the back
@@ -909,6 +911,7 @@ void drain_control_messages(pg_graph* g) {
       } break;
       case pgc::CT_STOP_ALL: stop_all_voices_now(g); break;
       default: {
+        if (sampler_drain_message(g, m)) break;   // (pg_sampler.hip: SAMPLER_EVENTS)
         if (m.id < 0 || m.id >= (int)g->voices.size() || g->voices[m.id].mixer < 0) break;
         const HostVoice& hv = g->voices[m.id];
         c.target = hv.dev_index; c.param = m.id;
@@ -1480,6 +1483,7 @@ static void collect_piece_commands(pg_graph* g, std::vector<PgCmd>& cmds, uint64
       uint64_t t = mx.events.front().sample_time;
       c.frame = t <= t0 ? 0u : (uint32_t)(t - t0);
       c.unit = mx.unit_slot;
+      sampler_stage_command(g, c);
       cmds.push_back(c);
       mx.events.erase(mx.events.begin());
     }

@@ -1,5 +1,5 @@
 // Internals shared by the host-side translation units of libphonic_gpu.so (pg_host.hip: the mixer graph and its write path;
-// pg_sampler.hip: envelopes, granular voices and their modulation; pg_fxstate.hip: effect construction and parameter descriptors;
+// pg_sampler.hip: envelopes, granular voices and their modulation, sample buffers, samplers; pg_fxstate.hip: effect construction and parameter descriptors;
 // pg_effect.hip: the standalone `Effect` handle; pg_sharded.hip: the multi-GPU handle). Nothing here is part of the ABI (include/phonic_gpu.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -260,6 +260,16 @@ struct HostVoice {
   float* d_trace = nullptr;        // ... of a granular voice: PgGrainVoice::pos_trace (owned by the voice)
   uint32_t file_channels = 0, file_rate = 0;   // the FILE buffer behind the voice: what a Position record divides by (common.rs:195-196) ...
   uint64_t file_samples = 0;                   // ... and its buffer().len() (voice.rs:463)
+  int sampler = -1;                // a pool voice of pg_graph::samplers[sampler] (pg_graph_add_sampler): no public id, its unit stays on the exact kernel
+};
+// A sampler (pg_graph_add_sampler): the pool's place in the graph; the note layer's state is the device's (PgSamplerRec `rec` of pg_graph::d_samp)
+struct HostSampler {
+  int mixer = -1, rec = -1;
+  int voice_id_slot0 = -1;         // the pool's voices were registered last slot first, so that the mixer's list holds them in slot order: slot k has id voice_id_slot0 - k
+  int n_voices = 0;
+  bool has_envelope = false, transient = false;
+  bool alive = true;               // until pg_graph_remove_sampler / the removal of its mixer / `stopped` has been seen
+  int transpose = 0, finetune = 0; // the base pitch as of the last event STAGED (events are staged in time order): what the next pitch factor is made of
 };
 // A sample buffer on the device (pg_graph_add_sample_buffer): AudioFileBuffer behind an Arc (src/source/file/buffer.rs). The host holds one
 // reference until pg_graph_release_sample_buffer, every voice made from it one until its memory is released (graph_voice_release).
@@ -481,6 +491,16 @@ struct pg_graph {
   DeviceTable<int32_t> d_gran_live;      // their records
   std::vector<int32_t> gran_live;        // ... as the next upload puts them together (capacity kept across writes)
   bool gran_live_dirty = false;
+  // samplers (pg_graph_add_sampler): the note layer's records in device memory (header + records, grown by doubling with the graph quiescent),
+  // reached by the exact kernel through the envelope table's header; speed_from_note's table; one `stopped` word per record in mapped host
+  // memory (polled at the top of a write)
+  std::vector<HostSampler> samplers;     // by sampler id (ids are never reused)
+  pgc::ChunkTable<int8_t> sampler_alive_tab;   // sampler id -> 1 while it takes messages (readable from any thread)
+  PgSamplerTab* d_samp = nullptr;
+  size_t samp_cap = 0;                   // records d_samp has room for
+  double* d_speed_tab = nullptr;
+  MappedWords samp_stopped;              // one word per record
+  std::atomic<int64_t> next_note_id{1};  // unique_note_id (generator.rs:32), per graph
   PstatState pstat;                      // playback status events (pg_graph_enable_status)
   std::vector<SampleBuffer> sample_buffers;   // by buffer id (ids are never reused)
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
@@ -531,7 +551,11 @@ int pg_ahdsr_params_check(const pg_ahdsr_params* p);   // the reference's parame
 int graph_env_reserve(pg_graph* g, size_t n);          // mutating calls, graph quiescent: may allocate
 int graph_env_head_refresh(pg_graph* g);               // ... the table's header again, behind a change of a table it names
 void graph_sampler_release(pg_graph* g);
-void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel
+void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel; stopped samplers leave their mixer
+void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd);   // (pg_host.hip) one event into a mixer's sorted list
+bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m);   // drain_control_messages: a sampler's message -> an event of its mixer (false: not a sampler message)
+void sampler_stage_command(pg_graph* g, PgCmd& c);     // an event leaves its mixer's list for a launch (in time order): a base-pitch command gets its pitch factor
+void samplers_of_removed_mixers(pg_graph* g);          // pg_graph_remove_mixer: their ids are dead from here on
 int graph_gran_upload_live(pg_graph* g, hipStream_t stream);
 int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream);
 // sample buffers (pg_sampler.hip; the conversion: pg_k_sample.hip)

@@ -129,6 +129,17 @@ static const ParamSpec GRANULAR_PARAMS[PG_GP_COUNT] = {
     {FCC('G', 'P', 'O', 'S'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.5f, 0, 0, 0, 0, "Position", S_NONE, 0},
     {FCC('G', 'S', 'T', 'P'), PG_PARAM_FLOAT, -4.0f, 4.0f, 0.0f, 0, 0, 0, 0, "Step", S_NONE, 0},
 };
+// The Sampler's base parameters in Sampler::base_parameters() order (src/generator/sampler.rs:98-127): the index is CMD_SAMPLER_PARAM's (PG_SP_*)
+static const ParamSpec SAMPLER_PARAMS[PG_SP_COUNT] = {
+    {FCC('S', 'T', 'R', 'N'), PG_PARAM_INTEGER, -48.0f, 48.0f, 0.0f, 0, 0, 0, 0, "Transpose", S_NONE, 0},
+    {FCC('S', 'F', 'T', 'N'), PG_PARAM_INTEGER, -100.0f, 100.0f, 0.0f, 0, 0, 0, 0, "Finetune", S_NONE, 0},
+    {FCC('S', 'V', 'O', 'L'), PG_PARAM_FLOAT, 0.000001f, 15.848932f, 1.0f, PG_SCALE_DECIBEL, -60.0f, 24.0f, 0, "Volume", S_NONE, 0},
+    {FCC('S', 'P', 'A', 'N'), PG_PARAM_FLOAT, -1.0f, 1.0f, 0.0f, 0, 0, 0, 0, "Panning", S_NONE, 0},
+};
+inline int find_sampler_param(uint32_t fourcc) {
+  for (int i = 0; i < PG_SP_COUNT; ++i) if (SAMPLER_PARAMS[i].fourcc == fourcc) return i;
+  return -1;
+}
 inline int find_granular_param(uint32_t fourcc) {
   for (int i = 0; i < PG_GP_COUNT; ++i) if (GRANULAR_PARAMS[i].fourcc == fourcc) return i;
   return -1;
@@ -188,6 +199,11 @@ inline bool resolve_update(const ParamSpec& p, float value, bool normalized, flo
       float n = h_clamp(value, 0.0f, 1.0f);
       out = (float)(int)std::round(n * (float)(p.n_values - 1));
     }
+    return true;
+  }
+  if (p.type == PG_PARAM_INTEGER) {  // IntegerParameter::clamp_value / denormalize_value (integer.rs:110-126); a raw value is the i32 the float holds, truncated
+    if (!normalized) out = h_clamp(std::trunc(value), p.min, p.max);
+    else out = std::round(p.min + h_clamp(value, 0.0f, 1.0f) * (p.max - p.min));
     return true;
   }
   if (!normalized) out = value != 0.0f ? 1.0f : 0.0f;

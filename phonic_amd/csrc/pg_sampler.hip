@@ -1,6 +1,7 @@
 // Host side of the sampler voices: per-voice AHDSR envelopes (src/utils/ahdsr.rs, src/generator/sampler/voice.rs:181-212), granular voices
 // (src/generator/sampler/granular.rs; rendered by pg_grain_kernel, pg_k_grain.hip), their modulation matrix (src/modulation/matrix.rs,
-// src/generator/sampler/modulation.rs) and the granular parameters that change while a voice plays (src/generator/sampler.rs:299-360).
+// src/generator/sampler/modulation.rs), the granular parameters that change while a voice plays (src/generator/sampler.rs:299-360), sample
+// buffers, and the samplers: pools of file voices whose note, allocation and stealing layer runs on the device (pg_sampler_dev.h).
 // The graph, the control ring's drain and the write path are pg_host.hip's; what crosses between the two files stands in pg_host_internal.h.
 #include "pg_host_internal.h"
 #include "pg_grain_dev.h"   // mod_lfo_reset: the note_on of a voice's modulation matrix runs on the host
@@ -33,10 +34,13 @@ static bool poll_ended(pg_graph* g, std::vector<int>& ids, const MappedWords& wo
   }
   return any;
 }
-// Enveloped voices the exact kernel has reported as ended, granular voices pg_grain_kernel has (they leave its launch list too)
+static void samplers_poll_stopped(pg_graph* g);
+// Enveloped voices the exact kernel has reported as ended, granular voices pg_grain_kernel has (they leave its launch list too); a pool voice of
+// a sampler is not among them: one that ended is started again by a later note
 void graph_sampler_poll(pg_graph* g) {
   if (!g->env_voices.empty()) poll_ended(g, g->env_voices, g->env_done, &HostVoice::dev_index, &HostVoice::env_live);
   if (!g->gran_voices.empty() && poll_ended(g, g->gran_voices, g->gran_ended, &HostVoice::gran, &HostVoice::gran_live)) g->gran_live_dirty = true;
+  samplers_poll_stopped(g);
 }
 
 // The header of envelope table `tab` — its words, its grain_of_voice list, the granular records as the graph holds them now (the graph is quiescent)
@@ -46,6 +50,7 @@ static hipError_t env_head_upload(const pg_graph* g, PgEnvTable* tab, const Mapp
   head.done = done.d; head.cap = done.cap;
   head.grain_of_voice = grain_of_voice; head.grains = g->d_gran; head.n_grains = (uint32_t)g->gran_n;
   head.stat_of_voice = stat_of_voice; head.stats = g->pstat.d_recs; head.n_stats = (uint32_t)g->pstat.n_recs;   // (playback status: pg_k_status.hip)
+  head.samplers = g->d_samp;   // (samplers: below)
   return pg_memcpy(tab, &head, sizeof head, hipMemcpyHostToDevice);
 }
 // The header again, for the tables as the graph holds them now (a table behind it grew: pg_k_status.hip). The graph is quiescent.
@@ -128,6 +133,9 @@ void graph_sampler_release(pg_graph* g) {
   if (g->d_gran) (void)pg_free(g->d_gran);
   if (g->d_grain_lut) (void)pg_free(g->d_grain_lut);
   g->env_done.release(); g->gran_ended.release(); g->d_gran_live.release();
+  if (g->d_samp) (void)pg_free(g->d_samp);
+  if (g->d_speed_tab) (void)pg_free(g->d_speed_tab);
+  g->samp_stopped.release();
 }
 
 // note_on belongs to a voice's start (voice.rs:181-184): neither an envelope nor a matrix for a voice that has rendered frames already.
@@ -584,6 +592,298 @@ int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_sta
   out->velocity = m.velocity; out->note_pitch = m.note_pitch;
   for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
   for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
+  return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- samplers: the note, voice-allocation and stealing layer of Sampler (src/generator/sampler.rs) for file playback. The layer itself runs on the
+// device (pg_sampler_dev.h, in pg_unit_kernel's command loop); here: construction, the message -> event -> command path, removal, the read-back ----
+static_assert(PG_SAMPLER_MAX_VOICES == 64, "the header's and the device's pool size agree (the header defines the same macro)");
+static HostSampler* sampler_find(pg_graph* g, int sampler_id) {   // owner thread: the sampler while it lives, else null (PG_ERR_NOT_FOUND is set)
+  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || !g->samplers[sampler_id].alive) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return nullptr; }
+  return &g->samplers[sampler_id];
+}
+static bool cmd_is_sampler_event(int cmd_type) { return cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP; }
+// The pool leaves its mixer (RemoveSource, a mixer that drops an exhausted generator: mixed.rs:612-616): its voices are retired like removed
+// sources — their buffer references return when their memory is released — and what is still queued for it finds no source when it comes due
+static void sampler_retire(pg_graph* g, int sampler_id) {
+  HostSampler& hs = g->samplers[sampler_id];
+  HostMixer& mx = g->mixers[hs.mixer];
+  for (int k = 0; k < hs.n_voices; ++k) {
+    const int v = hs.voice_id_slot0 - k;
+    if (g->voices[v].mixer < 0) continue;
+    mx.voices.erase(std::remove(mx.voices.begin(), mx.voices.end(), v), mx.voices.end());
+    g->voices[v].mixer = -1;
+    g->retired_voices.push_back(v);
+  }
+  for (Event& e : mx.events) if (cmd_is_sampler_event(e.cmd.type) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
+  hs.alive = false;
+  g->sampler_alive_tab.set((size_t)sampler_id, 0);
+  g->topo_dirty = true;
+}
+void samplers_of_removed_mixers(pg_graph* g) {
+  for (size_t i = 0; i < g->samplers.size(); ++i)
+    if (g->samplers[i].alive && g->mixers[g->samplers[i].mixer].removed) { g->samplers[i].alive = false; g->sampler_alive_tab.set(i, 0); }
+}
+// Transient samplers whose `stopped` word the exact kernel has set: the mixer drops them (reads mapped host words: no wait)
+static void samplers_poll_stopped(pg_graph* g) {
+  for (size_t i = 0; i < g->samplers.size(); ++i) {
+    const HostSampler& hs = g->samplers[i];
+    if (hs.alive && hs.transient && g->samp_stopped[(size_t)hs.rec] != 0) sampler_retire(g, (int)i);
+  }
+}
+// Room for `n` records, their `stopped` words and the header; speed_from_note's table with the first sampler. The graph is quiescent. A failure
+// leaves the graph on its old records.
+static int graph_samp_reserve(pg_graph* g, size_t n) {
+  if (!g->d_speed_tab) {
+    double tab[256];   // speed_from_note (utils.rs:67-78): pitch_from_note(n) / pitch_from_note(60), pitch = 440 * 2^((n - 69) / 12)
+    for (int i = 0; i < 256; ++i) tab[i] = (440.0 * std::pow(2.0, ((double)i - 69.0) / 12.0)) / (440.0 * std::pow(2.0, (60.0 - 69.0) / 12.0));
+    HIP_TRY(pg_malloc((void**)&g->d_speed_tab, sizeof tab));
+    HIP_TRY(pg_memcpy(g->d_speed_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  }
+  if (n <= g->samp_cap) return PG_OK;
+  const size_t cap = std::max<size_t>(next_pow2(n), 4);
+  PgSamplerTab* nt = nullptr;
+  MappedWords stopped;
+  HIP_TRY(pg_malloc((void**)&nt, sizeof(PgSamplerTab) + cap * sizeof(PgSamplerRec)));
+  if (pg_memset(nt, 0, sizeof(PgSamplerTab) + cap * sizeof(PgSamplerRec)) != hipSuccess || stopped.reserve(cap, g->samp_stopped) ||
+      (g->d_samp && pg_memcpy(nt + 1, g->d_samp + 1, g->samplers.size() * sizeof(PgSamplerRec), hipMemcpyDeviceToDevice) != hipSuccess)) {
+    (void)pg_free(nt); stopped.release();
+    return set_error(PG_ERR_DEVICE, "sampler table allocation failed");
+  }
+  if (g->d_samp) (void)pg_free(g->d_samp);
+  g->samp_stopped.release();
+  g->d_samp = nt; g->samp_stopped = stopped; g->samp_cap = cap;
+  return PG_OK;
+}
+static hipError_t samp_head_upload(const pg_graph* g, size_t n) {
+  PgSamplerTab head;
+  memset(&head, 0, sizeof head);
+  head.n = (uint32_t)n; head.speed_tab = g->d_speed_tab; head.stopped = g->samp_stopped.d;
+  return pg_memcpy(g->d_samp, &head, sizeof head, hipMemcpyHostToDevice);
+}
+
+// The timed sampler messages — each becomes an event of the sampler's mixer — with the command a message turns into and what the command carries
+// (pg_dev.h: PgCmdType). The ONE list of them: sampler_drain_message builds the events from it.
+struct SamplerEvent { int32_t msg, cmd; void (*fill)(const pgc::CtrlMsg& m, PgCmd& c); };
+static const SamplerEvent SAMPLER_EVENTS[] = {
+  {pgc::CT_SAMPLER_NOTE_ON, CMD_SAMPLER_NOTE_ON, [](const pgc::CtrlMsg& m, PgCmd& c) { uint32_t pan; memcpy(&pan, &m.value2, 4); c.param = m.param; c.value = m.value; c.value64 = (uint64_t)((int)m.dvalue & 0xff) | ((uint64_t)pan << 32); }},
+  {pgc::CT_SAMPLER_NOTE_OFF, CMD_SAMPLER_NOTE_OFF, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; }},
+  {pgc::CT_SAMPLER_ALL_NOTES_OFF, CMD_SAMPLER_ALL_NOTES_OFF, [](const pgc::CtrlMsg&, PgCmd&) {}},
+  {pgc::CT_SAMPLER_NOTE_SPEED, CMD_SAMPLER_NOTE_SPEED, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }},
+  {pgc::CT_SAMPLER_NOTE_VOLUME, CMD_SAMPLER_NOTE_VOLUME, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},
+  {pgc::CT_SAMPLER_NOTE_PAN, CMD_SAMPLER_NOTE_PAN, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},
+  {pgc::CT_SAMPLER_PARAM, CMD_SAMPLER_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},   // (the pitch factor: sampler_stage_command)
+  {pgc::CT_SAMPLER_STOP, CMD_SAMPLER_STOP, [](const pgc::CtrlMsg&, PgCmd&) {}},
+};
+bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
+  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_REMOVE) return false;
+  if (m.id < 0 || m.id >= (int)g->samplers.size() || !g->samplers[m.id].alive) return true;   // gone in the meantime: dropped
+  if (m.type == pgc::CT_SAMPLER_REMOVE) { sampler_retire(g, m.id); return true; }
+  const HostSampler& hs = g->samplers[m.id];
+  for (const SamplerEvent& se : SAMPLER_EVENTS) if (se.msg == m.type) {
+    PgCmd c;
+    memset(&c, 0, sizeof c);
+    c.type = se.cmd; c.target = hs.rec;
+    se.fill(m, c);
+    push_event(g, hs.mixer, m.sample_time, c);
+    break;
+  }
+  return true;
+}
+// The pitch factor of a base-pitch command is 2^(transpose / 12 + finetune / 1200) of the pair that holds once the command is applied
+// (voice.rs:144-148), with this host's libm. Messages may be sent out of time order, so the pair is tracked here, where a mixer's events leave its
+// sorted list one by one.
+void sampler_stage_command(pg_graph* g, PgCmd& c) {
+  if (c.type != CMD_SAMPLER_PARAM || (c.param != PG_SP_TRANSPOSE && c.param != PG_SP_FINETUNE)) return;
+  for (HostSampler& hs : g->samplers) if (hs.rec == c.target) {
+    if (c.param == PG_SP_TRANSPOSE) hs.transpose = (int)c.value; else hs.finetune = (int)c.value;
+    const double pitch_factor = std::pow(2.0, (double)hs.transpose / 12.0 + (double)hs.finetune / 1200.0);
+    memcpy(&c.value64, &pitch_factor, 8);
+    return;
+  }
+}
+// One sampler message into the control ring (any thread)
+static int sampler_message(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int64_t note_id = 0, float value = 0.0f, float value2 = 0.0f, double dvalue = 0.0) {
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  // (a note id this graph never handed out plays nowhere: 0 is no note's id)
+  m.type = type; m.id = sampler_id; m.param = (note_id > 0 && note_id <= INT32_MAX) ? (int32_t)note_id : 0; m.value = value; m.value2 = value2; m.dvalue = dvalue; m.sample_time = sample_time;
+  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
+  return PG_OK;
+}
+
+extern "C" {
+
+void pg_sampler_options_default(pg_sampler_options* o) {   // GeneratorPlaybackOptions / Sampler::new (generator.rs:48-72): 8 voices, no envelope, not transient
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  o->voice_count = 8;
+  pg_ahdsr_params_default(&o->envelope);
+}
+int pg_sampler_options_check(const pg_sampler_options* o) {
+  if (!o) return set_error(PG_ERR_PARAMETER, "sampler options must not be null");
+  if (o->voice_count < 1 || o->voice_count > PG_SAMPLER_MAX_VOICES) return set_error(PG_ERR_PARAMETER, "Invalid voice count: %u. Must be in range [1, %d]", o->voice_count, PG_SAMPLER_MAX_VOICES);
+  if (o->has_envelope) { const int rc = pg_ahdsr_params_check(&o->envelope); if (rc) return rc; }
+  if (o->has_loop_range && o->loop_start >= o->loop_end) return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu", (unsigned long long)o->loop_start, (unsigned long long)o->loop_end);
+  return PG_OK;
+}
+int pg_sampler_param_count(void) { return PG_SP_COUNT; }
+int pg_sampler_param(int index, pg_param_desc* out) {   // Sampler::base_parameters() (sampler.rs:120-127)
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (index < 0 || index >= PG_SP_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
+  const ParamSpec& p = SAMPLER_PARAMS[index];
+  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
+  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  return PG_OK;
+}
+int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt) {
+  pg_sampler_options def;
+  if (!opt) { pg_sampler_options_default(&def); opt = &def; }
+  { const int rc = pg_sampler_options_check(opt); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (mixer_id == PG_MAIN_MIXER) return -set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, the pool needs one workgroup that sees all of its voices");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  if (!sample_buffer_find(g, buffer_id)) return -PG_ERR_NOT_FOUND;
+  const SampleBuffer sb = g->sample_buffers[buffer_id];
+  if (opt->has_loop_range && (opt->loop_start >= sb.n_frames || opt->loop_end > sb.n_frames)) return -set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%zu", (unsigned long long)opt->loop_start, (unsigned long long)opt->loop_end, sb.n_frames);
+  drain_control_messages(g);
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  const int n = (int)opt->voice_count, sampler_id = (int)g->samplers.size();
+  // a pool voice: PreloadedFileSource::from_shared_buffer(buffer, FilePlaybackOptions::default().fade_out(50 ms), rate) behind AmplifiedSource(1.0) /
+  // PannedSource(0.0) (sampler.rs:505-530, voice.rs:60-65) — a source its mixer keeps, with no note yet: inactive, delivering nothing
+  pg_voice_options vo;
+  pg_voice_options_default(&vo);
+  vo.non_transient = 1; vo.start_time = opt->start_time;
+  PgVoice v;
+  voice_init_neutral(g, v, &vo, 1.0f, 0.0f);
+  v.active = 0;
+  v.pcm = (const float*)sb.d_pcm; v.n_samples = (uint64_t)sb.n_frames * sb.channels; v.channels = sb.channels; v.src_rate = sb.rate; v.out_rate = g->sample_rate;
+  v.ratio = (float)((double)sb.rate / (double)(uint32_t)d2u64((double)g->sample_rate / 1.0));
+  if (!(v.ratio > 0.0f) || v.ratio > 64.0f) return -set_error(PG_ERR_PARAMETER, "Invalid resampling ratio");
+  if (opt->has_loop_range) { v.has_loop = 1; v.loop_start = opt->loop_start; v.loop_end = opt->loop_end; v.repeat = PG_USIZE_MAX; }   // SamplerVoice::set_loop_range (voice.rs:313-328)
+  else if (sb.has_loop) { v.has_loop = 1; v.loop_start = sb.loop_start; v.loop_end = sb.loop_end; v.repeat = PG_USIZE_MAX; }          // the file's embedded loop (preloaded.rs:89-104)
+  v.repeat_count = v.repeat;
+  v.fade_out_seconds = 0.05f;
+  v.current_speed = 1.0; v.target_speed = 1.0;
+  v.sched_class = -1;   // (always on the exact kernel, every note at a speed of its own: no shared resampler schedule)
+  if (graph_samp_reserve(g, g->samplers.size() + 1)) return -graph_fail(g, PG_ERR_DEVICE);
+  int voice0 = -1;
+  for (int k = 0; k < n; ++k) {
+    int di = -1;
+    const int rc = g->d_voices.push(v, &di);
+    if (rc || (k > 0 && di != voice0 + k)) return -graph_fail(g, rc ? rc : set_error(PG_ERR_STATE, "pool voices are not contiguous"));
+    if (k == 0) voice0 = di;
+  }
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + (size_t)n, (size_t)(voice0 + n)))) return -graph_fail(g, PG_ERR_DEVICE);
+  (void)hipSetDevice(g->device);
+  if (opt->has_envelope) {
+    PgEnv e;
+    memset(&e, 0, sizeof e);
+    e.on = 1; e.params = ahdsr_build_params(opt->envelope, g->sample_rate);   // (state: Idle until the slot's first note_on)
+    std::vector<PgEnv> es((size_t)n, e);
+    if (pg_memcpy(g->d_env + voice0, es.data(), es.size() * sizeof(PgEnv), hipMemcpyHostToDevice) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
+  }
+  std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
+  memset(r.get(), 0, sizeof(PgSamplerRec));
+  r->unit = g->mixers[mixer_id].unit_slot; r->voice0 = voice0; r->n_voices = n; r->has_envelope = opt->has_envelope ? 1 : 0; r->transient = opt->transient ? 1 : 0;
+  r->base_volume = 1.0f; r->base_panning = 0.0f; r->pitch_factor = std::pow(2.0, 0.0 / 12.0 + 0.0 / 1200.0);
+  for (int k = 0; k < PG_SAMPLER_MAX_VOICES; ++k) { r->slots[k].release_start_frame = UINT64_MAX; r->slots[k].note = 60; r->slots[k].note_volume = 1.0f; }   // SamplerVoice::new (voice.rs:51-55)
+  if (pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, r.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess || samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess ||
+      graph_env_head_refresh(g)) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
+  g->samp_stopped[(size_t)sampler_id] = 0;
+  // the mixer's list inserts a new source in FRONT of those with the same start time (mixed.rs:324-329): the last slot goes in first, so that the
+  // kernel meets — and sums — the pool in slot order (sampler.rs:989-1006)
+  HostSampler hs;
+  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0;
+  for (int k = n - 1; k >= 0; --k) {
+    HostVoice hv;
+    hv.sbuf = buffer_id; hv.sampler = sampler_id;
+    hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
+    g->sample_buffers[buffer_id].use_count += 1;
+    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
+    if (id < 0) return id;
+    if (k == 0) hs.voice_id_slot0 = id;
+  }
+  g->samplers.push_back(hs);
+  if (!g->sampler_alive_tab.append(1)) return -set_error(PG_ERR_STATE, "too many samplers");
+  return sampler_id;
+}
+int pg_graph_remove_sampler(pg_graph* g, int sampler_id) {
+  const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_REMOVE, 0);
+  if (rc == PG_OK) g->sampler_alive_tab.set((size_t)sampler_id, 0);   // dead for every later call; messages pushed before this one are still delivered
+  return rc;
+}
+int64_t pg_graph_sampler_note_on(pg_graph* g, int sampler_id, uint8_t note, float volume, float panning, uint64_t sample_time) {
+  if (!(volume >= 0.0f) || !std::isfinite(volume)) return -set_error(PG_ERR_PARAMETER, "Invalid note volume: %g. Must be finite and >= 0", (double)volume);
+  if (!std::isfinite(panning)) return -set_error(PG_ERR_PARAMETER, "Invalid note panning: %g. Must be finite", (double)panning);
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return -set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  const int64_t note_id = g->next_note_id.fetch_add(1, std::memory_order_relaxed);
+  if (note_id > INT32_MAX) return -set_error(PG_ERR_STATE, "note ids are used up");
+  const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_ON, sample_time, note_id, volume, panning, (double)note);
+  return rc ? -rc : note_id;
+}
+int pg_graph_sampler_note_off(pg_graph* g, int sampler_id, int64_t note_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_OFF, sample_time, note_id); }
+int pg_graph_sampler_all_notes_off(pg_graph* g, int sampler_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_ALL_NOTES_OFF, sample_time); }
+int pg_graph_sampler_set_note_speed(pg_graph* g, int sampler_id, int64_t note_id, double speed, float glide, uint64_t sample_time) {
+  if (!(speed > 0.0) || !std::isfinite(speed)) return set_error(PG_ERR_PARAMETER, "speed must be > 0");
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_SPEED, sample_time, note_id, glide > 0.0f ? glide : 0.0f, 0.0f, speed);
+}
+int pg_graph_sampler_set_note_volume(pg_graph* g, int sampler_id, int64_t note_id, float volume, uint64_t sample_time) {
+  if (!(volume >= 0.0f) || !std::isfinite(volume)) return set_error(PG_ERR_PARAMETER, "Invalid note volume: %g. Must be finite and >= 0", (double)volume);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_VOLUME, sample_time, note_id, volume);
+}
+int pg_graph_sampler_set_note_panning(pg_graph* g, int sampler_id, int64_t note_id, float panning, uint64_t sample_time) {
+  if (!std::isfinite(panning)) return set_error(PG_ERR_PARAMETER, "Invalid note panning: %g. Must be finite", (double)panning);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_PAN, sample_time, note_id, panning);
+}
+int pg_graph_sampler_set_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  const int pi = find_sampler_param(fourcc);
+  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown sampler parameter 0x%08x", fourcc);
+  if (value != value) return set_error(PG_ERR_PARAMETER, "Sampler parameter '%s' is not a number", SAMPLER_PARAMS[pi].name);
+  if (is_normalized && !(value >= 0.0f && value <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid parameter update: value should be a normalized value, but is: '%g'", (double)value);
+  float raw = 0.0f;
+  (void)resolve_update(SAMPLER_PARAMS[pi], value, is_normalized != 0, raw);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = pgc::CT_SAMPLER_PARAM; m.id = sampler_id; m.param = pi; m.value = raw; m.sample_time = sample_time;
+  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
+  return PG_OK;
+}
+int pg_graph_sampler_stop(pg_graph* g, int sampler_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_STOP, sample_time); }
+int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out) {
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  // (a transient sampler that has stopped keeps its record: the state that says so stays readable until the id is removed or its mixer goes)
+  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
+    return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  const HostSampler& hs = g->samplers[sampler_id];
+  (void)hipSetDevice(g->device);
+  if (g->d_voices.flush()) return PG_ERR_DEVICE;   // (pool voices no write has carried to the device yet)
+  std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
+  std::vector<PgVoice> vs((size_t)hs.n_voices);
+  std::vector<PgEnv> es((size_t)hs.n_voices);
+  { const int rc = graph_read_back(g, r.get(), (const PgSamplerRec*)(g->d_samp + 1) + hs.rec, sizeof(PgSamplerRec)); if (rc) return rc; }
+  { const int rc = graph_read_back(g, vs.data(), g->d_voices.d + r->voice0, vs.size() * sizeof(PgVoice)); if (rc) return rc; }
+  if (hs.has_envelope) { const int rc = graph_read_back(g, es.data(), g->d_env + r->voice0, es.size() * sizeof(PgEnv)); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  out->voice_count = hs.n_voices; out->stopping = r->stopping; out->stopped = r->stopped;
+  out->transpose = r->transpose; out->finetune = r->finetune; out->volume = r->base_volume; out->panning = r->base_panning;
+  for (int k = 0; k < hs.n_voices; ++k) {
+    const bool active = vs[(size_t)k].active != 0 && vs[(size_t)k].finished == 0;   // SamplerVoice::is_active (pg_sampler_dev.h: sampler_slot_active)
+    pg_sampler_slot_state& o = out->slots[k];
+    o.note_id = active ? (int64_t)r->slots[k].note_id : 0;
+    o.release_start_frame = active ? r->slots[k].release_start_frame : UINT64_MAX;   // SamplerVoice::reset clears it (voice.rs:234-235)
+    o.note = r->slots[k].note; o.note_volume = r->slots[k].note_volume; o.note_panning = r->slots[k].note_panning;
+    o.envelope_stage = hs.has_envelope ? (int)es[(size_t)k].state.stage : -1;
+    out->active_voices += active ? 1 : 0;
+  }
   return PG_OK;
 }
 

@@ -12,6 +12,7 @@
 #include "pg_fx_serial.h"
 #include "pg_source_dev.h"
 #include "pg_fx_fast.h"
+#include "pg_sampler_dev.h"
 
 using namespace pgd;
 
@@ -549,7 +550,11 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
       }
       int flush = 0;
       __syncthreads();
-      if (tid == 0) {
+      if (!FAST_ONLY && cmd.type >= CMD_SAMPLER_NOTE_ON && cmd.type <= CMD_SAMPLER_STOP) {
+        // a sampler's message (pg_sampler_dev.h): wave 0, one lane per slot of the pool where a voice is allocated
+        if (tid == 0) ctl[2] = 0;
+        if (tid < 64) sampler_command(L, cmd, pos0 + (uint64_t)frame0);
+      } else if (tid == 0) {
         if (cmd.type == CMD_FX_PARAM) flush = fx_apply_param(L.fx[cmd.target], cmd.param, cmd.value, cmd.value64);
         else if (cmd.type == CMD_VOICE_VOLUME) sm_set_target(L.voices[cmd.target].volume, cmd.value);
         else if (cmd.type == CMD_VOICE_PAN) sm_set_target(L.voices[cmd.target].panning, cmd.value);
@@ -631,6 +636,8 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         audible_input |= (r & 1) != 0;
         later |= r & 2;
       }
+      // (samplers of this mixer: the end of a Sampler::write — a stopping sampler without an active slot is stopped, sampler.rs:1011-1024)
+      if (!FAST_ONLY && seg_last && tid == 0 && PG_UL(kind) == UNIT_SUBMIXER) sampler_end_of_write(L, u);
       if (PG_UL(kind) == UNIT_SOURCE) {  // (no chain: the unit's result is whether its source produced output anywhere in the chunk)
         if (audible_input && tid == 0) { unit.chunk_any_audible = 1; PG_UL(chunk_any_audible) = 1; }
       } else {

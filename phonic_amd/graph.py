@@ -35,6 +35,52 @@ class Graph(GraphHandle):
         self._check(self._lib.pg_debug_sample_buffer_waveform_time(self._h, buffer_id, C.byref(out)))
         return float(out.value)
 
+    # -- samplers: the Sampler generator's note layer (notes, voice allocation, stealing) for file playback; sub-mixers only ----------
+    def add_sampler(self, mixer_id, buffer_id, options=None, **kw):
+        """A pool of `voice_count` file voices of sample buffer `buffer_id` in sub-mixer `mixer_id` (Sampler::from_file + Player::add_generator /
+        play_generator). `options`: a _capi.SamplerOptions, or the keywords of _capi.sampler_options (voice_count, envelope, loop_range, transient,
+        start_time). Returns the sampler id."""
+        o = options if options is not None else _capi.sampler_options(**kw)
+        return self._id(self._lib.pg_graph_add_sampler(self._h, mixer_id, buffer_id, C.byref(o)))
+
+    def remove_sampler(self, sampler):
+        """MixerMessage::RemoveSource: the pool leaves its mixer at the start of the next write."""
+        self._check(self._lib.pg_graph_remove_sampler(self._h, sampler))
+
+    def sampler_note_on(self, sampler, note, volume=1.0, panning=0.0, sample_time=0):
+        """GeneratorPlaybackHandle::note_on in front of frame sample_time (0: the next write's first frame); returns the note id."""
+        return self._id(self._lib.pg_graph_sampler_note_on(self._h, sampler, int(note), float(volume), float(panning), sample_time))
+
+    def sampler_note_off(self, sampler, note_id, sample_time=0):
+        self._check(self._lib.pg_graph_sampler_note_off(self._h, sampler, note_id, sample_time))
+
+    def sampler_all_notes_off(self, sampler, sample_time=0):
+        self._check(self._lib.pg_graph_sampler_all_notes_off(self._h, sampler, sample_time))
+
+    def sampler_set_note_speed(self, sampler, note_id, speed, sample_time=0, glide=None):
+        """set_speed of one note: composed with the base pitch; glide in semitones per second, None = immediate."""
+        self._check(self._lib.pg_graph_sampler_set_note_speed(self._h, sampler, note_id, float(speed), float(glide) if glide else 0.0, sample_time))
+
+    def sampler_set_note_volume(self, sampler, note_id, volume, sample_time=0):
+        self._check(self._lib.pg_graph_sampler_set_note_volume(self._h, sampler, note_id, float(volume), sample_time))
+
+    def sampler_set_note_panning(self, sampler, note_id, panning, sample_time=0):
+        self._check(self._lib.pg_graph_sampler_set_note_panning(self._h, sampler, note_id, float(panning), sample_time))
+
+    def sampler_set_parameter(self, sampler, id4, value, sample_time=0, normalized=False):
+        """One of the base parameters (_capi.SAMPLER_PARAM_IDS: STRN, SFTN, SVOL, SPAN) in front of frame sample_time."""
+        self._check(self._lib.pg_graph_sampler_set_parameter(self._h, sampler, _capi.fourcc(id4), float(value), 1 if normalized else 0, sample_time))
+
+    def sampler_stop(self, sampler, sample_time=0):
+        """Sampler::stop: all notes off; a transient sampler stops for good once its last voice has ended."""
+        self._check(self._lib.pg_graph_sampler_stop(self._h, sampler, sample_time))
+
+    def sampler_state(self, sampler):
+        """The slot table and the sampler's own state as a dict (debug read-back: waits for the graph's work)."""
+        st = _capi.SamplerState()
+        self._check(self._lib.pg_graph_sampler_state(self._h, sampler, C.byref(st)))
+        return _capi.sampler_state_dict(st)
+
     def set_max_blocks_per_launch(self, n_blocks):
         """Offline rendering: let one write call render up to `n_blocks` blocks of max_frames per launch sequence (steady state only)."""
         self._check(self._lib.pg_graph_set_max_blocks_per_launch(self._h, int(n_blocks)))
@@ -184,6 +230,19 @@ def hip_calls():
     out = (C.c_uint64 * 4)()
     _capi.load().pg_debug_hip_calls(out)
     return dict(alloc=out[0], free=out[1], sync=out[2], blocking_copy=out[3])
+
+
+def sampler_parameters():
+    """The four base parameter descriptors of the Sampler (Sampler::base_parameters()), as effect_parameters returns them."""
+    lib = _capi.load()
+    out = []
+    for i in range(lib.pg_sampler_param_count()):
+        d = _capi.ParamDesc()
+        if lib.pg_sampler_param(i, C.byref(d)) != 0:
+            raise PhonicError(_capi.PG_ERR_NOT_FOUND, "parameter")
+        out.append(dict(fourcc=d.fourcc, type=d.type, min=d.min, max=d.max, default=d.default_value, scaling=d.scaling,
+                        scaling_args=(d.scaling_arg0, d.scaling_arg1), n_values=d.n_values, name=d.name.decode()))
+    return out
 
 
 def effect_parameters(kind):
