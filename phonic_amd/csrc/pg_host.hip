@@ -871,11 +871,13 @@ static bool cmd_is_voice_event(int cmd_type) {
   return false;
 }
 
-void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd) {
+void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd, uint64_t stamp) {
   HostMixer& mx = g->mixers[mixer];
-  Event e{sample_time, g->event_seq++, cmd, mixer};
+  if (stamp > sample_time) stamp = sample_time;
+  Event e{sample_time, g->event_seq++, cmd, mixer, stamp};
   size_t pos = mx.events.size();  // partition_point(|e| e.sample_time <= sample_time); automation usually arrives in time order: search from the back
-  while (pos > 0 && mx.events[pos - 1].sample_time > sample_time) --pos;
+  // (events held back to one frame keep the order of the times they were stamped with: everything else has stamp == sample_time)
+  while (pos > 0 && (mx.events[pos - 1].sample_time > sample_time || (mx.events[pos - 1].sample_time == sample_time && mx.events[pos - 1].stamp > stamp))) --pos;
   mx.events.insert(mx.events.begin() + pos, e);
 }
 // MixedSource::process_messages (src/source/mixed.rs:294-499) for the whole graph: the writing thread only.

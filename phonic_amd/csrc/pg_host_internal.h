@@ -225,6 +225,7 @@ struct Event {  // MixerEvent (src/source/mixed.rs:47-109) resolved to a device 
   uint64_t seq;
   PgCmd cmd;  // unit/frame filled per launch
   int mixer;  // owning mixer (0 = main)
+  uint64_t stamp = 0;  // the sample time the message carried: below sample_time only for a message held back to its sampler's start time (pg_sampler.hip)
 };
 
 // What a voice id stands for, as the control calls of any thread see it (pg_graph::voice_alive_tab)
@@ -268,6 +269,7 @@ struct HostSampler {
   int voice_id_slot0 = -1;         // the pool's voices were registered last slot first, so that the mixer's list holds them in slot order: slot k has id voice_id_slot0 - k
   int n_voices = 0;
   bool has_envelope = false, transient = false;
+  uint64_t start_time = 0;         // the mixer does not call the sampler before this frame: messages due earlier are held until it (sampler_drain_message)
   bool alive = true;               // until pg_graph_remove_sampler / the removal of its mixer / `stopped` has been seen
   int transpose = 0, finetune = 0; // the base pitch as of the last event STAGED (events are staged in time order): what the next pitch factor is made of
 };
@@ -552,7 +554,7 @@ int graph_env_reserve(pg_graph* g, size_t n);          // mutating calls, graph 
 int graph_env_head_refresh(pg_graph* g);               // ... the table's header again, behind a change of a table it names
 void graph_sampler_release(pg_graph* g);
 void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel; stopped samplers leave their mixer
-void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd);   // (pg_host.hip) one event into a mixer's sorted list
+void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd, uint64_t stamp = UINT64_MAX);   // (pg_host.hip) one event into a mixer's sorted list; stamp: Event::stamp, default = sample_time
 bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m);   // drain_control_messages: a sampler's message -> an event of its mixer (false: not a sampler message)
 void sampler_stage_command(pg_graph* g, PgCmd& c);     // an event leaves its mixer's list for a launch (in time order): a base-pitch command gets its pitch factor
 void samplers_of_removed_mixers(pg_graph* g);          // pg_graph_remove_mixer: their ids are dead from here on

@@ -687,7 +687,17 @@ bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
     memset(&c, 0, sizeof c);
     c.type = se.cmd; c.target = hs.rec;
     se.fill(m, c);
-    push_event(g, hs.mixer, m.sample_time, c);
+    // The mixer does not call a source before its start time (mixed.rs:565-576); a trigger that comes due earlier only goes into the generator's
+    // queue (mixed.rs:902-918), and the sampler drains that queue at the top of its first write, whose first frame is `now` for all of them
+    // (sampler.rs:656-731). So such a message becomes an event AT the start time, ordered among those by the time it was stamped with and
+    // then by sending order, as the mixer would have queued them. The mixer still cuts its chunk where the message came due: a no-op event.
+    if (m.sample_time < hs.start_time) {
+      PgCmd nop;
+      memset(&nop, 0, sizeof nop);
+      nop.type = CMD_NOP;
+      push_event(g, hs.mixer, m.sample_time, nop);
+      push_event(g, hs.mixer, hs.start_time, c, m.sample_time);
+    } else push_event(g, hs.mixer, m.sample_time, c);
     break;
   }
   return true;
@@ -798,7 +808,7 @@ int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_samp
   // the mixer's list inserts a new source in FRONT of those with the same start time (mixed.rs:324-329): the last slot goes in first, so that the
   // kernel meets — and sums — the pool in slot order (sampler.rs:989-1006)
   HostSampler hs;
-  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0;
+  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
   for (int k = n - 1; k >= 0; --k) {
     HostVoice hv;
     hv.sbuf = buffer_id; hv.sampler = sampler_id;

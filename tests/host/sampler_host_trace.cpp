@@ -83,6 +83,9 @@ int main() {
     ids.push_back(id);
   }
   CHECK(pg_graph_sampler_note_on(g, s1, 60, 1.0f, 0.0f, 900) > last);
+  // s1 starts at frame 500: messages due earlier are held until then (each leaves a no-op event where it came due), sent out of time order
+  CHECK(pg_graph_sampler_note_on(g, s1, 62, 1.0f, 0.0f, 300) > last && pg_graph_sampler_set_parameter(g, s1, PG_FOURCC('S', 'V', 'O', 'L'), 0.5f, 0, 100) == PG_OK);
+  CHECK(pg_graph_sampler_note_off(g, s1, 12345678, 499) == PG_OK && pg_graph_sampler_note_on(g, s1, 64, 1.0f, 0.0f, 500) > last && pg_graph_sampler_all_notes_off(g, s1, 7) == PG_OK);
   CHECK(pg_graph_sampler_set_parameter(g, s0, PG_FOURCC('S', 'T', 'R', 'N'), 7.0f, 0, 4000) == PG_OK);
   CHECK(pg_graph_sampler_set_parameter(g, s0, PG_FOURCC('S', 'F', 'T', 'N'), 0.25f, 1, 2000) == PG_OK);   // sent later, due earlier
   CHECK(pg_graph_sampler_set_parameter(g, s0, PG_FOURCC('S', 'V', 'O', 'L'), 100.0f, 0, 0) == PG_OK);      // clamped

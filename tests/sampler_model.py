@@ -125,12 +125,15 @@ class Note:
     def __init__(self, note_id, slot, start, note, volume, panning, speed, inherited_volume, inherited_panning, volume_target, panning_target):
         self.note_id, self.slot, self.start, self.end = note_id, slot, start, None   # end: the frame it was stolen at, or behind the write that freed it
         self.stolen = False
+        self.stolen_releasing = False                     # stolen while its envelope was in Release
+        self.stole = None                                 # the id of the note this one took its slot from, None: the slot was free
         self.note, self.volume, self.panning = note, volume, panning
         self.inherited_volume, self.inherited_panning = inherited_volume, inherited_panning   # the smoothers' `current` as start() found them
         self.speed_events = [(start, speed, None)]        # (frame, effective speed, glide or None)
         self.volume_events = [(start, volume_target)]     # (frame, set_target value)
         self.panning_events = [(start, panning_target)]
         self.stop_frames = []                             # PreloadedFileSource::stop() calls (no envelope)
+        self.release_frames = []                          # AhdsrEnvelope::note_off calls (with an envelope)
         self.gains = []                                   # with an envelope: one f32 per rendered frame from `start`
 
 
@@ -157,10 +160,15 @@ class Voice:
 
 
 class SamplerModel:
-    def __init__(self, sample_rate, buffer_frames, channels, file_rate, voice_count=8, envelope=None, loop_range=None, transient=False, note_ids=None):
+    def __init__(self, sample_rate, buffer_frames, channels, file_rate, voice_count=8, envelope=None, loop_range=None, transient=False, note_ids=None,
+                 start_time=0, extra_cuts=()):
         """buffer_frames counts the frames the device gets (the decoder's extra zero frame included). envelope: keywords of ahdsr_model.Params
         or None. loop_range: the active loop range in source frames (Sampler::set_loop_range, or the buffer's embedded one) or None.
-        note_ids: a one-element list shared by the samplers of one graph (unique_note_id)."""
+        note_ids: a one-element list shared by the samplers of one graph (unique_note_id).
+        start_time: the sample time the owning mixer starts the sampler at (mixed.rs:565-576): no `write` reaches it before that frame, the first
+        one begins exactly there when the frame lies inside a chunk, and the messages that came due earlier wait in its queue (mixed.rs:902-918)
+        until the top of that write. extra_cuts: sample times of the owning mixer's OTHER events (a second sampler's messages, an ordinary
+        voice's events): the mixer cuts its chunk there too (mixed.rs:679-712)."""
         self.sr, self.buffer_frames, self.channels, self.file_rate = sample_rate, buffer_frames, channels, file_rate
         self.env_params = A.Params(sample_rate, **envelope) if envelope is not None else None
         self.loop_range, self.transient = loop_range, transient
@@ -173,6 +181,7 @@ class SamplerModel:
         self.note_ids = note_ids if note_ids is not None else [0]
         self.notes = {}
         self.pos = 0
+        self.start_time, self.extra_cuts = int(start_time), sorted(set(int(t) for t in extra_cuts))
 
     # ---- the handle's calls: (sample_time, seq, fn) ----
     def _send(self, t, fn):
@@ -266,6 +275,7 @@ class SamplerModel:
         v.release_start_frame = now
         if self.env_params is not None:
             v.env.note_off(self.env_params)
+            v.rec.release_frames.append(now)
         else:
             v.file.stop()
             v.rec.stop_frames.append(now)
@@ -287,8 +297,10 @@ class SamplerModel:
     def _note_on(self, nid, note, volume, panning, now):   # trigger_note_on + SamplerVoice::start (voice.rs:122-193)
         i = self.next_free_voice_index()
         v = self.voices[i]
-        if v.is_active():
-            v.rec.end, v.rec.stolen = now, True
+        victim = v.rec if v.is_active() else None
+        if victim is not None:
+            victim.end, victim.stolen = now, True
+            victim.stolen_releasing = self.env_params is not None and v.env.stage == A.RELEASE
         v.reset()
         v.note, v.note_volume, v.note_panning = note, volume, panning
         eff = speed_from_note(note) * pitch_factor(self.transpose, self.finetune)
@@ -304,6 +316,7 @@ class SamplerModel:
             v.env.note_on(self.env_params, 1.0)
         v.note_id = nid
         v.rec = Note(nid, i, now, note, volume, panning, eff, inherited[0], inherited[1], vt, pt)
+        v.rec.stole = victim.note_id if victim is not None else None
         self.notes[nid] = v.rec
         self.active_voices += 1
 
@@ -349,9 +362,14 @@ class SamplerModel:
             done = 0
             while done < main_chunk:
                 now = pos + total + done
-                later = [q[0] for q in self.queue if q[0] > now]
+                later = [q[0] for q in self.queue if q[0] > now] + [t for t in self.extra_cuts if t > now]
                 n = min(main_chunk - done, min(later) - now) if later else main_chunk - done
-                self._write_chunk(n, now)
+                if now + n <= self.start_time:        # process_sources skips a source that starts behind this chunk (mixed.rs:565-573)
+                    pass
+                elif now < self.start_time:           # ... and writes one that starts inside it from its start time on (:574-582)
+                    self._write_chunk(now + n - self.start_time, self.start_time)
+                else:
+                    self._write_chunk(n, now)
                 done += n
             total += main_chunk
         self.pos = pos + frames

@@ -14,177 +14,12 @@ import numpy as np
 import pytest
 
 import oracle
-import sampler_model as M
 from phonic_amd import _capi, workloads
 from phonic_amd._wrap import PhonicError
 from phonic_amd.graph import Graph
+from sampler_rig import ENV, LONG, MF, SHORT, SR, UNKNOWN, Rig, _assert_equal, _note_audio, _run, _single, expected_audio, resolve  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-SR = 48000
-MF = 1024
-SHORT = workloads.tone_buffer(1, SR, 6000 / SR)    # 6001 frames: ends by itself
-LONG = workloads.tone_buffer(2, SR, 4.0)           # 192001 frames: outlasts 1.5 s at any speed used here
-ENV = dict(attack_s=0.01, hold_s=0.05, decay_s=0.05, sustain_level=0.75, release_s=0.1)
-UNKNOWN = 999999
-
-
-def _frames(pcm):
-    return pcm.size // 2
-
-
-def _db_to_linear(x):
-    lib = oracle.lib()
-    return np.float32(lib.po_db_to_linear(np.float32(x)))
-
-
-def resolve(name, value, normalized):
-    """The raw value a parameter update resolves to (sampler.rs:862-906; integer.rs:110-126, float.rs:137-141, scaling.rs:45-74), from the
-    descriptors' constants: STRN -48..48, SFTN -100..100, SVOL 0.000001..15.848932 Decibel(-60, 24), SPAN -1..1."""
-    f = np.float32
-    if name in ("transpose", "finetune"):
-        lo, hi = (-48, 48) if name == "transpose" else (-100, 100)
-        if not normalized:
-            return int(min(max(int(value), lo), hi))
-        x = f(f(lo) + f(f(value) * f(hi - lo)))
-        return int(np.floor(abs(x) + f(0.5)) * np.sign(x))   # f32::round: half away from zero
-    lo, hi = (f(0.000001), f(15.848932)) if name == "volume" else (f(-1.0), f(1.0))
-    if not normalized:
-        return f(min(max(f(value), lo), hi))
-    n = f(value)
-    if name == "volume":
-        db = f(f(-60.0) + f(n * f(f(24.0) - f(-60.0))))
-        mn, mx = _db_to_linear(-60.0), _db_to_linear(24.0)
-        n = f(f(_db_to_linear(db) - mn) / f(mx - mn))
-    return f(lo + f(n * f(hi - lo)))
-
-
-PARAM_ID = dict(transpose="STRN", finetune="SFTN", volume="SVOL", panning="SPAN")
-
-
-class Rig:
-    """One sampler on the GPU and its model, driven by the same calls."""
-
-    def __init__(self, g, mixer, pcm, note_ids, voice_count, envelope=None, transient=False):
-        self.g, self.pcm = g, pcm
-        self.buf = g.add_sample_buffer(pcm, 2, SR)
-        self.s = g.add_sampler(mixer, self.buf, voice_count=voice_count, envelope=envelope, transient=transient)
-        self.m = M.SamplerModel(SR, _frames(pcm), 2, SR, voice_count=voice_count, envelope=envelope, transient=transient, note_ids=note_ids)
-        self.ids = []
-
-    def _id(self, k):
-        return UNKNOWN if k is None else self.ids[k]
-
-    def on(self, t, note, volume=1.0, panning=0.0):
-        a, b = self.g.sampler_note_on(self.s, note, volume, panning, t), self.m.note_on(note, volume, panning, t)
-        assert a == b, (a, b)
-        self.ids.append(a)
-        return len(self.ids) - 1
-
-    def off(self, t, k):
-        self.g.sampler_note_off(self.s, self._id(k), t)
-        self.m.note_off(self._id(k), t)
-
-    def all_off(self, t):
-        self.g.sampler_all_notes_off(self.s, t)
-        self.m.all_notes_off(t)
-
-    def speed(self, t, k, speed, glide=None):
-        self.g.sampler_set_note_speed(self.s, self._id(k), speed, t, glide)
-        self.m.set_note_speed(self._id(k), speed, t, glide)
-
-    def vol(self, t, k, v):
-        self.g.sampler_set_note_volume(self.s, self._id(k), v, t)
-        self.m.set_note_volume(self._id(k), v, t)
-
-    def pan(self, t, k, p):
-        self.g.sampler_set_note_panning(self.s, self._id(k), p, t)
-        self.m.set_note_panning(self._id(k), p, t)
-
-    def param(self, t, name, value, normalized=False):
-        self.g.sampler_set_parameter(self.s, PARAM_ID[name], value, t, normalized)
-        self.m.set_parameter(name, resolve(name, value, normalized), t)
-
-    def stop(self, t):
-        self.g.sampler_stop(self.s, t)
-        self.m.stop(t)
-
-    def check_state(self, where):
-        got, exp = self.g.sampler_state(self.s), self.m.state()
-        slots_g, slots_e = got.pop("slots"), exp.pop("slots")
-        assert got == exp, (where, got, exp)
-        for i, (a, b) in enumerate(zip(slots_g, slots_e)):
-            assert a == b, (where, i, a, b)
-
-
-def _single(pcm, voice_count, envelope=None, transient=False):
-    g = Graph(SR, 2, MF, 0)
-    return g, Rig(g, g.add_mixer(), pcm, [0], voice_count, envelope, transient)
-
-
-def _run(g, rigs, sizes):
-    """The writes; after every one, every sampler's state against its model."""
-    out, pos = [], 0
-    for k, n in enumerate(sizes):
-        buf = np.zeros(2 * n, dtype=np.float32)
-        g.write(buf, pos)
-        for r in rigs:
-            r.m.write(n, pos)
-            r.check_state((k, pos + n))
-        pos += n
-        out.append(buf)
-    assert g.device_errors() == 0
-    return np.concatenate(out)
-
-
-def _note_audio(rec, pcm, n_frames):
-    """One note as an ordinary oracle voice (stereo frames x 2), uncut and without its envelope. A mixer holds ONE stop time per source, so every
-    stop() of the note is sent when the oracle's writes have reached its frame: the writes are cut there (how a source's audio is cut into writes
-    changes none of its samples)."""
-    o = oracle.OracleGraph(SR, 2, MF)
-    mx = o.add_mixer()
-    first = (rec.start // MF) * MF
-    v = o.add_voice(mx, pcm, 2, SR, volume=float(rec.inherited_volume), panning=float(rec.inherited_panning), speed=rec.speed_events[0][1], start_time=rec.start)
-    for t, x in rec.volume_events:
-        o.set_voice_volume(v, float(x), t)
-    for t, x in rec.panning_events:
-        o.set_voice_panning(v, float(x), t)
-    for t, sp, gl in rec.speed_events[1:]:
-        o.set_voice_speed(v, sp, t, glide=gl)
-    end = rec.end if rec.end is not None else n_frames
-    last = min(((end + MF - 1) // MF) * MF, n_frames)
-    audio = np.zeros((n_frames, 2), np.float32)
-    cuts = sorted(set(list(range(first, last, MF)) + [t for t in rec.stop_frames if first < t < last]) | {last})
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        if a in rec.stop_frames:
-            o.stop_voice(v, a)
-        buf = np.zeros(2 * (b - a), np.float32)
-        o.write(buf, a)
-        audio[a:b] = buf.reshape(-1, 2)
-    return audio
-
-
-def expected_audio(model, pcm, n_frames):
-    slots = [np.zeros((n_frames, 2), np.float32) for _ in model.voices]
-    for rec in model.notes.values():
-        a = _note_audio(rec, pcm, n_frames)
-        end = min(rec.end if rec.end is not None else n_frames, n_frames)
-        a[end:] = 0.0
-        if model.env_params is not None:
-            gains = np.zeros(n_frames, np.float32)
-            k = min(len(rec.gains), n_frames - rec.start)
-            gains[rec.start:rec.start + k] = np.asarray(rec.gains[:k], np.float32)
-            a = (a * gains[:, None]).astype(np.float32)
-        slots[rec.slot] = (slots[rec.slot] + a).astype(np.float32)
-    out = np.zeros((n_frames, 2), np.float32)
-    for s in slots:   # the sampler's sum: its active voices in slot order (sampler.rs:989-1006)
-        out = (out + s).astype(np.float32)
-    return out.reshape(-1)
-
-
-def _assert_equal(got, exp):
-    assert np.abs(exp).max() > 1e-3
-    assert np.array_equal(got, exp), (int(np.flatnonzero(got != exp)[0]) // 2, float(np.abs(got - exp).max()))
 
 
 def _slots(r):
