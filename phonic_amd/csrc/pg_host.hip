@@ -238,7 +238,6 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
 
 // Per-unit output tables the write path needs: one per block of a super-block launch, and one per piece of a chunk (the mixer sum runs
 // behind a chunk's last piece).
-static size_t graph_table_blocks(const pg_graph* g) { return std::max<size_t>(g->max_blocks, (PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames); }
 // Device capacity for the graph as the host mirror describes it now. Called at the end of every mutating call (after graph_quiesce):
 // this is where the library allocates — grow-by-doubling — so that rebuild_topology and everything else inside write never does.
 static int graph_reserve(pg_graph* g) {
@@ -380,7 +379,7 @@ pg_graph* pg_graph_create(uint32_t sample_rate, uint32_t channel_count, size_t m
   // staging of pg_graph_write (host buffers): whole chunks, so at least one of PG_MAX_FRAMES frames; one `audible` word per piece of a chunk
   // (and per block of a super-block launch)
   g->bus_frames = std::max<size_t>(max_frames, PG_MAX_FRAMES);
-  g->audible_slots = std::max<size_t>(PG_AUDIBLE_SLOTS, (PG_MAX_FRAMES + max_frames - 1) / max_frames);
+  g->audible_slots = audible_table_words(max_frames);
   if (pg_malloc((void**)&g->d_bus, (2 * g->bus_frames + 4) * sizeof(float)) != hipSuccess || pg_malloc((void**)&g->d_audible, g->audible_slots * sizeof(int)) != hipSuccess ||
       pg_host_malloc((void**)&g->h_pinned, (2 * g->bus_frames + 4) * sizeof(float), hipHostMallocDefault) != hipSuccess) {
     set_error(PG_ERR_DEVICE, "device allocation failed");
@@ -851,25 +850,38 @@ int pg_graph_remove_voice(pg_graph* g, int voice_id) {  // MixerMessage::RemoveS
 }  // extern "C"
 
 // The timed voice messages — each becomes an event of the voice's mixer — with the command a message turns into and what the command carries
-// beyond its voice (pg_dev.h: PgCmdType). The ONE list of them: drain_control_messages builds the events from it, and the removal of a source
-// finds the source's queued events by it.
-struct VoiceEvent { int32_t msg, cmd; void (*fill)(const pgc::CtrlMsg& m, uint32_t sample_rate, PgCmd& c); };
+// beyond its voice (pg_dev.h: PgCmdType). The ONE list of them: drain_control_messages builds the events from it, the removal of a source
+// finds the source's queued events by it, and the write path asks it what a command leaves behind (cmd_keeps_steady).
+// keeps_steady: the command changes nothing the time-parallel kernels do not render — AmplifiedSource / PannedSource smoothers, the fader, a new
+// position, an envelope's release; the matrix's and the granular parameters' commands reach pg_grain_kernel only — so a unit deferred for it alone is
+// back on its kernel in the next block and the host need not wait for the device to say so. A speed command may start a glide: it is not.
+struct VoiceEvent { int32_t msg, cmd; bool keeps_steady; void (*fill)(const pgc::CtrlMsg& m, uint32_t sample_rate, PgCmd& c); };
 static const VoiceEvent VOICE_EVENTS[] = {
-  {pgc::CT_VOICE_VOLUME, CMD_VOICE_VOLUME, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
-  {pgc::CT_VOICE_PAN, CMD_VOICE_PAN, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
-  {pgc::CT_VOICE_SPEED, CMD_VOICE_SPEED, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }},
-  {pgc::CT_VOICE_SEEK, CMD_VOICE_SEEK, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { memcpy(&c.value64, &m.dvalue, 8); }},
-  {pgc::CT_VOICE_RELEASE, CMD_VOICE_RELEASE, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = m.sample_time; }},
-  {pgc::CT_VOICE_MOD_ROUTE, CMD_VOICE_MOD_ROUTE, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
-  {pgc::CT_VOICE_LFO_RATE, CMD_VOICE_LFO_RATE, [](const pgc::CtrlMsg& m, uint32_t sr, PgCmd& c) { c.value = (float)((double)m.value / (double)sr); c.value64 = (uint64_t)(uint32_t)m.param; }},   // Lfo::set_rate (lfo.rs:102-104)
-  {pgc::CT_VOICE_LFO_WAVEFORM, CMD_VOICE_LFO_WAVEFORM, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = (uint64_t)(uint32_t)m.param; }},
-  {pgc::CT_VOICE_GRAIN_PARAM, CMD_VOICE_GRAIN_PARAM, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
-  {pgc::CT_VOICE_GRAIN_LOOP, CMD_VOICE_GRAIN_LOOP, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { uint32_t end; memcpy(&end, &m.value2, 4); c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)end << 32); }},
+  {pgc::CT_VOICE_VOLUME, CMD_VOICE_VOLUME, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
+  {pgc::CT_VOICE_PAN, CMD_VOICE_PAN, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; }},
+  {pgc::CT_VOICE_SPEED, CMD_VOICE_SPEED, false, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }},
+  {pgc::CT_VOICE_SEEK, CMD_VOICE_SEEK, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { memcpy(&c.value64, &m.dvalue, 8); }},
+  {pgc::CT_VOICE_RELEASE, CMD_VOICE_RELEASE, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = m.sample_time; }},
+  {pgc::CT_VOICE_MOD_ROUTE, CMD_VOICE_MOD_ROUTE, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_LFO_RATE, CMD_VOICE_LFO_RATE, true, [](const pgc::CtrlMsg& m, uint32_t sr, PgCmd& c) { c.value = (float)((double)m.value / (double)sr); c.value64 = (uint64_t)(uint32_t)m.param; }},   // Lfo::set_rate (lfo.rs:102-104)
+  {pgc::CT_VOICE_LFO_WAVEFORM, CMD_VOICE_LFO_WAVEFORM, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_GRAIN_PARAM, CMD_VOICE_GRAIN_PARAM, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_VOICE_GRAIN_LOOP, CMD_VOICE_GRAIN_LOOP, true, [](const pgc::CtrlMsg& m, uint32_t, PgCmd& c) { uint32_t end; memcpy(&end, &m.value2, 4); c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)end << 32); }},
 };
-static bool cmd_is_voice_event(int cmd_type) {
-  for (const VoiceEvent& ve : VOICE_EVENTS) if (ve.cmd == cmd_type) return true;
-  return false;
+static const VoiceEvent* voice_event_of_cmd(int cmd_type) {
+  for (const VoiceEvent& ve : VOICE_EVENTS) if (ve.cmd == cmd_type) return &ve;
+  return nullptr;
 }
+static bool cmd_is_voice_event(int cmd_type) { return voice_event_of_cmd(cmd_type) != nullptr; }
+// Can the command NOT leave the steady state behind it? A voice event says so itself; a StopSource message (not an event: pg_graph_stop_voice) cannot.
+// Everything else can: a parameter command may start a smoother of an effect (the device knows how long: the next rounds' scans tell), a sampler's
+// command starts notes, markers belong to split chunks.
+static bool cmd_keeps_steady(int cmd_type) {
+  const VoiceEvent* ve = voice_event_of_cmd(cmd_type);
+  return ve ? ve->keeps_steady : cmd_type == CMD_VOICE_STOP;
+}
+// Is the command addressed to the main mixer's bus chain (its unit: HostMixer::unit_slot of mixer 0) rather than to a source of the main mixer?
+static bool cmd_is_bus_chain(int cmd_type) { return cmd_type == CMD_FX_PARAM || cmd_type == CMD_FX_RESET || cmd_type == CMD_NOP; }
 
 void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd, uint64_t stamp) {
   HostMixer& mx = g->mixers[mixer];
@@ -1145,7 +1157,7 @@ double pg_graph_kernel_ms(pg_graph* g, int reset, uint64_t* launches) {
 // nothing deferred, and units leave the steady state only through those host-visible events.
 static bool graph_steady(const pg_graph* g) {
   if (!(g->fast && g->levels.size() == 1 && g->n_static_defer == 0 && g->d_feedback)) return false;
-  // word 3: (round << 32 | units that round deferred for their STATE); units deferred for a command alone do not count — see cmd_may_ramp
+  // word 3: (round << 32 | units that round deferred for their STATE); units deferred for a command alone do not count — see cmd_keeps_steady
   const unsigned long long fb = *(volatile unsigned long long*)(g->h_feedback + 3);
   return fb != ~0ull && (uint32_t)fb == 0u && (int32_t)((uint32_t)(fb >> 32) - (uint32_t)g->last_change_round) >= 0;
 }
@@ -1204,7 +1216,6 @@ static void bus_pipeline_setup(pg_graph* g, PgLaunch& B) {
   }
 }
 
-#define HIP_TRY_FAIL(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { set_error(PG_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e)); g->failed = true; return 0; } } while (0)
 // The unit kernels of ONE level of the mixer tree for n_chunks blocks of n frames starting at t0: block c goes to the per-unit output table
 // `row_block + c` (a chunk's pieces sit in consecutive tables; the mixer sum and the bus chain run behind a chunk's last piece). `round`: the
 // launch round the blocks belong to (deferral feedback, schedule-cache bank); grid_off / grid_span: PgLaunch (pg_dev.h).
@@ -1220,6 +1231,14 @@ struct LaunchSpan {
   bool timed = false;        // a hipEvent pair is reserved for this span (g->ev_used names it)
   bool generic_idle = false;
   const PgCmd* h_cmds = nullptr;   // the round's commands travel as an argument of its decision-scan kernel (no copy was enqueued): the pinned list
+  int row_step = 1;          // output tables between consecutive blocks (0: a bus the caller holds — no per-unit rows behind it, process_bus_impl)
+  // the span without its first `blocks` blocks (and without commands: they are due at the span's first frame)
+  LaunchSpan behind(int blocks) const {
+    LaunchSpan r = *this;
+    r.d_cmds = nullptr; r.h_cmds = nullptr; r.n_cmds = 0;
+    r.t0 += (uint64_t)n * (uint64_t)blocks; r.grid_off += n * (uint32_t)blocks; r.n_chunks -= blocks; r.row_block += row_step * blocks;
+    return r;
+  }
 };
 static void fill_launch(pg_graph* g, const LaunchSpan& sp, PgLaunch& L) {
   memset(&L, 0, sizeof L);
@@ -1397,7 +1416,10 @@ bool graph_is_empty(const pg_graph* g) {
   for (size_t m = 1; m < g->mixers.size(); ++m) no_sub_mixers &= g->mixers[m].removed;
   return g->main_active_voices == 0 && g->mixers[0].fx.empty() && no_sub_mixers && g->mixers[0].events.empty();
 }
-uint64_t graph_next_main_event(const pg_graph* g) { return g->mixers[0].events.empty() ? UINT64_MAX : g->mixers[0].events.front().sample_time; }
+uint64_t graph_frames_to_main_event(const pg_graph* g, uint64_t now) {
+  for (const Event& e : g->mixers[0].events) if (e.sample_time > now) return e.sample_time - now;
+  return UINT64_MAX;
+}
 // The number of main-mixer sources still alive -> the graph's mapped status word, behind everything enqueued on `stream` so far;
 // graph_collect_status reads it once the stream has drained.
 int graph_enqueue_status(pg_graph* g, hipStream_t stream) {
@@ -1415,33 +1437,35 @@ void graph_collect_status(pg_graph* g) {
   g->main_active_voices = *(volatile int*)(g->h_feedback + 1);
 }
 
-// The bus chain over blocks [row_block, +n_chunks) of a chunk (or of several whole chunks) whose sum sits in d_dst. Commands (main-mixer
-// effect events, due at the chunk's first frame) ride on a launch of the first block alone: a launch that walks several blocks applies nothing.
-static int launch_bus(pg_graph* g, float* d_dst, LaunchSpan sp, int audible_slot, hipStream_t stream) {
+// A chunk's pieces as launches that take runs of equal blocks: its full pieces in one, a shorter last piece in one of its own.
+// launch(first piece, pieces) returns PG_OK or an error, which ends the walk.
+template <class F>
+static int full_then_last(const ChunkPieces& c, F launch) {
+  if (c.n_full() > 0) { const int rc = launch((uint64_t)0, c.n_full()); if (rc) return rc; }
+  return c.n_pieces() > c.n_full() ? launch(c.n_full(), (uint64_t)1) : PG_OK;
+}
+// The bus chain over the blocks of `sp` — of a chunk, or of several whole chunks — whose sum sits in d_dst. `flags`: the blocks' `audible` words,
+// one per block (nullptr: audible). Commands (main-mixer effect events, due at the span's first frame) ride on a launch of the first block
+// alone: a launch that walks several blocks applies nothing.
+static int launch_bus(pg_graph* g, float* d_dst, const LaunchSpan& sp, int* flags, hipStream_t stream) {
   if (g->mixers[0].fx.empty()) return PG_OK;
-  auto one = [&](const LaunchSpan& q, float* dst, int slot) -> int {
-    PgLaunch B;
-    fill_launch(g, q, B);
-    B.mode = 0;
-    B.n_units = 1; B.unit_order = nullptr; B.unit_base = g->mixers[0].unit_slot;
-    B.bus = dst; B.bus_audible = g->d_audible + slot; B.audible_tab = nullptr;
-    B.sched = nullptr;
-    bus_pipeline_setup(g, B);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (q.timed && g->ev_bus_used < g->ev_bus_pool.size()) { e0 = g->ev_bus_pool[g->ev_bus_used].first; e1 = g->ev_bus_pool[g->ev_bus_used].second; g->ev_bus_blocks[g->ev_bus_used] = (uint32_t)q.n_chunks; g->ev_bus_used++; }
-    HIP_TRY(pg_launch_units(B, stream, e0, e1));
-    return PG_OK;
-  };
   if (sp.n_cmds > 0 && sp.n_chunks > 1) {
     LaunchSpan head = sp;
     head.n_chunks = 1;
-    int rc = one(head, d_dst, audible_slot);
-    if (rc) return rc;
-    sp.d_cmds = nullptr; sp.n_cmds = 0;
-    sp.t0 += sp.n; sp.grid_off += sp.n; sp.n_chunks -= 1; sp.row_block += 1;
-    return one(sp, d_dst + (size_t)sp.n * 2, audible_slot + 1);
+    const int rc = launch_bus(g, d_dst, head, flags, stream);
+    return rc ? rc : launch_bus(g, d_dst + (size_t)sp.n * 2, sp.behind(1), flags ? flags + 1 : nullptr, stream);
   }
-  return one(sp, d_dst, audible_slot);
+  PgLaunch B;
+  fill_launch(g, sp, B);
+  B.mode = 0;
+  B.n_units = 1; B.unit_order = nullptr; B.unit_base = g->mixers[0].unit_slot;
+  B.bus = d_dst; B.bus_audible = flags; B.audible_tab = nullptr;
+  B.sched = nullptr;
+  bus_pipeline_setup(g, B);
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (sp.timed && g->ev_bus_used < g->ev_bus_pool.size()) { e0 = g->ev_bus_pool[g->ev_bus_used].first; e1 = g->ev_bus_pool[g->ev_bus_used].second; g->ev_bus_blocks[g->ev_bus_used] = (uint32_t)sp.n_chunks; g->ev_bus_used++; }
+  HIP_TRY(pg_launch_units(B, stream, e0, e1));
+  return PG_OK;
 }
 
 // Commands of the launch that renders frames [t0, t0 + n) of the chunk [chunk_t0, chunk_end): `head` (main-mixer events and messages due at
@@ -1527,7 +1551,7 @@ static void meter_push_job(pg_graph* g, size_t m, int span_first, int span_count
 // A super-block launch sequence: k blocks of mf frames from `now`, whole chunks of CH frames (the last one may be shorter), one level.
 static void meter_collect_super(pg_graph* g, uint64_t now, uint64_t k, uint64_t mf) {
   g->meter_jobs.clear(); g->meter_spans.clear();
-  const uint64_t CH = PG_MAX_FRAMES, per_chunk = CH % mf == 0 ? CH / mf : k;
+  const uint64_t CH = PG_MAX_FRAMES, per_chunk = CH % mf == 0 ? pieces_per_chunk(mf) : k;
   const uint64_t chunk_stride = (uint64_t)g->unit_out_rows * g->stride;
   for (uint64_t b = 0; b < k; ++b) {
     PgMeterSpan sp;
@@ -1542,10 +1566,11 @@ static void meter_collect_super(pg_graph* g, uint64_t now, uint64_t k, uint64_t 
 // Called before the pieces' commands are taken out of the queues: `pending events` is what the mixers hold as the chunk begins.
 static void meter_collect_chunk(pg_graph* g, uint64_t now, uint64_t chunk_n, uint64_t mf) {
   g->meter_jobs.clear(); g->meter_spans.clear();
-  const uint64_t chunk_stride = (uint64_t)g->unit_out_rows * g->stride, n_pieces = (chunk_n + mf - 1) / mf;
+  const uint64_t chunk_stride = (uint64_t)g->unit_out_rows * g->stride;
+  const ChunkPieces cp{chunk_n, mf};
   auto add_record = [&](uint64_t s, uint64_t e) {   // frames [s, e) of the chunk
-    for (uint64_t p = s / mf; p < n_pieces && p * mf < e; ++p) {
-      const uint64_t a = std::max(s, p * mf), b = std::min(e, std::min((p + 1) * mf, chunk_n));
+    for (uint64_t p = s / mf; p < cp.n_pieces() && p * mf < e; ++p) {
+      const uint64_t a = std::max(s, p * mf), b = std::min(e, p * mf + cp.piece_len(p));
       PgMeterSpan sp;
       sp.off = p * chunk_stride + (a - p * mf) * 2; sp.time = now + s; sp.n_frames = (uint32_t)(b - a);
       sp.flags = b == e ? PG_METER_END_OF_RECORD : 0;
@@ -1587,265 +1612,298 @@ uint64_t call_budget_bound(std::vector<uint64_t>& cuts, uint64_t now, uint64_t c
   return cuts.size() > (size_t)(PG_MAX_CALLS - 1) ? cuts[PG_MAX_CALLS - 1] - now : chunk_n;
 }
 
-// Renders frames [pos, pos + n_samples / 2) of the write call into d_out. The call is walked in the reference's chunks — min(remaining,
+// graph_write_impl renders frames [pos, pos + n_samples / 2) of the write call into d_out. The call is walked in the reference's chunks — min(remaining,
 // PG_MAX_FRAMES) frames from the call's start and from every main-mixer event (mixed.rs:679-712) — whatever max_frames is: a chunk is rendered
 // as pieces of at most max_frames frames, every per-chunk decision taken once per chunk on the device (pg_dev.h: PG_MAX_FRAMES).
 // cap_frames > 0: stop in front of the first chunk that would end beyond cap_frames (the caller's staging holds that much; >= PG_MAX_FRAMES)
 // and return what was rendered; the caller goes on with begin = false. Returns the samples rendered (0: nothing to do, or the graph failed).
-size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t pos, hipStream_t stream, bool begin, size_t cap_frames) {
-  if (g->failed) return 0;
+// The call is a short loop over named steps: write_prologue (stream change, polls, topology, feeds), then per span of the chunk grid
+// take_head_commands, super_block_count, render_super_block or render_chunk, and WriteCall::advance.
+struct WriteCall {
+  float* d_out;
+  hipStream_t stream;
+  uint64_t pos, frames;       // the call: frames [pos, pos + frames)
+  uint64_t cap_frames;        // 0, or the frames the caller's staging holds
+  int* aud_words;             // where the mixer sum leaves the `audible` words
+  uint64_t done = 0;          // frames rendered so far
+  // Deferred bus chain: the call leaves ONE `audible` word per piece it emits, in order (a running cursor — a chunk that an event cut short
+  // has pieces of its own, and max_frames need not divide a chunk), and EVERY offset at which the chunk grid restarted (advance):
+  // process_bus_impl walks the same grid with the same cursor (round-4 advisor finding: the words used to sit at done / max_frames).
+  uint64_t word_cursor = 0;
+  uint64_t now() const { return pos + done; }
+  // Does the chunk grid restart behind the `len` frames just rendered of a span of `span` frames? At the event that ends the span, and behind
+  // every chunk that ended short of the grid's chunk length for another reason: the call budget of nested mixers (render_chunk). Each restart of a
+  // deferred-bus write is recorded, so that process_bus_impl walks the pieces this write walked and finds one word per piece.
+  void advance(pg_graph* g, uint64_t len, uint64_t span) {
+    const bool span_ends_at_event = span < frames - done;   // the grid restarts behind this span
+    done += len;
+    if (g->defer_bus && done < frames && ((span_ends_at_event && len == span) || len % PG_MAX_FRAMES != 0)) g->defer_cuts.push_back(done);
+  }
+};
+// The call's prologue. false: nothing to render — the graph has failed (now or before) or is empty.
+static bool write_prologue(pg_graph* g, size_t n_samples, uint64_t pos, hipStream_t stream, bool begin) {
+  if (g->failed) return false;
   // a consistency flag the kernels mirrored into the mapped feedback block (a unit left unrendered inside a super-block launch): what was
   // handed out since is not trustworthy — the graph goes silent like a GuardedSource whose source panicked (src/source/guarded.rs:87-107)
   if (g->h_feedback && *(volatile unsigned long long*)(g->h_feedback + 2) != 0) {
     g->failed = true;
     set_error(PG_ERR_DEVICE, "kernel consistency flag %llu raised (see pg_graph_device_errors): the graph is disabled", *(volatile unsigned long long*)(g->h_feedback + 2));
-    return 0;
+    return false;
   }
-  if (n_samples % 2 != 0) { set_error(PG_ERR_PARAMETER, "n_samples must be a multiple of the channel count"); return 0; }
+  if (n_samples % 2 != 0) { set_error(PG_ERR_PARAMETER, "n_samples must be a multiple of the channel count"); return false; }
   (void)hipSetDevice(g->device);
   // a caller that moves from one stream to another without a graph mutation in between: the tables and rings are ordered per stream
-  if (g->last_stream && g->last_stream != stream) { if (pg_stream_sync(g->last_stream) != hipSuccess) { g->failed = true; return 0; } g->cmds_since_sync = 0; }
+  if (g->last_stream && g->last_stream != stream) { if (pg_stream_sync(g->last_stream) != hipSuccess) { g->failed = true; return false; } g->cmds_since_sync = 0; }
   g->last_stream = stream;
   if (begin) { graph_begin_write(g, pos); g->call_end = pos + n_samples / 2; }
   graph_sampler_poll(g);
-  if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return 0; } }
-  if (g->gran_live_dirty && graph_gran_upload_live(g, stream)) { g->failed = true; return 0; }
-  if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return 0; } }
+  if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return false; } }
+  if (g->gran_live_dirty && graph_gran_upload_live(g, stream)) { g->failed = true; return false; }
+  if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return false; } }
   if (g->overlap_stream != stream) { g->rows_free_fresh = false; g->overlap_stream = stream; }
   g->write_done_attached = false;
   g->audible_valid = false;   // (a write that finds nothing to do launches nothing: the words an earlier call left are not this call's)
-  if (graph_is_empty(g)) return 0;
+  if (graph_is_empty(g)) return false;
   g->audible_valid = true;
-  const uint64_t frames = n_samples / 2, mf = g->max_frames, CH = PG_MAX_FRAMES;
-  uint64_t done = 0;
-  auto fail = [&]() -> size_t { g->failed = true; return 0; };
-  // Deferred bus chain: the call leaves ONE `audible` word per piece it emits, in order (a running cursor — a chunk that an event cut short
-  // has pieces of its own, and max_frames need not divide a chunk), and EVERY offset at which the chunk grid restarted (grid_restarts below):
-  // process_bus_impl walks the same grid with the same cursor (round-4 advisor finding: the words used to sit at done / max_frames).
-  uint64_t word_cursor = 0;
-  int* const aud_words = (g->defer_bus && g->d_audible_out) ? g->d_audible_out : g->d_audible;   // where the mixer sum leaves the `audible` words
-  if (g->defer_bus) { g->defer_cuts.clear(); g->defer_pos = pos; g->defer_words = 0; }
-  while (done < frames) {
-    const uint64_t now = pos + done;
-    HostMixer& main = g->mixers[0];
-    if (cap_frames && done > 0) {  // would the next chunk still fit the caller's staging? (decided before its events are taken out of the queue)
-      uint64_t next_n = std::min<uint64_t>(frames - done, CH);
-      for (const Event& e : main.events) if (e.sample_time > now) { next_n = std::min<uint64_t>(next_n, e.sample_time - now); break; }
-      if (done + next_n > cap_frames) break;
-    }
-    // main-mixer events due now apply at frame 0 of the chunk; the next main event bounds it (:679-693)
-    std::vector<PgCmd> head;
-    while (!main.events.empty() && main.events.front().sample_time <= now) {
-      PgCmd c = main.events.front().cmd;
-      if (g->defer_bus && (c.type == CMD_FX_PARAM || c.type == CMD_FX_RESET || c.type == CMD_NOP)) {  // the bus chain runs in pg_graph_process_bus_device
-        if (main.bus_events.size() >= 65536) main.bus_events.erase(main.bus_events.begin(), main.bus_events.begin() + 32768);  // a shard that never runs the bus
-        main.bus_events.push_back(main.events.front());
-        main.events.erase(main.events.begin());
-        continue;
-      }
-      c.frame = 0;
-      c.unit = (c.type == CMD_FX_PARAM || c.type == CMD_FX_RESET || c.type == CMD_NOP) ? main.unit_slot : g->source_unit_of_voice[c.param];  // voice commands carry the voice id in `param`
-      head.push_back(c);
+  return true;
+}
+// The commands due at the first frame of the chunk that begins at `now`: main-mixer events (the bus chain's go to the deferred bus's queue when
+// it is deferred) and, once per write call, the StopSource messages of every mixer.
+static void take_head_commands(pg_graph* g, uint64_t now, std::vector<PgCmd>& head) {
+  HostMixer& main = g->mixers[0];
+  // main-mixer events due now apply at frame 0 of the chunk; the next main event bounds it (:679-693)
+  while (!main.events.empty() && main.events.front().sample_time <= now) {
+    PgCmd c = main.events.front().cmd;
+    if (g->defer_bus && cmd_is_bus_chain(c.type)) {  // the bus chain runs in pg_graph_process_bus_device
+      if (main.bus_events.size() >= 65536) main.bus_events.erase(main.bus_events.begin(), main.bus_events.begin() + 32768);  // a shard that never runs the bus
+      main.bus_events.push_back(main.events.front());
       main.events.erase(main.events.begin());
-    }
-    // the regular chunk grid holds from here to the end of the call or the next main-mixer event
-    uint64_t span = frames - done;
-    if (!main.events.empty()) span = std::min<uint64_t>(span, main.events.front().sample_time - now);
-    if (span == 0) continue;
-    const bool span_ends_at_event = span < frames - done;   // the grid restarts behind this span
-    uint64_t chunk_n = std::min<uint64_t>(span, CH);
-    // Does the chunk grid restart behind the `len` frames just rendered (`done` already counts them)? At the event that ends the span, and behind
-    // every chunk that ended short of the grid's chunk length for another reason: the call budget of nested mixers below. Each restart of a
-    // deferred-bus write is recorded, so that process_bus_impl walks the pieces this write walked and finds one word per piece.
-    auto grid_restarts = [&](uint64_t len) { return g->defer_bus && done < frames && ((span_ends_at_event && len == span) || len % CH != 0); };
-    // StopSource messages: processed by process_messages at the start of write (:294-499)
-    if (g->messages_due) {
-      for (size_t m = 0; m < g->mixers.size(); ++m) {
-        for (PgCmd c : g->mixers[m].messages) {
-          c.frame = 0;
-          c.unit = m == 0 ? g->source_unit_of_voice[c.param] : g->mixers[m].unit_slot;
-          head.push_back(c);
-        }
-        g->mixers[m].messages.clear();
-      }
-      g->messages_due = false;
-    }
-    // ---- super-block: whole chunks without a command anywhere in them, in steady state, as ONE launch sequence (every workgroup of the staged /
-    // fast kernels walks the blocks of its unit; per-chunk decisions are still taken per chunk, on the device) ----
-    uint64_t k = 0;
-    if (head.empty() && span >= mf && graph_super_ok(g)) {
-      uint64_t kmax = std::min<uint64_t>(span / mf, g->max_blocks);
-      // (metering a sub-mixer whose records depend on its sources: the meter looks at them chunk by chunk)
-      if (g->metering && g->meter_fragile && CH % mf == 0) kmax = std::min<uint64_t>(kmax, CH / mf);
-      if (cap_frames) kmax = std::min<uint64_t>(kmax, (cap_frames - std::min<uint64_t>(done, cap_frames)) / mf);
-      uint64_t t_next = UINT64_MAX;
-      for (const HostMixer& mx : g->mixers) if (!mx.events.empty()) t_next = std::min(t_next, mx.events.front().sample_time);
-      if (t_next != UINT64_MAX && t_next < now + kmax * mf) kmax = t_next > now ? (t_next - now) / mf : 0;
-      // the launch must end where a chunk ends: at a multiple of the chunk length or at the end of the span
-      if (g->defer_bus) kmax = std::min<uint64_t>(kmax, g->audible_slots - std::min<uint64_t>(word_cursor, g->audible_slots));   // (one word per block)
-      if (CH % mf == 0) k = (kmax * mf >= span && span % mf == 0) ? span / mf : (kmax / (CH / mf)) * (CH / mf);
-      else k = (span % mf == 0 && span <= CH && span / mf <= kmax) ? span / mf : 0;
-    }
-    // A small unit level in front of a bus chain (BASELINE configs 2 and 4: 64 / 256 voices, then a chain that takes four times as long as they
-    // do): launch sequences of a few chunks each, so that the chain of one runs over the unit kernels of the next INSIDE a call too
-    // (the first sequence behind a serialisation has no chain to run under: it is one chunk, so that only that chunk's unit kernels are exposed)
-    if (CH % mf == 0 && g->overlap_bus && !g->defer_bus && !g->mixers[0].fx.empty() && g->n_graph_units <= 512) {
-      const uint64_t per_chunk = CH / mf;
-      // (a chain to run under: one was enqueued by the sequence before — in this call, or in the call before and the stream has not drained
-      // since: a caller that waited for its last call finds an idle device)
-      const bool under_chain = g->rows_free_fresh && (done > 0 || hipStreamQuery(stream) == hipErrorNotReady);
-      const uint64_t group = under_chain ? std::max<uint64_t>(per_chunk, (g->bus_group / per_chunk) * per_chunk) : std::max<uint64_t>(per_chunk, 2);
-      if (k > group) k = group;
-    }
-    if (k > 0) {
-      LaunchSpan sp;
-      sp.n = (uint32_t)mf; sp.t0 = now; sp.n_chunks = (int)k; sp.row_block = 0; sp.grid_off = 0; sp.grid_span = (uint32_t)std::min<uint64_t>(span, 0x7fffffffull);
-      sp.round = g->launch_counter++;
-      sp.generic_idle = true;  // (graph_super_ok: steady state, one level)
-      sp.timed = g->timing_period > 0 && (g->launch_counter % (uint64_t)g->timing_period) == 0 && g->ev_used < g->ev_pool.size() && g->n_graph_units > 0;
-      // A bus chain behind the sum: this sequence's unit kernels go to the unit stream, UNDER the bus chain of the sequence before (they wait for
-      // its sum to have read the per-unit rows, not for its chain), and this sequence's sum waits for them
-      const bool overlap = g->overlap_bus && !g->defer_bus && !g->mixers[0].fx.empty() && k > 1;
-      if (overlap) {
-        if (!g->rows_free_fresh) HIP_TRY_FAIL(hipEventRecord(g->ev_rows_free, stream));   // (behind whatever the write's stream holds: one serialisation, then the pipeline runs)
-        HIP_TRY_FAIL(hipStreamWaitEvent(g->unit_stream, g->ev_rows_free, 0));
-        if (launch_level(g, 0, sp, g->unit_stream)) return fail();
-        HIP_TRY_FAIL(hipEventRecord(g->ev_units_done, g->unit_stream));
-        HIP_TRY_FAIL(hipStreamWaitEvent(stream, g->ev_units_done, 0));
-      } else {
-        if (launch_level(g, 0, sp, stream)) return fail();
-        g->rows_free_fresh = false;
-      }
-      // where the blocks' `audible` words go: with the bus chain deferred to the caller, word c of the call belongs to its c-th block
-      const int slot = g->defer_bus ? (int)word_cursor : 0;
-      if (g->defer_bus) { word_cursor += k; g->defer_words = (int)word_cursor; }
-      {
-        const Level& top = g->levels.back();
-        HIP_TRY_FAIL(pg_launch_mix(g->d_unit_out + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, d_out + done * 2, (uint32_t)mf * 2, g->d_audible_tab + top.off, g->unit_out_rows,
-                                   aud_words + slot, stream, (int)k, (size_t)g->unit_out_rows * g->stride, (g->write_done_event && done + k * mf == frames) ? g->write_done_event : nullptr));
-        if (g->write_done_event && done + k * mf == frames) g->write_done_attached = true;
-      }
-      if (g->metering) { meter_collect_super(g, now, k, mf); if (graph_meter_launch(g, stream)) return fail(); }   // (in front of ev_rows_free: the rows are still this sequence's)
-      if (overlap) { HIP_TRY_FAIL(hipEventRecord(g->ev_rows_free, stream)); g->rows_free_fresh = true; }
-      if (!g->defer_bus && launch_bus(g, d_out + done * 2, sp, slot, stream)) return fail();
-      done += k * mf;
-      if (grid_restarts(k * mf)) g->defer_cuts.push_back(done);
       continue;
     }
-    // ---- one chunk, piece by piece ----
-    g->rows_free_fresh = false;
-    // A sub-mixer keeps one result bit per call of its parent: the chunk is bounded so that at most PG_MAX_CALLS - 1 call boundaries fall inside it
-    if (g->levels.size() > 1) {
-      std::vector<uint64_t> cuts;
-      graph_call_cuts(g, now, chunk_n, cuts);
-      chunk_n = call_budget_bound(cuts, now, chunk_n);
-    }
-    const uint64_t n_pieces = (chunk_n + mf - 1) / mf, n_full = chunk_n / mf;
-    if (g->defer_bus && word_cursor + n_pieces > g->audible_slots) {
-      // the call has used up its `audible` words (audible_slots = max(64, pieces of one chunk): only a call longer than 64 pieces, or one cut by
-      // many events, gets here): what was rendered is returned, the caller goes on with another call — silent aliasing of words is not an option
-      set_error(PG_ERR_PARAMETER, "a deferred-bus write leaves at most %zu `audible` words: %llu frames rendered, call again for the rest", g->audible_slots, (unsigned long long)done);
-      break;
-    }
-    if (n_pieces > g->unit_out_blocks) { set_error(PG_ERR_STATE, "per-unit buffers were not reserved for a chunk's pieces"); return fail(); }
-    if (g->metering) meter_collect_chunk(g, now, chunk_n, mf);   // (launched behind the chunk's sum)
-    std::vector<LaunchSpan> spans((size_t)n_pieces);
-    bool pstat_live = false;   // playback status: some voice of the graph reports (pg_k_status.hip)
-    for (int v : g->pstat.voices) pstat_live |= g->voices[v].mixer >= 0 && g->voices[v].pstat_on;
-    std::vector<std::vector<std::pair<int, int>>> pstat_cmds(pstat_live ? (size_t)n_pieces : 0);
-    const uint64_t round0 = g->launch_counter;
-    g->launch_counter += n_pieces;
-    const bool steady_now = g->levels.size() == 1 && graph_steady(g);
-    const size_t tl = timed_level_of(g);
-    for (uint64_t p = 0; p < n_pieces; ++p) {
-      LaunchSpan& sp = spans[(size_t)p];
-      sp.t0 = now + p * mf; sp.n = (uint32_t)std::min<uint64_t>(mf, chunk_n - p * mf);
-      sp.n_chunks = 1; sp.row_block = (int)p; sp.grid_off = (uint32_t)(p * mf); sp.grid_span = (uint32_t)chunk_n;
-      sp.round = round0 + p;
-      std::vector<PgCmd> cmds;
-      if (p == 0) cmds = head;
-      collect_piece_commands(g, cmds, sp.t0, sp.n, now, now + chunk_n);
-      if (pstat_live) for (const PgCmd& c : cmds) {  // (sorted by unit) how many commands each unit takes in this piece: what the exact kernel may log there
-        if (!pstat_cmds[(size_t)p].empty() && pstat_cmds[(size_t)p].back().first == c.unit) pstat_cmds[(size_t)p].back().second += 1;
-        else pstat_cmds[(size_t)p].emplace_back(c.unit, 1);
-      }
-      if (!cmds.empty()) {
-        // (a round that will run its decision-scan kernel takes a short list there as the kernel's argument: no copy kernel on the stream)
-        sp.n_cmds = (int)cmds.size();
-        // (pg_grain_kernel reads the list in front of the scan: with living granular voices it travels by copy)
-        const bool by_scan = cmds.size() <= PG_CMD_PACK && g->gran_voices.empty() && level_concurrent(g, 0, sp, stream);
-        if (stage_commands(g, cmds, stream, &sp.d_cmds, by_scan ? &sp.h_cmds : nullptr)) return fail();
-        // Which commands can leave the steady state behind them? A parameter command may start a smoother of an effect (the device knows how
-        // long: the next rounds' scans tell), a speed command a glide, markers belong to split chunks. Source volume / panning / stop / seek
-        // change nothing the time-parallel kernels do not render (AmplifiedSource / PannedSource smoothers, the fader, a new position): a unit
-        // deferred for those alone is back on its kernel in the next block, so the host need not wait for the device to say so — offline
-        // calls keep their super-block launches between such commands (notes that stop and start: bench.py --workload dyn --churn).
-        bool may_ramp = false;
-        for (const PgCmd& c : cmds) may_ramp |= !(c.type == CMD_VOICE_VOLUME || c.type == CMD_VOICE_PAN || c.type == CMD_VOICE_STOP || c.type == CMD_VOICE_SEEK || c.type == CMD_VOICE_RELEASE ||
-                                                         c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM ||
-                                                         c.type == CMD_VOICE_GRAIN_PARAM || c.type == CMD_VOICE_GRAIN_LOOP);   // (the matrix's and the granular parameters' commands reach pg_grain_kernel only)
-        // (the round AFTER this one is the first whose scan sees what the commands left behind: this round's own count of state-deferred units
-        // was taken in front of them)
-        if (may_ramp) g->last_change_round = sp.round + 1;
-      }
-      // Steady state: the generic kernel of an earlier round (not older than the last topology change / command / mode switch) found
-      // nothing deferred, and units leave the steady state only through those host-visible events -> the generic launch is skipped.
-      // (Graphs with nested sub-mixers always launch it: the parents are rendered there.)
-      sp.generic_idle = steady_now && cmds.empty() && g->last_change_round < round0;
-    }
-    // granular voices: their frames of every piece of the chunk, staged in front of the unit kernels that take them
-    if (!g->gran_voices.empty()) for (uint64_t p = 0; p < n_pieces; ++p) {
-      const LaunchSpan& sp = spans[(size_t)p];
-      if (launch_grains(g, sp.t0, sp.n, now, sp.d_cmds, sp.n_cmds, stream)) return fail();
-    }
-    if (pstat_live && graph_pstat_begin_chunk(g, pstat_cmds, stream)) return fail();
-    for (size_t li = 0; li < g->levels.size(); ++li) {
-      for (uint64_t p = 0; p < n_pieces; ++p) {
-        LaunchSpan sp = spans[(size_t)p];
-        // the event pair costs ~8 us of stream time per round (also when it rides on the dispatch): callers that only need the
-        // average can time every n-th round (pg_graph_set_timing_period)
-        sp.timed = li == tl && g->timing_period > 0 && ((sp.round + 1) % (uint64_t)g->timing_period) == 0 && g->ev_used < g->ev_pool.size() && g->n_graph_units > 0;
-        if (launch_level(g, li, sp, stream)) return fail();
-        // playback status: what this piece's source writes of the level's voices left, before the next piece moves them on
-        if (pstat_live && graph_pstat_launch(g, li, sp.t0, sp.n, p == 0, now + chunk_n, (uint32_t)sp.round, pstat_cmds[(size_t)p], stream)) return fail();
-      }
-    }
-    if (pstat_live) graph_pstat_end_chunk(g);
-    // the chunk's sum and bus chain: its full pieces in one launch each, a shorter last piece in launches of its own
-    const int slot0 = g->defer_bus ? (int)word_cursor : 0;
-    if (g->defer_bus) { word_cursor += n_pieces; g->defer_words = (int)word_cursor; }
-    const size_t chunk_stride = (size_t)g->unit_out_rows * g->stride;
-    const Level& top = g->levels.back();
-    float* dst = d_out + done * 2;
-    const bool last_chunk_of_call = g->write_done_event != nullptr && done + chunk_n == frames;   // (the event rides on the call's last sum launch)
-    if (last_chunk_of_call) g->write_done_attached = true;
-    if (n_full > 0) HIP_TRY_FAIL(pg_launch_mix(g->d_unit_out + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, dst, (uint32_t)mf * 2, g->d_audible_tab + top.off, g->unit_out_rows,
-                                               aud_words + slot0, stream, (int)n_full, chunk_stride, (last_chunk_of_call && n_pieces == n_full) ? g->write_done_event : nullptr));
-    if (n_pieces > n_full) {
-      const LaunchSpan& r = spans[(size_t)n_full];
-      HIP_TRY_FAIL(pg_launch_mix(g->d_unit_out + (size_t)n_full * chunk_stride + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, dst + n_full * mf * 2, r.n * 2,
-                                 g->d_audible_tab + (size_t)n_full * g->unit_out_rows + top.off, g->unit_out_rows, aud_words + slot0 + (int)n_full, stream, 1, chunk_stride, last_chunk_of_call ? g->write_done_event : nullptr));
-    }
-    if (g->metering && graph_meter_launch(g, stream)) return fail();
-    if (!g->defer_bus && !g->mixers[0].fx.empty()) {
-      // the bus unit's commands of the chunk's first piece (main-mixer effect events) ride on its bus launch
-      const bool bus_timed = g->timing_period > 0 && ((spans[0].round + 1) % (uint64_t)g->timing_period) == 0;
-      if (n_full > 0) {
-        LaunchSpan b = spans[0];
-        b.timed = bus_timed;
-        b.n_chunks = (int)n_full;
-        if (launch_bus(g, dst, b, slot0, stream)) return fail();
-      }
-      if (n_pieces > n_full) {
-        LaunchSpan b = spans[(size_t)n_full];
-        b.timed = bus_timed;
-        if (n_full > 0) { b.d_cmds = nullptr; b.n_cmds = 0; }
-        if (launch_bus(g, dst + n_full * mf * 2, b, slot0 + (int)n_full, stream)) return fail();
-      }
-    }
-    done += chunk_n;
-    if (grid_restarts(chunk_n)) g->defer_cuts.push_back(done);
+    c.frame = 0;
+    c.unit = cmd_is_bus_chain(c.type) ? main.unit_slot : g->source_unit_of_voice[c.param];  // voice commands carry the voice id in `param`
+    head.push_back(c);
+    main.events.erase(main.events.begin());
   }
+  // StopSource messages: processed by process_messages at the start of write (:294-499)
+  if (g->messages_due) {
+    for (size_t m = 0; m < g->mixers.size(); ++m) {
+      for (PgCmd c : g->mixers[m].messages) {
+        c.frame = 0;
+        c.unit = m == 0 ? g->source_unit_of_voice[c.param] : g->mixers[m].unit_slot;
+        head.push_back(c);
+      }
+      g->mixers[m].messages.clear();
+    }
+    g->messages_due = false;
+  }
+}
+// How many blocks of max_frames of the span that begins at w.now() go out as ONE super-block launch sequence (0: the next chunk is rendered piece by piece)
+static uint64_t super_block_count(pg_graph* g, const WriteCall& w, uint64_t span, bool head_empty) {
+  const uint64_t now = w.now(), mf = g->max_frames, CH = PG_MAX_FRAMES;
+  hipStream_t const stream = w.stream;
+  // ---- super-block: whole chunks without a command anywhere in them, in steady state, as ONE launch sequence (every workgroup of the staged /
+  // fast kernels walks the blocks of its unit; per-chunk decisions are still taken per chunk, on the device) ----
+  uint64_t k = 0;
+  if (head_empty && span >= mf && graph_super_ok(g)) {
+    uint64_t kmax = std::min<uint64_t>(span / mf, g->max_blocks);
+    // (metering a sub-mixer whose records depend on its sources: the meter looks at them chunk by chunk)
+    if (g->metering && g->meter_fragile && CH % mf == 0) kmax = std::min<uint64_t>(kmax, CH / mf);
+    if (w.cap_frames) kmax = std::min<uint64_t>(kmax, (w.cap_frames - std::min<uint64_t>(w.done, w.cap_frames)) / mf);
+    uint64_t t_next = UINT64_MAX;
+    for (const HostMixer& mx : g->mixers) if (!mx.events.empty()) t_next = std::min(t_next, mx.events.front().sample_time);
+    if (t_next != UINT64_MAX && t_next < now + kmax * mf) kmax = t_next > now ? (t_next - now) / mf : 0;
+    // the launch must end where a chunk ends: at a multiple of the chunk length or at the end of the span
+    if (g->defer_bus) kmax = std::min<uint64_t>(kmax, g->audible_slots - std::min<uint64_t>(w.word_cursor, g->audible_slots));   // (one word per block)
+    if (CH % mf == 0) k = (kmax * mf >= span && span % mf == 0) ? span / mf : (kmax / (CH / mf)) * (CH / mf);
+    else k = (span % mf == 0 && span <= CH && span / mf <= kmax) ? span / mf : 0;
+  }
+  // A small unit level in front of a bus chain (BASELINE configs 2 and 4: 64 / 256 voices, then a chain that takes four times as long as they
+  // do): launch sequences of a few chunks each, so that the chain of one runs over the unit kernels of the next INSIDE a call too
+  // (the first sequence behind a serialisation has no chain to run under: it is one chunk, so that only that chunk's unit kernels are exposed)
+  if (CH % mf == 0 && g->overlap_bus && !g->defer_bus && !g->mixers[0].fx.empty() && g->n_graph_units <= 512) {
+    const uint64_t per_chunk = CH / mf;
+    // (a chain to run under: one was enqueued by the sequence before — in this call, or in the call before and the stream has not drained
+    // since: a caller that waited for its last call finds an idle device)
+    const bool under_chain = g->rows_free_fresh && (w.done > 0 || hipStreamQuery(stream) == hipErrorNotReady);
+    const uint64_t group = under_chain ? std::max<uint64_t>(per_chunk, (g->bus_group / per_chunk) * per_chunk) : std::max<uint64_t>(per_chunk, 2);
+    if (k > group) k = group;
+  }
+  return k;
+}
+// k blocks of max_frames from w.now() as one launch sequence: unit kernels, sum, meter, bus chain
+static int render_super_block(pg_graph* g, WriteCall& w, uint64_t k, uint64_t span) {
+  const uint64_t now = w.now(), mf = g->max_frames, frames = w.frames;
+  hipStream_t const stream = w.stream;
+  float* const d_out = w.d_out;
+  LaunchSpan sp;
+  sp.n = (uint32_t)mf; sp.t0 = now; sp.n_chunks = (int)k; sp.row_block = 0; sp.grid_off = 0; sp.grid_span = (uint32_t)std::min<uint64_t>(span, 0x7fffffffull);
+  sp.round = g->launch_counter++;
+  sp.generic_idle = true;  // (graph_super_ok: steady state, one level)
+  sp.timed = g->timing_period > 0 && (g->launch_counter % (uint64_t)g->timing_period) == 0 && g->ev_used < g->ev_pool.size() && g->n_graph_units > 0;
+  // A bus chain behind the sum: this sequence's unit kernels go to the unit stream, UNDER the bus chain of the sequence before (they wait for
+  // its sum to have read the per-unit rows, not for its chain), and this sequence's sum waits for them
+  const bool overlap = g->overlap_bus && !g->defer_bus && !g->mixers[0].fx.empty() && k > 1;
+  if (overlap) {
+    if (!g->rows_free_fresh) HIP_TRY(hipEventRecord(g->ev_rows_free, stream));   // (behind whatever the write's stream holds: one serialisation, then the pipeline runs)
+    HIP_TRY(hipStreamWaitEvent(g->unit_stream, g->ev_rows_free, 0));
+    if (launch_level(g, 0, sp, g->unit_stream)) return PG_ERR_DEVICE;
+    HIP_TRY(hipEventRecord(g->ev_units_done, g->unit_stream));
+    HIP_TRY(hipStreamWaitEvent(stream, g->ev_units_done, 0));
+  } else {
+    if (launch_level(g, 0, sp, stream)) return PG_ERR_DEVICE;
+    g->rows_free_fresh = false;
+  }
+  // where the blocks' `audible` words go: with the bus chain deferred to the caller, word c of the call belongs to its c-th block
+  const int slot = g->defer_bus ? (int)w.word_cursor : 0;
+  if (g->defer_bus) { w.word_cursor += k; g->defer_words = (int)w.word_cursor; }
+  {
+    const Level& top = g->levels.back();
+    HIP_TRY(pg_launch_mix(g->d_unit_out + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, d_out + w.done * 2, (uint32_t)mf * 2, g->d_audible_tab + top.off, g->unit_out_rows,
+                               w.aud_words + slot, stream, (int)k, (size_t)g->unit_out_rows * g->stride, (g->write_done_event && w.done + k * mf == frames) ? g->write_done_event : nullptr));
+    if (g->write_done_event && w.done + k * mf == frames) g->write_done_attached = true;
+  }
+  if (g->metering) { meter_collect_super(g, now, k, mf); if (graph_meter_launch(g, stream)) return PG_ERR_DEVICE; }   // (in front of ev_rows_free: the rows are still this sequence's)
+  if (overlap) { HIP_TRY(hipEventRecord(g->ev_rows_free, stream)); g->rows_free_fresh = true; }
+  if (!g->defer_bus && launch_bus(g, d_out + w.done * 2, sp, g->d_audible + slot, stream)) return PG_ERR_DEVICE;
+  return PG_OK;
+}
+// One chunk from w.now(), piece by piece: at most `span` frames, a chunk's length, and what the call budget of nested mixers allows.
+// *rendered: its frames; 0 (with PG_OK): the call has run out of `audible` words and ends here.
+static int render_chunk(pg_graph* g, WriteCall& w, uint64_t span, const std::vector<PgCmd>& head, uint64_t* rendered) {
+  const uint64_t now = w.now(), mf = g->max_frames, frames = w.frames;
+  hipStream_t const stream = w.stream;
+  float* const d_out = w.d_out;
+  uint64_t chunk_n = std::min<uint64_t>(span, PG_MAX_FRAMES);
+  // ---- one chunk, piece by piece ----
+  g->rows_free_fresh = false;
+  // A sub-mixer keeps one result bit per call of its parent: the chunk is bounded so that at most PG_MAX_CALLS - 1 call boundaries fall inside it
+  if (g->levels.size() > 1) {
+    std::vector<uint64_t> cuts;
+    graph_call_cuts(g, now, chunk_n, cuts);
+    chunk_n = call_budget_bound(cuts, now, chunk_n);
+  }
+  const ChunkPieces pieces{chunk_n, mf};
+  const uint64_t n_pieces = pieces.n_pieces();
+  if (g->defer_bus && w.word_cursor + n_pieces > g->audible_slots) {
+    // the call has used up its `audible` words (audible_slots = max(64, pieces of one chunk): only a call longer than 64 pieces, or one cut by
+    // many events, gets here): what was rendered is returned, the caller goes on with another call — silent aliasing of words is not an option
+    set_error(PG_ERR_PARAMETER, "a deferred-bus write leaves at most %zu `audible` words: %llu frames rendered, call again for the rest", g->audible_slots, (unsigned long long)w.done);
+    *rendered = 0;
+    return PG_OK;
+  }
+  if (n_pieces > g->unit_out_blocks) return set_error(PG_ERR_STATE, "per-unit buffers were not reserved for a chunk's pieces");
+  if (g->metering) meter_collect_chunk(g, now, chunk_n, mf);   // (launched behind the chunk's sum)
+  std::vector<LaunchSpan> spans((size_t)n_pieces);
+  bool pstat_live = false;   // playback status: some voice of the graph reports (pg_k_status.hip)
+  for (int v : g->pstat.voices) pstat_live |= g->voices[v].mixer >= 0 && g->voices[v].pstat_on;
+  std::vector<std::vector<std::pair<int, int>>> pstat_cmds(pstat_live ? (size_t)n_pieces : 0);
+  const uint64_t round0 = g->launch_counter;
+  g->launch_counter += n_pieces;
+  const bool steady_now = g->levels.size() == 1 && graph_steady(g);
+  const size_t tl = timed_level_of(g);
+  for (uint64_t p = 0; p < n_pieces; ++p) {
+    LaunchSpan& sp = spans[(size_t)p];
+    sp.t0 = now + p * mf; sp.n = (uint32_t)pieces.piece_len(p);
+    sp.n_chunks = 1; sp.row_block = (int)p; sp.grid_off = (uint32_t)(p * mf); sp.grid_span = (uint32_t)chunk_n;
+    sp.round = round0 + p;
+    std::vector<PgCmd> cmds;
+    if (p == 0) cmds = head;
+    collect_piece_commands(g, cmds, sp.t0, sp.n, now, now + chunk_n);
+    if (pstat_live) for (const PgCmd& c : cmds) {  // (sorted by unit) how many commands each unit takes in this piece: what the exact kernel may log there
+      if (!pstat_cmds[(size_t)p].empty() && pstat_cmds[(size_t)p].back().first == c.unit) pstat_cmds[(size_t)p].back().second += 1;
+      else pstat_cmds[(size_t)p].emplace_back(c.unit, 1);
+    }
+    if (!cmds.empty()) {
+      // (a round that will run its decision-scan kernel takes a short list there as the kernel's argument: no copy kernel on the stream)
+      sp.n_cmds = (int)cmds.size();
+      // (pg_grain_kernel reads the list in front of the scan: with living granular voices it travels by copy)
+      const bool by_scan = cmds.size() <= PG_CMD_PACK && g->gran_voices.empty() && level_concurrent(g, 0, sp, stream);
+      if (stage_commands(g, cmds, stream, &sp.d_cmds, by_scan ? &sp.h_cmds : nullptr)) return PG_ERR_DEVICE;
+      // Which commands can leave the steady state behind them (cmd_keeps_steady)? Offline calls keep their super-block launches between
+      // commands that cannot (notes that stop and start: bench.py --workload dyn --churn).
+      bool may_ramp = false;
+      for (const PgCmd& c : cmds) may_ramp |= !cmd_keeps_steady(c.type);
+      // (the round AFTER this one is the first whose scan sees what the commands left behind: this round's own count of state-deferred units
+      // was taken in front of them)
+      if (may_ramp) g->last_change_round = sp.round + 1;
+    }
+    // Steady state: the generic kernel of an earlier round (not older than the last topology change / command / mode switch) found
+    // nothing deferred, and units leave the steady state only through those host-visible events -> the generic launch is skipped.
+    // (Graphs with nested sub-mixers always launch it: the parents are rendered there.)
+    sp.generic_idle = steady_now && cmds.empty() && g->last_change_round < round0;
+  }
+  // granular voices: their frames of every piece of the chunk, staged in front of the unit kernels that take them
+  if (!g->gran_voices.empty()) for (uint64_t p = 0; p < n_pieces; ++p) {
+    const LaunchSpan& sp = spans[(size_t)p];
+    if (launch_grains(g, sp.t0, sp.n, now, sp.d_cmds, sp.n_cmds, stream)) return PG_ERR_DEVICE;
+  }
+  if (pstat_live && graph_pstat_begin_chunk(g, pstat_cmds, stream)) return PG_ERR_DEVICE;
+  for (size_t li = 0; li < g->levels.size(); ++li) {
+    for (uint64_t p = 0; p < n_pieces; ++p) {
+      LaunchSpan sp = spans[(size_t)p];
+      // the event pair costs ~8 us of stream time per round (also when it rides on the dispatch): callers that only need the
+      // average can time every n-th round (pg_graph_set_timing_period)
+      sp.timed = li == tl && g->timing_period > 0 && ((sp.round + 1) % (uint64_t)g->timing_period) == 0 && g->ev_used < g->ev_pool.size() && g->n_graph_units > 0;
+      if (launch_level(g, li, sp, stream)) return PG_ERR_DEVICE;
+      // playback status: what this piece's source writes of the level's voices left, before the next piece moves them on
+      if (pstat_live && graph_pstat_launch(g, li, sp.t0, sp.n, p == 0, now + chunk_n, (uint32_t)sp.round, pstat_cmds[(size_t)p], stream)) return PG_ERR_DEVICE;
+    }
+  }
+  if (pstat_live) graph_pstat_end_chunk(g);
+  // the chunk's sum and bus chain: its full pieces in one launch each, a shorter last piece in launches of its own (full_then_last)
+  const int slot0 = g->defer_bus ? (int)w.word_cursor : 0;
+  if (g->defer_bus) { w.word_cursor += n_pieces; g->defer_words = (int)w.word_cursor; }
+  const size_t chunk_stride = (size_t)g->unit_out_rows * g->stride;
+  const Level& top = g->levels.back();
+  float* dst = d_out + w.done * 2;
+  const bool last_chunk_of_call = g->write_done_event != nullptr && w.done + chunk_n == frames;   // (the event rides on the call's last sum launch)
+  if (last_chunk_of_call) g->write_done_attached = true;
+  if (full_then_last(pieces, [&](uint64_t p0, uint64_t count) -> int {
+        const bool last_launch = p0 + count == n_pieces;
+        HIP_TRY(pg_launch_mix(g->d_unit_out + (size_t)p0 * chunk_stride + (size_t)top.off * g->stride, g->stride, top.cnt, g->d_partial, dst + p0 * mf * 2, spans[(size_t)p0].n * 2,
+                              g->d_audible_tab + (size_t)p0 * g->unit_out_rows + top.off, g->unit_out_rows, w.aud_words + slot0 + (int)p0, stream, (int)count, chunk_stride,
+                              (last_chunk_of_call && last_launch) ? g->write_done_event : nullptr));
+        return PG_OK;
+      })) return PG_ERR_DEVICE;
+  if (g->metering && graph_meter_launch(g, stream)) return PG_ERR_DEVICE;
+  if (!g->defer_bus && !g->mixers[0].fx.empty()) {
+    // the bus unit's commands of the chunk's first piece (main-mixer effect events) ride on its bus launch
+    const bool bus_timed = g->timing_period > 0 && ((spans[0].round + 1) % (uint64_t)g->timing_period) == 0;
+    if (full_then_last(pieces, [&](uint64_t p0, uint64_t count) -> int {
+          LaunchSpan b = spans[(size_t)p0];
+          b.timed = bus_timed;
+          b.n_chunks = (int)count;
+          if (p0 > 0) { b.d_cmds = nullptr; b.n_cmds = 0; }
+          return launch_bus(g, dst + p0 * mf * 2, b, g->d_audible + slot0 + (int)p0, stream);
+        })) return PG_ERR_DEVICE;
+  }
+  *rendered = chunk_n;
+  return PG_OK;
+}
+size_t graph_write_impl(pg_graph* g, float* d_out, size_t n_samples, uint64_t pos, hipStream_t stream, bool begin, size_t cap_frames) {
+  if (!write_prologue(g, n_samples, pos, stream, begin)) return 0;
+  WriteCall w{d_out, stream, pos, n_samples / 2, cap_frames, (g->defer_bus && g->d_audible_out) ? g->d_audible_out : g->d_audible};
+  if (g->defer_bus) { g->defer_cuts.clear(); g->defer_pos = pos; g->defer_words = 0; }
+  std::vector<PgCmd> head;   // (stays empty, and unallocated, in a call that renders only super-block sequences)
+  while (w.done < w.frames) {
+    const uint64_t now = w.now();
+    if (w.cap_frames && w.done > 0) {  // would the next chunk still fit the caller's staging? (decided before its events are taken out of the queue)
+      const uint64_t next_n = std::min<uint64_t>(std::min<uint64_t>(w.frames - w.done, PG_MAX_FRAMES), graph_frames_to_main_event(g, now));
+      if (w.done + next_n > w.cap_frames) break;
+    }
+    head.clear();
+    take_head_commands(g, now, head);
+    // the regular chunk grid holds from here to the end of the call or the next main-mixer event
+    const uint64_t span = std::min<uint64_t>(w.frames - w.done, graph_frames_to_main_event(g, now));
+    const uint64_t k = super_block_count(g, w, span, head.empty());
+    uint64_t len = k * g->max_frames;   // frames this step renders
+    const int rc = k ? render_super_block(g, w, k, span) : render_chunk(g, w, span, head, &len);
+    if (rc) { g->failed = true; return 0; }
+    if (len == 0) break;
+    w.advance(g, len, span);
+  }
+  const uint64_t done = w.done;
   if (done) {  // suffix maxima of the writes' end positions (one entry while the position only moves forward): pg_graph_set_voice_envelope
     g->write_count += 1;
     while (!g->write_end_max.empty() && g->write_end_max.back().second <= pos + done) g->write_end_max.pop_back();
@@ -1952,14 +2010,15 @@ int process_bus_impl(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_i
       const uint64_t chunk_start = (off / CH) * CH, chunk_end = std::min<uint64_t>(chunk_start + CH, span);
       LaunchSpan sp;
       sp.t0 = now + off; sp.grid_off = (uint32_t)off; sp.grid_span = (uint32_t)std::min<uint64_t>(span, 0x7fffffffull);
-      sp.round = g->launch_counter;
+      sp.round = g->launch_counter; sp.row_step = 0;
+      const ChunkPieces rest{chunk_end - off, mf};   // what is left of this chunk (`off` sits on a piece boundary)
       uint64_t k;
-      if (chunk_end - off < mf) { sp.n = (uint32_t)(chunk_end - off); k = 1; }      // the chunk's last, shorter piece
+      if (rest.n_full() == 0) { sp.n = (uint32_t)rest.chunk_n; k = 1; }      // the chunk's last, shorter piece
       else {
         sp.n = (uint32_t)mf;
         // full pieces: to the end of this chunk, and on through the following whole chunks when the pieces tile them
-        k = (chunk_end - off) / mf;
-        if (CH % mf == 0 && (chunk_end - off) % mf == 0) k = (span - off) / mf;
+        k = rest.n_full();
+        if (CH % mf == 0 && rest.n_pieces() == rest.n_full()) k = (span - off) / mf;
         k = std::max<uint64_t>(1, std::min<uint64_t>(k, g->audible_slots));
       }
       sp.n_chunks = (int)k;
@@ -1968,30 +2027,7 @@ int process_bus_impl(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_i
       if (bus_audible && word_cursor + k > g->audible_slots) return set_error(PG_ERR_PARAMETER, "the bus chain ran out of `audible` words (%zu): cut the call as the write was cut", g->audible_slots);
       const uint64_t word = word_cursor;
       word_cursor += k;
-      auto one = [&](const LaunchSpan& q, float* dst, int* flags) -> int {
-        PgLaunch B;
-        fill_launch(g, q, B);
-        B.mode = 0; B.n_units = 1; B.unit_order = nullptr; B.unit_base = main.unit_slot;
-        B.bus = dst; B.bus_audible = flags; B.audible_tab = nullptr; B.sched = nullptr;
-        bus_pipeline_setup(g, B);
-        HIP_TRY(pg_launch_units(B, s));
-        return PG_OK;
-      };
-      float* dst = d_bus + (done + off) * 2;
-      int* flags = bus_audible ? bus_audible + word : nullptr;
-      if (sp.n_cmds > 0 && sp.n_chunks > 1) {  // commands ride on a launch of the first block alone
-        LaunchSpan head = sp;
-        head.n_chunks = 1;
-        int rc = one(head, dst, flags);
-        if (rc) return rc;
-        LaunchSpan rest = sp;
-        rest.d_cmds = nullptr; rest.n_cmds = 0; rest.t0 += sp.n; rest.grid_off += sp.n; rest.n_chunks -= 1;
-        rc = one(rest, dst + (size_t)sp.n * 2, flags ? flags + 1 : nullptr);
-        if (rc) return rc;
-      } else {
-        int rc = one(sp, dst, flags);
-        if (rc) return rc;
-      }
+      { const int rc = launch_bus(g, d_bus + (done + off) * 2, sp, bus_audible ? bus_audible + word : nullptr, s); if (rc) return rc; }
       off += (uint64_t)sp.n * k;
     }
     done += span;
@@ -2024,8 +2060,8 @@ int pg_graph_process_bus_device(pg_graph* g, float* d_bus, size_t n_samples, uin
 int pg_graph_audible_words(pg_graph* g) { return g->audible_valid ? g->defer_words : 0; }
 uint64_t pg_graph_next_main_event(pg_graph* g, uint64_t pos_in_frames) {
   drain_control_messages(g);
-  for (const Event& e : g->mixers[0].events) if (e.sample_time > pos_in_frames) return e.sample_time;
-  return UINT64_MAX;
+  const uint64_t ahead = graph_frames_to_main_event(g, pos_in_frames);
+  return ahead == UINT64_MAX ? UINT64_MAX : pos_in_frames + ahead;
 }
 int pg_graph_export_audible(pg_graph* g, float* d_dst, int n_words, void* hip_stream) {
   if (n_words < 0 || (size_t)n_words > g->audible_slots) return set_error(PG_ERR_PARAMETER, "a write leaves at most %zu words", g->audible_slots);
@@ -2039,8 +2075,7 @@ int pg_graph_export_audible(pg_graph* g, float* d_dst, int n_words, void* hip_st
 int pg_graph_process_bus_device_flags(pg_graph* g, float* d_bus, size_t n_samples, uint64_t pos_in_frames, void* hip_stream, const float* d_flags, int n_words) {
   hipStream_t s = hip_stream ? (hipStream_t)hip_stream : g->stream;
   if (!d_flags) return bus_meter_record(g, process_bus_impl(g, d_bus, n_samples, pos_in_frames, s, nullptr), d_bus, n_samples, pos_in_frames, s);
-  const size_t fr = n_samples / 2, per_chunk = (PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames;
-  const size_t need = (fr / PG_MAX_FRAMES) * per_chunk + (fr % PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames;   // pieces of an event-free call (events add pieces: pg_graph_audible_words)
+  const size_t need = (size_t)span_audible_words(n_samples / 2, g->max_frames);   // pieces of an event-free call (events add pieces: pg_graph_audible_words)
   if (n_words < 0 || (size_t)n_words > g->audible_slots || (size_t)n_words < need) return set_error(PG_ERR_PARAMETER, "the bus chain needs one word per block of max_frames (%zu)", need);
   (void)hipSetDevice(g->device);
   hipLaunchKernelGGL(pg_float_to_words_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, s, d_flags, g->d_audible, n_words);

@@ -509,6 +509,23 @@ struct pg_graph {
   std::vector<std::pair<uint64_t, uint64_t>> write_end_max;   // largest end of the writes since a voice was added = first entry behind its number
 };
 
+// ---- the chunk grid, stated once (pg_dev.h: PG_MAX_FRAMES) ---------------------------------------------------------
+// A chunk of chunk_n frames rendered as pieces of at most mf frames (the graph's max_frames): n_full full pieces, then a shorter last one
+struct ChunkPieces {
+  uint64_t chunk_n, mf;
+  uint64_t n_pieces() const { return (chunk_n + mf - 1) / mf; }
+  uint64_t n_full() const { return chunk_n / mf; }
+  uint64_t piece_len(uint64_t p) const { return std::min<uint64_t>(mf, chunk_n - p * mf); }
+};
+static inline uint64_t pieces_per_chunk(uint64_t mf) { return ChunkPieces{PG_MAX_FRAMES, mf}.n_pieces(); }
+// `audible` words of a span of `frames` frames that starts on the chunk grid and holds no event: one per piece — whole chunks, then the pieces
+// of the last, shorter chunk
+static inline uint64_t span_audible_words(uint64_t frames, uint64_t mf) { return (frames / PG_MAX_FRAMES) * pieces_per_chunk(mf) + ChunkPieces{frames % PG_MAX_FRAMES, mf}.n_pieces(); }
+// Words of an `audible` table (pg_graph::audible_slots, the sharded handle's flag_stride): one per block of a launch sequence / piece of a chunk
+static inline size_t audible_table_words(size_t mf) { return std::max<size_t>(PG_AUDIBLE_SLOTS, (size_t)pieces_per_chunk(mf)); }
+// Per-unit output tables and meter spans are sized for the blocks of a launch sequence or the pieces of a chunk, whichever is more
+static inline size_t graph_table_blocks(const pg_graph* g) { return std::max<size_t>(g->max_blocks, (size_t)pieces_per_chunk(g->max_frames)); }
+
 // ---- graph internals used by the sharded handle and the sampler voices (pg_host.hip) ---------------------------
 int graph_quiesce(pg_graph* g);
 static inline int graph_fail(pg_graph* g, int code) { g->failed = true; return code; }
@@ -526,7 +543,7 @@ int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voic
 // Debug read-backs: waits for the graph's stream and the last write's, then copies `bytes` from device memory (PG_OK / PG_ERR_DEVICE)
 int graph_read_back(pg_graph* g, void* dst, const void* d_src, size_t bytes);
 bool graph_is_empty(const pg_graph* g);
-uint64_t graph_next_main_event(const pg_graph* g);
+uint64_t graph_frames_to_main_event(const pg_graph* g, uint64_t now);   // frames from `now` to the next main-mixer event behind it (UINT64_MAX: none); events due at `now` are not ahead
 int graph_enqueue_status(pg_graph* g, hipStream_t stream);
 void graph_collect_status(pg_graph* g);
 void graph_call_cuts(const pg_graph* g, uint64_t now, uint64_t chunk_n, std::vector<uint64_t>& cuts);

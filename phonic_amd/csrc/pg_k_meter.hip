@@ -210,8 +210,7 @@ int graph_meter_reserve(pg_graph* g) {
   // a chunk), a nested one has its own, cut where an ancestor splits its chunk (at most PG_MAX_CALLS calls per chunk)
   size_t nested = 0;
   for (const HostMixer& mx : g->mixers) nested += mx.depth >= 2 ? 1 : 0;
-  const size_t blocks = std::max<size_t>(g->max_blocks, (PG_MAX_FRAMES + g->max_frames - 1) / g->max_frames);
-  return meter_ring_reserve(g, n_mixers, (nested + 2) * (blocks + PG_MAX_CALLS + 2));
+  return meter_ring_reserve(g, n_mixers, (nested + 2) * (graph_table_blocks(g) + PG_MAX_CALLS + 2));
 }
 
 void graph_meter_release(pg_graph* g) {

@@ -666,8 +666,8 @@ static int sharded_render_segment(pg_sharded_graph* s, float* d_dst, size_t stag
   const size_t n = s->shards.size();
   pg_graph* root = s->shards[0];
   // words of the span: one per piece (whole chunks of ceil(PG_MAX_FRAMES / max_frames) pieces, then the pieces of the last, shorter chunk)
-  const size_t fr = n_samples / 2, per_chunk = (PG_MAX_FRAMES + s->max_frames - 1) / s->max_frames;
-  const int n_chunks = (int)std::min<size_t>((fr / PG_MAX_FRAMES) * per_chunk + (fr % PG_MAX_FRAMES + s->max_frames - 1) / s->max_frames, s->flag_stride);
+  const size_t fr = n_samples / 2;
+  const int n_chunks = (int)std::min<size_t>((size_t)span_audible_words(fr, s->max_frames), s->flag_stride);
   const bool rccl = s->reduce_mode == PG_REDUCE_RCCL;
   const bool direct = s->direct && !rccl;
   // Direct delivery in BANKS: a segment of at most stage_frames / PG_FLAG_BANKS frames (a real-time call) takes region b of the partial /
@@ -777,8 +777,7 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
   if (empty) return 0;
   const uint64_t frames = n_samples / 2, CH = PG_MAX_FRAMES;
   // spans hold whole chunks; the words of a span must fit the shards' word tables (flag_stride = max(64, pieces of one chunk))
-  const uint64_t per_chunk = (CH + s->max_frames - 1) / s->max_frames;
-  const uint64_t span_chunks = std::max<uint64_t>(1, std::min<uint64_t>(s->stage_frames / CH, s->flag_stride / per_chunk));
+  const uint64_t span_chunks = std::max<uint64_t>(1, std::min<uint64_t>(s->stage_frames / CH, s->flag_stride / pieces_per_chunk(s->max_frames)));
   uint64_t done = 0;
   size_t stage_off = 0;
   std::vector<uint64_t> cuts;
@@ -786,8 +785,7 @@ static size_t sharded_write_walk(pg_sharded_graph* s, float* d_out, bool contigu
     // the segment ends where the next main-mixer event of any shard comes due (events at or before `now` apply at the segment's head)
     const uint64_t now = pos + done;
     uint64_t seg = frames - done;
-    for (pg_graph* g : s->shards)
-      for (const Event& e : g->mixers[0].events) { if (e.sample_time > now) { seg = std::min<uint64_t>(seg, e.sample_time - now); break; } }
+    for (const pg_graph* g : s->shards) seg = std::min<uint64_t>(seg, graph_frames_to_main_event(g, now));
     uint64_t off = 0;
     while (off < seg) {
       uint64_t n = std::min<uint64_t>(seg - off, span_chunks * CH);
