@@ -181,9 +181,13 @@ def test_reverb_long_run_state():
 def test_delay_time_parallel_path_short_delays_and_lfo_phase(mode, ftyp, dlay):
     """The time-parallel DelayEffect path (LFO depths 0, nothing ramping): delays of a few ms force many chunks per block
     (chunk <= floor(delay_samples) - 1), both routing modes and the three feedback-filter types. The LFO only advances its phase
-    there (closed-form f32 accumulation); switching the LFO depths on afterwards hands over to the serial path, which must
-    continue from exactly the phase the reference would have — any drift shows up in the modulated blocks. The 375 ms case
-    (18 000 frames, the default) runs 45 blocks so that two echoes pass through the wet path before the hand-over."""
+    there (closed-form f32 accumulation); switching the LFO depths on afterwards must continue from exactly the phase the
+    reference would have — any drift shows up in the modulated blocks. Who renders those blocks follows from delay_fast_eligible:
+    at 1.4 and 2.0 ms the LFO -> time margin (0.02 * 50 * 1.01 + 0.01 = 1.02 ms) brings the shortest delay under 66 samples, so
+    the serial path takes over; at 3.5 and 375 ms the time-parallel paths keep the effect (delay_ramp_fast while the depths
+    ramp, then delay_fast, which renders LFO modulation itself from a per-chunk phase array) — the index log shows every read
+    of those blocks logged in the latter two cases and none in the former. The 375 ms case (18 000 frames, the default) runs 45
+    blocks so that two echoes pass through the wet path before the depths are switched on."""
     params = {"mode": mode, "dlay": dlay, "fdbk": 0.6, "ftyp": ftyp, "driv": 0.3, "lfor": 3.7}
     long_run = dlay > 100.0
     blocks = 45 if long_run else 7
