@@ -299,10 +299,10 @@ int pg_graph_voice_envelope_stage(pg_graph* g, int voice_id);
  * The granular parameters and the loop range change while the voice plays: pg_graph_set_voice_granular_parameter / _grain_loop_range below.
  * The mono buffer the pool reads is what create_granular_sample_buffer (sampler.rs:908-952) makes of a file: hand it over here as `mono_pcm`, or
  * let the device make it from a sample buffer (pg_graph_add_granular_voice_from_buffer below).
- * OUT OF SCOPE for granular voices: the note, voice-allocation and voice-stealing layer of Sampler and the Sampler's
- * base transpose, finetune, volume and panning parameters — they exist for FILE-playback samplers (pg_graph_add_sampler, below); a binding drives
- * granular voices one by one, as before (pg_graph_set_voice_speed / _volume / _panning carry the base parameters' effect);
- * AHDSR parameter changes on a running envelope. (The voice's playback-position status events — the start event, a Position per process call,
+ * The note, voice-allocation and voice-stealing layer of Sampler and its base transpose, finetune, volume and panning parameters exist for pools
+ * of such voices too: pg_graph_add_granular_sampler, below. A voice added HERE is a lone one: the host starts it once, a binding drives it with
+ * pg_graph_set_voice_speed / _volume / _panning.
+ * OUT OF SCOPE for granular voices: AHDSR parameter changes on a running envelope. (The voice's playback-position status events — the start event, a Position per process call,
  * the two Stopped records — are pg_graph_set_voice_status's, below.)
  * pg_granular_params = GranularParameters (granular.rs:241-266): overlap_mode 0 Cloud, 1 Sequential (:35-45); window 0 Hann, 1 Blackman,
  * 2 Triangle, 3 Tukey, 4 Trapezoid, 5 Exponential, 6 RampUp, 7 RampDown (:61-70); size in ms, density in Hz, playback_direction 0 Forward,
@@ -492,7 +492,7 @@ int64_t pg_graph_sample_buffer_waveform(pg_graph* g, int buffer_id, int source, 
  * and as UNVERIFIED against the crate). The matrix advances on the frames the voice renders only: not in front of its start time, not after it
  * has ended. A release touches no modulation source (note_off reaches envelope slots, and the sampler has none, sampler/modulation.rs:101-103).
  * In the reference the timed calls below reach every voice of a Sampler; here they address ONE voice — a binding loops over its voices.
- * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix; the note layer of a granular-mode Sampler (pg_graph_add_sampler plays files).
+ * OUT OF SCOPE: envelope modulation sources and the FunDSP generator's matrix. (The note layer of a granular-mode Sampler: pg_graph_add_granular_sampler.)
  * (pg_modulation_state::last[5] is the value a granular voice's Position records use, voice.rs:435-446: pg_graph_set_voice_status.) (The granular parameters
  * themselves change through pg_graph_set_voice_granular_parameter above; a route's sum applies to the parameter's value as of its frame.) */
 #define PG_MOD_SOURCES 4
@@ -598,9 +598,9 @@ int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_sta
  * The sharded handle has NO sampler entry points yet (tests/test_host_sharded_routing.py counts the header's handle-taking pg_sharded_* functions
  * against its fixed program): they follow in a change that may touch that program.
  * OUT OF SCOPE: samplers on the main mixer (its sources are one unit, one workgroup, each; the pool needs one workgroup that sees every slot — a
- * multi-voice source unit is the follow-up); granular-mode samplers (Sampler::with_granular_playback: their start runs through GrainPool::start
- * and the modulation state, built on the host today); AMP_* envelope-parameter changes while playing; playback status events of sampler voices
- * and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101). */
+ * multi-voice source unit is the follow-up); AMP_* envelope-parameter changes while playing; playback status events of sampler voices
+ * and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101).
+ * (Granular-mode samplers, Sampler::with_granular_playback: pg_graph_add_granular_sampler, below.) */
 #define PG_SAMPLER_MAX_VOICES 64
 typedef struct pg_sampler_options {
   uint32_t voice_count;      /* 1..=64, default 8 */
@@ -640,6 +640,62 @@ int pg_graph_sampler_set_note_panning(pg_graph* g, int sampler_id, int64_t note_
 int pg_graph_sampler_set_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
 int pg_graph_sampler_stop(pg_graph* g, int sampler_id, uint64_t sample_time);
 int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out);
+
+/* Granular-mode samplers: Sampler::with_granular_playback (src/generator/sampler.rs:598-637) — a pool of up to 64 granular voices (GrainPool<100>
+ * each, with or without a modulation matrix) that notes start, steal and release. The note layer runs on the device in a kernel of its own
+ * (pg_gsampler_kernel; DESIGN.md "Granular samplers"), between the grain launches of consecutive Sampler::write spans: a granular slot becomes free
+ * at the END of the Sampler::write in which its pool ran dry or its envelope went Idle (voice.rs:488-502), and the ends of those writes are the
+ * cuts of the owning mixer chain (its own events and its ancestors', mixed.rs:679-712) — until then the slot's scheduler, and its generator, run on.
+ * pg_graph_add_granular_sampler(g, mixer, buffer, opt, gopt): `opt` as for pg_graph_add_sampler (voice count 1..=64, envelope, transient, start
+ * time; null: the defaults). has_loop_range + loop_start / loop_end there are Sampler::set_loop_range before playback (voice.rs:329-338): source
+ * frames over the file's frame count, as f32; without it gopt->params' own normalised range applies, and without that the buffer's embedded loop
+ * (enable_granular_playback, voice.rs:353-360). `gopt` (not null):
+ *   params       the GranularParameters (checked by pg_granular_params_check); params.rng_state is the pools' base state (below);
+ *   modulation   null: no slot has a matrix (every `*_mod` input is 0.0: what a sampler without routings feeds, at a lower cost); else every slot
+ *                gets a matrix made as pg_graph_set_voice_modulation_matrix makes one — Lfo::new's three draws, then the rates, waveforms and
+ *                routes — but WITHOUT a note: velocity 0, keytracking 60 / 127 until the slot's first note_on; `velocity` and `note` of the
+ *                struct are not used, a note brings its own;
+ *   rng_states   null, or voice_count x 3 x 4 words: the Xoshiro256++ state of slot k's pool, LFO 1 and LFO 2 at rng_states[(3 k + j) * 4 ..]
+ *                (an all-zero state: SplitMix64(0x5EED0000) x 4, as everywhere). Without the table, slot k's generator j (0 pool, 1 LFO 1,
+ *                2 LFO 2) gets pg_granular_sampler_rng_state(given, k, j): `given` = params.rng_state for j = 0, modulation->lfo[j - 1].rng_state
+ *                else, all-zero replaced as above; z = (given[0] ^ rotl(given[1], 16) ^ rotl(given[2], 32) ^ rotl(given[3], 48)) +
+ *                (3 k + j + 1) * 0xD1B54A32D192ED03; the state is four SplitMix64 outputs from z, the low byte of the last word replaced by
+ *                3 k + j — so no two generators of a sampler share a state. The reference seeds from the OS: this rule is this implementation's.
+ * The mono buffer the pools read is the buffer's granular buffer (pg_graph_prepare_granular_buffer), shared by all slots. Refusals as for
+ * pg_graph_add_sampler (the main mixer included), plus what pg_granular_params_check / pg_modulation_params_check refuse and a null `gopt`.
+ * Every pg_graph_sampler_* call above works on such a sampler, with the same sample_time and start-time rules. What a message does:
+ *   note_on      next_free_voice_index as above (releasing = an envelope in Release); SamplerVoice::start (voice.rs:122-193): the pool is reset if
+ *                the slot was active (granular.rs:495-502: every grain deactivated, the primary cleared — the generator carries on), then
+ *                GrainPool::start (:474-489): trigger_phase 1, playhead = the position parameter, speed / volume / panning set DIRECTLY (a pool
+ *                has no smoothers: no ramps, no glide); AhdsrEnvelope::note_on(params, 1.0); ModulationMatrix::note_on (matrix.rs:394-408): both
+ *                LFOs reset, velocity = the note's volume, keytracking = note / 127;
+ *   note_off     with an envelope its note_off alone — the pool goes on triggering until Idle; without one GrainPool::stop: no new grains, the slot
+ *                is free with the write in which the last grain ends (the file source behind the voice is never written in this mode);
+ *   setters      the per-note ones and STRN / SFTN / SVOL / SPAN go to the pool as voice.rs:239-310 sends them, from that frame on.
+ * pg_graph_sampler_set_granular_parameter: Sampler::set_granular_parameter (sampler.rs:299-360) at exactly `sample_time`, resolved as
+ * pg_graph_set_voice_granular_parameter resolves it; it reaches every slot, playing or free; grains keep the window and loop range they were born
+ * with, the pool follows a new overlap mode. Dropped while the sampler stops, like every trigger. PG_ERR_STATE on a file sampler.
+ * Read-backs (debug; they wait for the graph's work): after a write each shows the state as of the end of that write, the last span closed.
+ * pg_graph_sampler_voice_grain_state / _voice_modulation_state: slot `slot`'s pool and matrix (PG_ERR_STATE: a file sampler, no matrix;
+ * PG_ERR_PARAMETER: no such slot); pg_graph_sampler_granular_params: the sampler's parameters and loop range.
+ * Exact / not exact: DESIGN.md. The sub-mixer that holds such a sampler counts it as a source that delivered a full block for as long as it lives.
+ * OUT OF SCOPE: granular samplers on the main mixer; the sharded handle; modulation messages to a sampler while it plays (routes, LFO rate and
+ * waveform: the matrix is what creation gave it); set_loop_range while playing; AMP_* changes while playing; playback status events of sampler
+ * voices and the sampler's own Stopped event; GeneratorPlaybackOptions::volume and ::panning; the reference's 54-entry message queue (the
+ * control ring and PG_ERR_QUEUE_FULL stand in for it). */
+typedef struct pg_granular_sampler_options {
+  pg_granular_params params;
+  const pg_modulation_params* modulation;   /* NULL: no matrix */
+  const uint64_t* rng_states;               /* NULL, or voice_count * 3 * 4 words */
+} pg_granular_sampler_options;
+void pg_granular_sampler_options_default(pg_granular_sampler_options* opt);
+int pg_granular_sampler_options_check(const pg_granular_sampler_options* opt);
+void pg_granular_sampler_rng_state(const uint64_t given[4], uint32_t slot, uint32_t generator, uint64_t out[4]);
+int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt);
+int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
+int pg_graph_sampler_voice_grain_state(pg_graph* g, int sampler_id, int slot, pg_grain_state* out);
+int pg_graph_sampler_voice_modulation_state(pg_graph* g, int sampler_id, int slot, pg_modulation_state* out);
+int pg_graph_sampler_granular_params(pg_graph* g, int sampler_id, pg_granular_params* out);
 
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and

@@ -384,6 +384,37 @@ def sampler_state_dict(st):
                 finetune=int(st.finetune), volume=np.float32(st.volume), panning=np.float32(st.panning), slots=slots)
 
 
+class GranularSamplerOptions(C.Structure):
+    """pg_granular_sampler_options: the GranularParameters of Sampler::with_granular_playback, an optional matrix for every slot, an optional table
+    of Xoshiro256++ states (voice_count x 3 x 4 words: slot k's pool, LFO 1, LFO 2)."""
+    _fields_ = [("params", GranularParams), ("modulation", C.POINTER(ModulationParams)), ("rng_states", C.POINTER(C.c_uint64))]
+
+
+def granular_sampler_options(params=None, modulation=None, rng_states=None):
+    """pg_granular_sampler_options_default with overrides. params: a GranularParams; modulation: a ModulationParams or None; rng_states: None, or
+    per slot three states of four u64 (pool, LFO 1, LFO 2). The returned struct keeps what it points to alive."""
+    o = GranularSamplerOptions()
+    load().pg_granular_sampler_options_default(C.byref(o))
+    if params is not None:
+        o.params = params
+    if modulation is not None:
+        o._modulation = modulation
+        o.modulation = C.pointer(modulation)
+    if rng_states is not None:
+        flat = [int(w) & (2**64 - 1) for slot in rng_states for gen in slot for w in gen]
+        o._rng_states = (C.c_uint64 * len(flat))(*flat)
+        o.rng_states = C.cast(o._rng_states, C.POINTER(C.c_uint64))
+    return o
+
+
+def granular_sampler_rng_state(given, slot, generator):
+    """pg_granular_sampler_rng_state: the state slot `slot`'s generator (0 pool, 1 LFO 1, 2 LFO 2) gets without an explicit table. No device."""
+    g = (C.c_uint64 * 4)(*[int(x) & (2**64 - 1) for x in (given if given is not None else (0, 0, 0, 0))])
+    out = (C.c_uint64 * 4)()
+    load().pg_granular_sampler_rng_state(g, int(slot), int(generator), out)
+    return tuple(int(x) for x in out)
+
+
 def make_init(params=None, reverb_seeds=None, lfo_seed=None):
     """Build a pg_effect_init. params: dict {fourcc-str: raw value}; reverb_seeds: (fpd_l, fpd_r, [16 phases]); lfo_seed: the four u64 of the
     Delay LFO's Xoshiro256++ state (Random / Smooth Random shapes)."""
@@ -531,6 +562,12 @@ GRAPH_ONLY_CALLS = (
     ("sampler_set_parameter", _int, [_int, _u32, _f32, _int, _u64]),
     ("sampler_stop", _int, [_int, _u64]),
     ("sampler_state", _int, [_int, _P(SamplerState)]),
+    # granular-mode samplers
+    ("add_granular_sampler", _int, [_int, _int, _P(SamplerOptions), _P(GranularSamplerOptions)]),
+    ("sampler_set_granular_parameter", _int, [_int, _u32, _f32, _int, _u64]),
+    ("sampler_voice_grain_state", _int, [_int, _int, _P(GrainState)]),
+    ("sampler_voice_modulation_state", _int, [_int, _int, _P(ModulationState)]),
+    ("sampler_granular_params", _int, [_int, _P(GranularParams)]),
 )
 
 # what only the sharded handle has (pg_sharded_create and _destroy: in load)
@@ -565,6 +602,9 @@ PLAIN_CALLS = (
     ("pg_sampler_options_check", _int, [_P(SamplerOptions)]),
     ("pg_sampler_param_count", _int, []),
     ("pg_sampler_param", _int, [_int, _P(ParamDesc)]),
+    ("pg_granular_sampler_options_default", None, [_P(GranularSamplerOptions)]),
+    ("pg_granular_sampler_options_check", _int, [_P(GranularSamplerOptions)]),
+    ("pg_granular_sampler_rng_state", None, [_P(_u64), _u32, _u32, _P(_u64)]),
     ("pg_modulation_params_default", None, [_P(ModulationParams)]),
     ("pg_modulation_params_check", _int, [_P(ModulationParams)]),
     ("pg_debug_sample_buffer_times", _int, [_vp, _int, _P(_f32)]),

@@ -44,6 +44,7 @@ enum CtrlType : int32_t {
   CT_SAMPLER_PARAM = 21,          // param = index in Sampler::base_parameters() order, value = resolved raw value
   CT_SAMPLER_STOP = 22,
   CT_SAMPLER_REMOVE = 23,         // RemoveSource: a message, not an event
+  CT_SAMPLER_GRAIN_PARAM = 24,    // a granular-mode sampler: param = index in Sampler::granular_parameters() order, value = resolved raw value
 };
 
 struct CtrlMsg {

@@ -424,6 +424,43 @@ struct PgGrainVoice {
 static_assert(sizeof(PgGrain) == 80 && sizeof(PgGrainPool) == 72 && sizeof(PgGrainParams) == 56 && sizeof(PgGrainVoice) % 8 == 0, "host and device agree on the layout");
 static_assert(sizeof(PgModLfo) == 64 && sizeof(PgGrainMod) == 400 && offsetof(PgGrainVoice, mod) % 8 == 0, "host and device agree on the layout");
 
+// ---- granular-mode samplers (pg_graph_add_granular_sampler; pg_gsampler_dev.h / pg_k_gsampler.hip): Sampler::with_granular_playback ----
+// A pool of note.n_voices granular voices that notes start, steal and release. Slot k renders through PgGrainVoice record grain0 + k (pg_grain_kernel)
+// into that record's staging buffer; the sub-mixer unit takes the frames through PgVoice note.voice0 + k, which is always `active` and carries no
+// envelope of the unit kernel's: whether a slot plays, its envelope and its end are THIS record's, decided by pg_gsampler_kernel between the
+// grain launches of consecutive Sampler::write spans. The sampler's PgSamplerRec in PgSamplerTab (same index: CMD_SAMPLER_*'s target) has
+// n_voices 0, so the unit kernel's sampler_command leaves its commands alone. A FREE slot's grain record has start_time UINT64_MAX.
+struct PgGSampler {
+  PgSamplerRec note;               // as for a file sampler; note.unit = the owning sub-mixer's unit slot
+  int32_t grain0;                  // slot 0's record in the graph's PgGrainVoice table
+  int32_t index;                   // CMD_SAMPLER_*'s target
+  uint64_t start_time;             // the mixer calls the sampler from here on
+  uint64_t span_t0;                // first frame of the Sampler::write span that is open (UINT64_MAX: none)
+  PgEnvParams env_params;          // with note.has_envelope
+  int32_t pad;
+  PgEnvState env[PG_SAMPLER_MAX_VOICES];
+  int32_t active[PG_SAMPLER_MAX_VOICES];   // SamplerVoice::is_active (voice.rs:100-102)
+};
+static_assert(sizeof(PgGSampler) % 8 == 0, "host and device agree on the layout");
+struct PgCmd;
+struct PgGSamplerLaunch {
+  PgGSampler* recs;                // the graph's granular-sampler records ...
+  const int32_t* live;             // ... and the ones workgroup b of the launch works on: live[b]
+  uint32_t n_recs;                 // records `recs` holds: no record at or beyond it is taken
+  uint32_t n_live;
+  uint32_t n_grains;               // records `grains` holds: no record at or beyond it is taken
+  PgGrainVoice* grains;
+  const PgCmd* cmds;               // the command list of the piece that holds frame `t` (PgLaunch::cmds) ...
+  int32_t n_cmds;
+  uint32_t frame;                  // ... and t relative to that piece's first frame
+  uint64_t t;                      // position of the boundary: the spans that end here are closed, the messages due here applied
+  uint64_t chunk_t0;               // position of frame 0 of the staging buffers: the start of the main mixer's chunk
+  int32_t chunk_first;             // t is the chunk's first frame: a boundary of every sampler
+  int32_t closing;                 // t is the chunk's end: close only
+  const double* speed_tab;         // PgSamplerTab::speed_tab
+  int32_t* stopped;                // PgSamplerTab::stopped (mapped host memory, indexed by PgGSampler::index)
+};
+
 // Parameter indices per effect kind = order of `Effect::parameters()` in the reference.
 enum { P_GAIN_GAIN = 0, P_GAIN_DCFM };
 enum { P_PAN_PAN = 0, P_PAN_WIDTH, P_PAN_INVL, P_PAN_INVR };
@@ -519,6 +556,8 @@ enum PgCmdType {
   CMD_SAMPLER_NOTE_PAN = 22,      // param = note id, value                                                                     (trigger_set_panning)
   CMD_SAMPLER_PARAM = 23,         // param = PG_SP_*, value = the resolved raw value, value64 = f64 bits of the new pitch factor (TRANSPOSE / FINETUNE)
   CMD_SAMPLER_STOP = 24,          //                                                                                            (Sampler::stop)
+  // a granular-mode sampler only (pg_graph_add_granular_sampler; pg_gsampler_kernel applies it, the unit kernels ignore it but end a segment at it):
+  CMD_SAMPLER_GRAIN_PARAM = 25,   // param = PG_GP_*, value = the resolved raw value (an enum's index as a float)               (Sampler::set_granular_parameter)
 };
 enum { PG_SP_TRANSPOSE = 0, PG_SP_FINETUNE, PG_SP_VOLUME, PG_SP_PANNING, PG_SP_COUNT };   // CMD_SAMPLER_PARAM's index: Sampler::base_parameters() (sampler.rs:120-127)
 // CMD_VOICE_GRAIN_PARAM's index: Sampler::granular_parameters() (sampler.rs:283-296)

@@ -142,6 +142,22 @@ DEV void mod_lfo_reset(PgModLfo& m) {
     m.jitter_target = lfo_random_bipolar(m.rng);
   }
 }
+// Sampler::set_granular_parameter (sampler.rs:299-360): the host has resolved the update to a raw value inside the descriptor's range
+DEVO void grain_set_parameter(PgGrainParams& p, uint32_t index, float value) {
+  switch (index) {
+    case PG_GP_OVERLAP_MODE: p.overlap_mode = (int32_t)value & 1; break;
+    case PG_GP_WINDOW: p.window = (int32_t)value & (PG_GRAIN_WINDOWS - 1); break;
+    case PG_GP_SIZE: p.size = value; break;
+    case PG_GP_DENSITY: p.density = value; break;
+    case PG_GP_VARIATION: p.variation = value; break;
+    case PG_GP_SPRAY: p.spray = value; break;
+    case PG_GP_PAN_SPREAD: p.pan_spread = value; break;
+    case PG_GP_DIRECTION: { const int32_t d = (int32_t)value; p.direction = d < 0 ? 0 : (d > 2 ? 2 : d); } break;
+    case PG_GP_POSITION: p.position = value; break;
+    case PG_GP_STEP: p.step = value; break;
+    default: break;
+  }
+}
 // One slot's contribution to a target's sum (ModulationMatrix::output, matrix.rs:201-231): LFOs are bipolar sources, velocity and keytracking
 // unipolar ones.
 DEV float mod_bipolar_source(float v, int bipolar) { return bipolar ? v : (v + 1.0f) / 2.0f; }

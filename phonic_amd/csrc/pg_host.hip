@@ -1659,6 +1659,7 @@ static bool write_prologue(pg_graph* g, size_t n_samples, uint64_t pos, hipStrea
   graph_sampler_poll(g);
   if (g->topo_dirty) { g->rows_free_fresh = false; if (rebuild_topology(g, stream)) { g->failed = true; return false; } }
   if (g->gran_live_dirty && graph_gran_upload_live(g, stream)) { g->failed = true; return false; }
+  if (g->gsamp_dirty && graph_gsampler_upload_live(g, stream)) { g->failed = true; return false; }
   if (!g->stream_voices.empty()) { g->rows_free_fresh = false; if (flush_stream_feeds(g, stream)) { g->failed = true; return false; } }
   if (g->overlap_stream != stream) { g->rows_free_fresh = false; g->overlap_stream = stream; }
   g->write_done_attached = false;
@@ -1794,6 +1795,10 @@ static int render_chunk(pg_graph* g, WriteCall& w, uint64_t span, const std::vec
   }
   if (n_pieces > g->unit_out_blocks) return set_error(PG_ERR_STATE, "per-unit buffers were not reserved for a chunk's pieces");
   if (g->metering) meter_collect_chunk(g, now, chunk_n, mf);   // (launched behind the chunk's sum)
+  // granular-mode samplers: where their mixer chains cut the chunk (taken while the chunk's events are still in their mixers' lists)
+  const bool gsamplers = graph_has_gsamplers(g);
+  std::vector<uint64_t> gs_cuts;
+  if (gsamplers) graph_gsampler_cuts(g, now, chunk_n, gs_cuts);
   std::vector<LaunchSpan> spans((size_t)n_pieces);
   bool pstat_live = false;   // playback status: some voice of the graph reports (pg_k_status.hip)
   for (int v : g->pstat.voices) pstat_live |= g->voices[v].mixer >= 0 && g->voices[v].pstat_on;
@@ -1818,7 +1823,7 @@ static int render_chunk(pg_graph* g, WriteCall& w, uint64_t span, const std::vec
       // (a round that will run its decision-scan kernel takes a short list there as the kernel's argument: no copy kernel on the stream)
       sp.n_cmds = (int)cmds.size();
       // (pg_grain_kernel reads the list in front of the scan: with living granular voices it travels by copy)
-      const bool by_scan = cmds.size() <= PG_CMD_PACK && g->gran_voices.empty() && level_concurrent(g, 0, sp, stream);
+      const bool by_scan = cmds.size() <= PG_CMD_PACK && g->gran_voices.empty() && !gsamplers && level_concurrent(g, 0, sp, stream);
       if (stage_commands(g, cmds, stream, &sp.d_cmds, by_scan ? &sp.h_cmds : nullptr)) return PG_ERR_DEVICE;
       // Which commands can leave the steady state behind them (cmd_keeps_steady)? Offline calls keep their super-block launches between
       // commands that cannot (notes that stop and start: bench.py --workload dyn --churn).
@@ -1837,6 +1842,17 @@ static int render_chunk(pg_graph* g, WriteCall& w, uint64_t span, const std::vec
   if (!g->gran_voices.empty()) for (uint64_t p = 0; p < n_pieces; ++p) {
     const LaunchSpan& sp = spans[(size_t)p];
     if (launch_grains(g, sp.t0, sp.n, now, sp.d_cmds, sp.n_cmds, stream)) return PG_ERR_DEVICE;
+  }
+  // granular-mode samplers: per span of their source-write grid — close the span before, apply the messages due at this one's first frame
+  // (pg_gsampler_kernel, reading the command list of the piece that holds that frame), render the span's grains — then close the last span
+  if (gsamplers) {
+    for (size_t i = 0; i <= gs_cuts.size(); ++i) {
+      const uint64_t t = i == 0 ? now : gs_cuts[i - 1], t_next = i < gs_cuts.size() ? gs_cuts[i] : now + chunk_n;
+      const LaunchSpan& sp = spans[(size_t)((t - now) / mf)];
+      if (launch_gsampler_boundary(g, t, (uint32_t)(t - sp.t0), sp.d_cmds, sp.n_cmds, now, i == 0, false, stream)) return PG_ERR_DEVICE;
+      if (launch_gsampler_grains(g, t, (uint32_t)(t_next - t), now, stream)) return PG_ERR_DEVICE;
+    }
+    if (launch_gsampler_boundary(g, now + chunk_n, 0, nullptr, 0, now, false, true, stream)) return PG_ERR_DEVICE;
   }
   if (pstat_live && graph_pstat_begin_chunk(g, pstat_cmds, stream)) return PG_ERR_DEVICE;
   for (size_t li = 0; li < g->levels.size(); ++li) {

@@ -58,6 +58,8 @@ struct PgGrainLaunch {
 };
 hipError_t pg_launch_grain(const PgGrainLaunch& L, hipStream_t stream);
 void pg_grain_build_lut(float* out);   // GRAIN_WINDOW_LUT, host side
+// ---- granular-mode samplers (pg_k_gsampler.hip): one pg_gsampler_kernel launch closes the spans that end at a boundary and opens the next ----
+hipError_t pg_launch_gsampler(const PgGSamplerLaunch& L, hipStream_t stream);
 
 // ---- errors ---------------------------------------------------------------------------------------------
 int set_error(int code, const char* fmt, ...);  // records the thread's last error message (pg_last_error_message) and returns `code`
@@ -272,6 +274,10 @@ struct HostSampler {
   uint64_t start_time = 0;         // the mixer does not call the sampler before this frame: messages due earlier are held until it (sampler_drain_message)
   bool alive = true;               // until pg_graph_remove_sampler / the removal of its mixer / `stopped` has been seen
   int transpose = 0, finetune = 0; // the base pitch as of the last event STAGED (events are staged in time order): what the next pitch factor is made of
+  // a granular-mode sampler (pg_graph_add_granular_sampler): its note layer is PgGSampler `rec` of pg_graph::d_gsamp (PgSamplerRec `rec` is inert),
+  // slot k renders through PgGrainVoice record grain0 + k; with_mod: every slot has a modulation matrix
+  bool granular = false, with_mod = false;
+  int grain0 = -1;
 };
 // A sample buffer on the device (pg_graph_add_sample_buffer): AudioFileBuffer behind an Arc (src/source/file/buffer.rs). The host holds one
 // reference until pg_graph_release_sample_buffer, every voice made from it one until its memory is released (graph_voice_release).
@@ -503,6 +509,15 @@ struct pg_graph {
   double* d_speed_tab = nullptr;
   MappedWords samp_stopped;              // one word per record
   std::atomic<int64_t> next_note_id{1};  // unique_note_id (generator.rs:32), per graph
+  // granular-mode samplers (pg_graph_add_granular_sampler): their note layer's records, indexed like d_samp's (a file sampler's entry is unused);
+  // the records of the living ones and of their slots' grain pools, uploaded when the set changes — what pg_gsampler_kernel and the
+  // pg_grain_kernel launches of their spans work on
+  PgGSampler* d_gsamp = nullptr;
+  size_t gsamp_cap = 0;
+  size_t n_gsamplers = 0;                // granular samplers ever added (the lists below are reserved for all of them)
+  DeviceTable<int32_t> d_gsamp_live, d_gsamp_grains;
+  std::vector<int32_t> gsamp_live, gsamp_grains;   // ... as the next upload puts them together (capacity kept across writes)
+  bool gsamp_dirty = false;
   PstatState pstat;                      // playback status events (pg_graph_enable_status)
   std::vector<SampleBuffer> sample_buffers;   // by buffer id (ids are never reused)
   uint64_t write_count = 0;        // writes that rendered frames so far, and the suffix maxima of their end positions (write number, end): the
@@ -577,6 +592,16 @@ void sampler_stage_command(pg_graph* g, PgCmd& c);     // an event leaves its mi
 void samplers_of_removed_mixers(pg_graph* g);          // pg_graph_remove_mixer: their ids are dead from here on
 int graph_gran_upload_live(pg_graph* g, hipStream_t stream);
 int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream);
+// granular-mode samplers (pg_sampler.hip). The living ones' source-write grid inside the chunk [now, now + chunk_n): the positions behind `now` at
+// which the mixer chain of any of them cuts (events of its mixer and of that mixer's ancestors, its start time), sorted. Called before the
+// chunk's events leave their mixers' lists.
+bool graph_has_gsamplers(const pg_graph* g);
+void graph_gsampler_cuts(const pg_graph* g, uint64_t now, uint64_t chunk_n, std::vector<uint64_t>& cuts);
+int graph_gsampler_upload_live(pg_graph* g, hipStream_t stream);
+// pg_gsampler_kernel at boundary `t` = frame `frame` of the piece whose command list is d_cmds (closing: t is the chunk's end) ...
+int launch_gsampler_boundary(pg_graph* g, uint64_t t, uint32_t frame, const PgCmd* d_cmds, int n_cmds, uint64_t chunk_t0, bool chunk_first, bool closing, hipStream_t stream);
+// ... and pg_grain_kernel over the span [t0, t0 + n) of the living samplers' slots
+int launch_gsampler_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, hipStream_t stream);
 // sample buffers (pg_sampler.hip; the conversion: pg_k_sample.hip)
 int sample_buffer_desc_check(const float* pcm, size_t n_frames, const pg_sample_buffer_desc* desc);   // PG_OK / PG_ERR_PARAMETER: no graph, no device
 SampleBuffer* sample_buffer_find(pg_graph* g, int buffer_id);      // the buffer while the host holds it, else null (PG_ERR_NOT_FOUND is set)

@@ -31,22 +31,6 @@ __device__ __forceinline__ bool grain_cmd_matches(const PgCmd& c, int voice) {
                                c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM || c.type == CMD_VOICE_GRAIN_PARAM ||
                                c.type == CMD_VOICE_GRAIN_LOOP);
 }
-// Sampler::set_granular_parameter (sampler.rs:299-360): the host has resolved the update to a raw value inside the descriptor's range
-__device__ __forceinline__ void grain_set_parameter(PgGrainParams& p, uint32_t index, float value) {
-  switch (index) {
-    case PG_GP_OVERLAP_MODE: p.overlap_mode = (int32_t)value & 1; break;
-    case PG_GP_WINDOW: p.window = (int32_t)value & (PG_GRAIN_WINDOWS - 1); break;
-    case PG_GP_SIZE: p.size = value; break;
-    case PG_GP_DENSITY: p.density = value; break;
-    case PG_GP_VARIATION: p.variation = value; break;
-    case PG_GP_SPRAY: p.spray = value; break;
-    case PG_GP_PAN_SPREAD: p.pan_spread = value; break;
-    case PG_GP_DIRECTION: { const int32_t d = (int32_t)value; p.direction = d < 0 ? 0 : (d > 2 ? 2 : d); } break;
-    case PG_GP_POSITION: p.position = value; break;
-    case PG_GP_STEP: p.step = value; break;
-    default: break;
-  }
-}
 // A route command's source and target, -1 when either is out of range (the host checks them: nothing out of range indexes the table)
 __device__ __forceinline__ int grain_route_source(const PgCmd& c) { const uint32_t s = (uint32_t)(c.value64 & 0xff); return s < PG_GMOD_SOURCES ? (int)s : -1; }
 __device__ __forceinline__ int grain_route_target(const PgCmd& c) { const uint32_t t = (uint32_t)((c.value64 >> 8) & 0xff); return t < PG_GMOD_TARGETS ? (int)t : -1; }

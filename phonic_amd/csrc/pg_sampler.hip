@@ -136,6 +136,8 @@ void graph_sampler_release(pg_graph* g) {
   if (g->d_samp) (void)pg_free(g->d_samp);
   if (g->d_speed_tab) (void)pg_free(g->d_speed_tab);
   g->samp_stopped.release();
+  if (g->d_gsamp) (void)pg_free(g->d_gsamp);
+  g->d_gsamp_live.release(); g->d_gsamp_grains.release();
 }
 
 // note_on belongs to a voice's start (voice.rs:181-184): neither an envelope nor a matrix for a voice that has rendered frames already.
@@ -173,6 +175,45 @@ int pg_ahdsr_params_check(const pg_ahdsr_params* p) {
   if (!(p->decay_scaling >= -1.0f && p->decay_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid decay scaling: %g. Must be in range [-1.0, 1.0]", (double)p->decay_scaling);
   if (!(p->sustain_level >= 0.0f && p->sustain_level <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid sustain level: %g. Must be in range [0.0, 1.0]", (double)p->sustain_level);
   if (!(p->release_scaling >= -1.0f && p->release_scaling <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid release scaling: %g. Must be in range [-1.0, 1.0]", (double)p->release_scaling);
+  return PG_OK;
+}
+
+// The debug read-backs of a granular record `rec`: a voice's, or a slot's of a granular-mode sampler
+static int grain_state_read(pg_graph* g, int rec, pg_grain_state* out) {
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  { const int rc = graph_read_back(g, r.get(), g->d_gran + rec, sizeof(PgGrainVoice)); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  const PgGrainPool& pool = r->pool;
+  out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
+  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->overlap_mode = pool.overlap_mode; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
+  memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) {
+    const PgGrain& s = r->grains[i];
+    pg_grain_slot& o = out->slots[i];
+    o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
+    o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
+  }
+  return PG_OK;
+}
+static int granular_params_read(pg_graph* g, int rec, pg_granular_params* out) {
+  PgGrainParams q;
+  { const int rc = graph_read_back(g, &q, (const char*)(g->d_gran + rec) + offsetof(PgGrainVoice, params), sizeof q); if (rc) return rc; }
+  grain_params_from_device(q, *out);
+  return PG_OK;
+}
+static int modulation_state_read(pg_graph* g, int rec, pg_modulation_state* out) {
+  PgGrainMod m;
+  { const int rc = graph_read_back(g, &m, (const char*)(g->d_gran + rec) + offsetof(PgGrainVoice, mod), sizeof m); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  for (int l = 0; l < 2; ++l) {
+    const PgModLfo& s = m.lfo[l];
+    pg_mod_lfo_state& o = out->lfo[l];
+    o.phase = s.phase; o.phase_inc = s.phase_inc; o.sample_hold = s.sample_hold; o.jitter_current = s.jitter_current; o.jitter_target = s.jitter_target; o.waveform = s.waveform;
+    memcpy(o.rng_state, s.rng, sizeof o.rng_state);
+  }
+  out->velocity = m.velocity; out->note_pitch = m.note_pitch;
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
+  for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
   return PG_OK;
 }
 
@@ -440,21 +481,7 @@ int64_t pg_graph_read_granular_buffer(pg_graph* g, int buffer_id, float* out, si
 int pg_graph_voice_grain_state(pg_graph* g, int voice_id, pg_grain_state* out) {
   if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
   if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  const HostVoice* hv = &g->voices[voice_id];
-  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
-  { const int rc = graph_read_back(g, r.get(), g->d_gran + hv->gran, sizeof(PgGrainVoice)); if (rc) return rc; }
-  memset(out, 0, sizeof *out);
-  const PgGrainPool& pool = r->pool;
-  out->trigger_phase = pool.trigger_phase; out->playhead = pool.playhead; out->playing_loop_range = pool.playing_loop_range;
-  out->trigger_new_grains = pool.trigger_new_grains; out->primary_slot = pool.primary; out->overlap_mode = pool.overlap_mode; out->speed = pool.speed; out->volume = pool.volume; out->panning = pool.panning;
-  memcpy(out->rng_state, pool.rng, sizeof out->rng_state);
-  for (int i = 0; i < PG_GRAIN_POOL; ++i) {
-    const PgGrain& s = r->grains[i];
-    pg_grain_slot& o = out->slots[i];
-    o.position = s.position; o.increment = s.increment; o.window_phase = s.window_phase; o.window_increment = s.window_increment;
-    o.samples_remaining = s.samples_remaining; o.volume = s.volume; o.panning = s.panning; o.active = s.active; o.window_mode = s.window_mode; o.has_loop_range = s.has_loop;
-  }
-  return PG_OK;
+  return grain_state_read(g, g->voices[voice_id].gran, out);
 }
 // ---- the granular parameters and the loop range while the voice plays (Sampler::set_granular_parameter, sampler.rs:299-360, :1132-1147;
 // SamplerMessage::SetLoopRange -> GrainPool::set_loop_range, sampler.rs:1246-1270, granular.rs:516-518) ----
@@ -480,11 +507,7 @@ int pg_graph_set_voice_grain_loop_range(pg_graph* g, int voice_id, int has_loop_
 int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params* out) {
   if (!g || !out) return set_error(PG_ERR_PARAMETER, "graph handle or output is null");
   if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
-  const HostVoice* hv = &g->voices[voice_id];
-  PgGrainParams q;
-  { const int rc = graph_read_back(g, &q, (const char*)(g->d_gran + hv->gran) + offsetof(PgGrainVoice, params), sizeof q); if (rc) return rc; }
-  grain_params_from_device(q, *out);
-  return PG_OK;
+  return granular_params_read(g, g->voices[voice_id].gran, out);
 }
 
 // ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
@@ -580,19 +603,7 @@ int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_sta
   if (voice_id < 0 || voice_id >= (int)g->voices.size() || g->voices[voice_id].gran < 0) return set_error(PG_ERR_NOT_FOUND, "Source with id %d is not a granular voice", voice_id);
   const HostVoice* hv = &g->voices[voice_id];
   if (!hv->mod) return set_error(PG_ERR_STATE, "Source with id %d has no modulation matrix", voice_id);
-  PgGrainMod m;
-  { const int rc = graph_read_back(g, &m, (const char*)(g->d_gran + hv->gran) + offsetof(PgGrainVoice, mod), sizeof m); if (rc) return rc; }
-  memset(out, 0, sizeof *out);
-  for (int l = 0; l < 2; ++l) {
-    const PgModLfo& s = m.lfo[l];
-    pg_mod_lfo_state& o = out->lfo[l];
-    o.phase = s.phase; o.phase_inc = s.phase_inc; o.sample_hold = s.sample_hold; o.jitter_current = s.jitter_current; o.jitter_target = s.jitter_target; o.waveform = s.waveform;
-    memcpy(o.rng_state, s.rng, sizeof o.rng_state);
-  }
-  out->velocity = m.velocity; out->note_pitch = m.note_pitch;
-  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { out->routes[s][t].amount = m.amount[s][t]; out->routes[s][t].bipolar = m.bipolar[s][t]; }
-  for (int t = 0; t < PG_MOD_TARGETS; ++t) out->last[t] = m.last[t];
-  return PG_OK;
+  return modulation_state_read(g, hv->gran, out);
 }
 
 }  // extern "C"
@@ -604,7 +615,7 @@ static HostSampler* sampler_find(pg_graph* g, int sampler_id) {   // owner threa
   if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || !g->samplers[sampler_id].alive) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return nullptr; }
   return &g->samplers[sampler_id];
 }
-static bool cmd_is_sampler_event(int cmd_type) { return cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP; }
+static bool cmd_is_sampler_event(int cmd_type) { return (cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP) || cmd_type == CMD_SAMPLER_GRAIN_PARAM; }
 // The pool leaves its mixer (RemoveSource, a mixer that drops an exhausted generator: mixed.rs:612-616): its voices are retired like removed
 // sources — their buffer references return when their memory is released — and what is still queued for it finds no source when it comes due
 static void sampler_retire(pg_graph* g, int sampler_id) {
@@ -619,12 +630,13 @@ static void sampler_retire(pg_graph* g, int sampler_id) {
   }
   for (Event& e : mx.events) if (cmd_is_sampler_event(e.cmd.type) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
   hs.alive = false;
+  if (hs.granular) g->gsamp_dirty = true;
   g->sampler_alive_tab.set((size_t)sampler_id, 0);
   g->topo_dirty = true;
 }
 void samplers_of_removed_mixers(pg_graph* g) {
   for (size_t i = 0; i < g->samplers.size(); ++i)
-    if (g->samplers[i].alive && g->mixers[g->samplers[i].mixer].removed) { g->samplers[i].alive = false; g->sampler_alive_tab.set(i, 0); }
+    if (g->samplers[i].alive && g->mixers[g->samplers[i].mixer].removed) { g->samplers[i].alive = false; g->sampler_alive_tab.set(i, 0); if (g->samplers[i].granular) g->gsamp_dirty = true; }
 }
 // Transient samplers whose `stopped` word the exact kernel has set: the mixer drops them (reads mapped host words: no wait)
 static void samplers_poll_stopped(pg_graph* g) {
@@ -676,9 +688,10 @@ static const SamplerEvent SAMPLER_EVENTS[] = {
   {pgc::CT_SAMPLER_NOTE_PAN, CMD_SAMPLER_NOTE_PAN, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},
   {pgc::CT_SAMPLER_PARAM, CMD_SAMPLER_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},   // (the pitch factor: sampler_stage_command)
   {pgc::CT_SAMPLER_STOP, CMD_SAMPLER_STOP, [](const pgc::CtrlMsg&, PgCmd&) {}},
+  {pgc::CT_SAMPLER_GRAIN_PARAM, CMD_SAMPLER_GRAIN_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},
 };
 bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
-  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_REMOVE) return false;
+  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_GRAIN_PARAM) return false;
   if (m.id < 0 || m.id >= (int)g->samplers.size() || !g->samplers[m.id].alive) return true;   // gone in the meantime: dropped
   if (m.type == pgc::CT_SAMPLER_REMOVE) { sampler_retire(g, m.id); return true; }
   const HostSampler& hs = g->samplers[m.id];
@@ -876,6 +889,23 @@ int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out) {
   const HostSampler& hs = g->samplers[sampler_id];
   (void)hipSetDevice(g->device);
   if (g->d_voices.flush()) return PG_ERR_DEVICE;   // (pool voices no write has carried to the device yet)
+  if (hs.granular) {   // the note layer's record is pg_gsampler_kernel's: which slot is active and where its envelope stands is written there
+    std::unique_ptr<PgGSampler> q(new PgGSampler);
+    { const int rc = graph_read_back(g, q.get(), g->d_gsamp + hs.rec, sizeof(PgGSampler)); if (rc) return rc; }
+    memset(out, 0, sizeof *out);
+    out->voice_count = hs.n_voices; out->stopping = q->note.stopping; out->stopped = q->note.stopped;
+    out->transpose = q->note.transpose; out->finetune = q->note.finetune; out->volume = q->note.base_volume; out->panning = q->note.base_panning;
+    for (int k = 0; k < hs.n_voices; ++k) {
+      const bool active = q->active[k] != 0;
+      pg_sampler_slot_state& o = out->slots[k];
+      o.note_id = active ? (int64_t)q->note.slots[k].note_id : 0;
+      o.release_start_frame = active ? q->note.slots[k].release_start_frame : UINT64_MAX;
+      o.note = q->note.slots[k].note; o.note_volume = q->note.slots[k].note_volume; o.note_panning = q->note.slots[k].note_panning;
+      o.envelope_stage = hs.has_envelope ? (int)q->env[k].stage : -1;
+      out->active_voices += active ? 1 : 0;
+    }
+    return PG_OK;
+  }
   std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
   std::vector<PgVoice> vs((size_t)hs.n_voices);
   std::vector<PgEnv> es((size_t)hs.n_voices);
@@ -895,6 +925,276 @@ int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out) {
     out->active_voices += active ? 1 : 0;
   }
   return PG_OK;
+}
+
+}  // extern "C"
+
+// ---- granular-mode samplers: Sampler::with_granular_playback (src/generator/sampler.rs:598-637). The note layer runs on the device in a kernel
+// of its own (pg_k_gsampler.hip, pg_gsampler_dev.h) between the grain launches of consecutive Sampler::write spans; here: construction, the
+// span grid, the launches, the granular-parameter message, the read-backs ----
+bool graph_has_gsamplers(const pg_graph* g) { return !g->gsamp_live.empty(); }
+// The living granular samplers and their slots' grain records -> the launch lists (inside write: capacity was reserved with the samplers)
+int graph_gsampler_upload_live(pg_graph* g, hipStream_t stream) {
+  g->gsamp_live.clear(); g->gsamp_grains.clear();
+  for (const HostSampler& hs : g->samplers) {
+    if (!hs.alive || !hs.granular) continue;
+    g->gsamp_live.push_back(hs.rec);
+    for (int k = 0; k < hs.n_voices; ++k) g->gsamp_grains.push_back(hs.grain0 + k);
+  }
+  g->gsamp_dirty = false;   // (a failure is the graph's: it renders nothing from then on)
+  const int rc = g->d_gsamp_live.upload_async(g->gsamp_live, stream);
+  return rc ? rc : g->d_gsamp_grains.upload_async(g->gsamp_grains, stream);
+}
+void graph_gsampler_cuts(const pg_graph* g, uint64_t now, uint64_t chunk_n, std::vector<uint64_t>& cuts) {
+  const uint64_t end = now + chunk_n;
+  for (const HostSampler& hs : g->samplers) {
+    if (!hs.alive || !hs.granular) continue;
+    if (hs.start_time > now && hs.start_time < end) cuts.push_back(hs.start_time);
+    // every event of the sampler's mixer ends a call of its sources, every event of an ancestor a call of the mixer itself (mixed.rs:679-712);
+    // the main mixer's events bound the chunk
+    for (int m = hs.mixer; m != 0; m = g->mixers[m].parent)
+      for (const Event& e : g->mixers[m].events) { if (e.sample_time >= end) break; if (e.sample_time > now) cuts.push_back(e.sample_time); }
+  }
+  std::sort(cuts.begin(), cuts.end());
+  cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+}
+int launch_gsampler_boundary(pg_graph* g, uint64_t t, uint32_t frame, const PgCmd* d_cmds, int n_cmds, uint64_t chunk_t0, bool chunk_first, bool closing, hipStream_t stream) {
+  if (g->gsamp_live.empty()) return PG_OK;
+  PgGSamplerLaunch L;
+  memset(&L, 0, sizeof L);
+  L.recs = g->d_gsamp; L.live = g->d_gsamp_live.d; L.n_recs = (uint32_t)g->gsamp_cap; L.n_live = (uint32_t)g->gsamp_live.size();
+  L.n_grains = (uint32_t)g->gran_n; L.grains = g->d_gran; L.cmds = d_cmds; L.n_cmds = d_cmds ? n_cmds : 0; L.frame = frame; L.t = t; L.chunk_t0 = chunk_t0;
+  L.chunk_first = chunk_first ? 1 : 0; L.closing = closing ? 1 : 0; L.speed_tab = g->d_speed_tab; L.stopped = g->samp_stopped.d;
+  HIP_TRY(pg_launch_gsampler(L, stream));
+  return PG_OK;
+}
+int launch_gsampler_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, hipStream_t stream) {
+  if (g->gsamp_grains.empty() || n == 0) return PG_OK;
+  PgGrainLaunch L;
+  memset(&L, 0, sizeof L);
+  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gsamp_grains.size(); L.live = g->d_gsamp_grains.d;
+  L.voices = g->d_voices.d; L.cmds = nullptr; L.n_cmds = 0; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->gran_ended.d;   // (everything a slot takes is applied at a span's edge, by pg_gsampler_kernel)
+  L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
+  HIP_TRY(pg_launch_grain(L, stream));
+  return PG_OK;
+}
+// Room for `n` records, indexed like the samplers. The graph is quiescent. A failure leaves the graph on its old records.
+static int graph_gsamp_reserve(pg_graph* g, size_t n) {
+  if (n <= g->gsamp_cap) return PG_OK;
+  const size_t cap = std::max<size_t>(next_pow2(n), 4);
+  PgGSampler* nt = nullptr;
+  HIP_TRY(pg_malloc((void**)&nt, cap * sizeof(PgGSampler)));
+  if (pg_memset(nt, 0, cap * sizeof(PgGSampler)) != hipSuccess || (g->d_gsamp && pg_memcpy(nt, g->d_gsamp, g->gsamp_cap * sizeof(PgGSampler), hipMemcpyDeviceToDevice) != hipSuccess)) {
+    (void)pg_free(nt);
+    return set_error(PG_ERR_DEVICE, "granular sampler table allocation failed");
+  }
+  if (g->d_gsamp) (void)pg_free(g->d_gsamp);
+  g->d_gsamp = nt; g->gsamp_cap = cap;
+  return PG_OK;
+}
+static uint64_t splitmix64_next(uint64_t& z) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); }
+static uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
+
+extern "C" {
+
+void pg_granular_sampler_options_default(pg_granular_sampler_options* o) {
+  if (!o) return;
+  memset(o, 0, sizeof *o);
+  pg_granular_params_default(&o->params);
+}
+int pg_granular_sampler_options_check(const pg_granular_sampler_options* o) {
+  if (!o) return set_error(PG_ERR_PARAMETER, "granular sampler options must not be null");
+  { const int rc = pg_granular_params_check(&o->params); if (rc) return rc; }
+  if (o->modulation) { const int rc = pg_modulation_params_check(o->modulation); if (rc) return rc; }
+  return PG_OK;
+}
+void pg_granular_sampler_rng_state(const uint64_t given[4], uint32_t slot, uint32_t generator, uint64_t out[4]) {
+  if (!out) return;
+  uint64_t base[4] = {0, 0, 0, 0};
+  rng_state_from(given ? given : base, base);
+  const uint64_t index = (uint64_t)slot * 3u + (uint64_t)(generator % 3u);
+  uint64_t z = (base[0] ^ rotl64(base[1], 16) ^ rotl64(base[2], 32) ^ rotl64(base[3], 48)) + (index + 1u) * 0xD1B54A32D192ED03ull;
+  for (int i = 0; i < 4; ++i) out[i] = splitmix64_next(z);
+  out[3] = (out[3] & ~0xFFull) | (index & 0xFFull);
+  if ((out[0] | out[1] | out[2] | out[3]) == 0) out[0] = 1;
+}
+int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt) {
+  pg_sampler_options def;
+  if (!opt) { pg_sampler_options_default(&def); opt = &def; }
+  { const int rc = pg_sampler_options_check(opt); if (rc) return -rc; }
+  { const int rc = pg_granular_sampler_options_check(gopt); if (rc) return -rc; }
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (mixer_id == PG_MAIN_MIXER) return -set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, the pool is one source of one mixer");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  if (!sample_buffer_find(g, buffer_id)) return -PG_ERR_NOT_FOUND;
+  {
+    const SampleBuffer& b0 = g->sample_buffers[buffer_id];
+    if (opt->has_loop_range && (opt->loop_start >= b0.n_frames || opt->loop_end > b0.n_frames)) return -set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%zu", (unsigned long long)opt->loop_start, (unsigned long long)opt->loop_end, b0.n_frames);
+  }
+  { const int rc = pg_graph_prepare_granular_buffer(g, buffer_id); if (rc) return -rc; }   // Sampler::create_granular_sample_buffer, shared by all slots
+  drain_control_messages(g);
+  if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  const SampleBuffer sb = g->sample_buffers[buffer_id];
+  const int n = (int)opt->voice_count, sampler_id = (int)g->samplers.size();
+  // the pool's loop range: Sampler::set_loop_range (voice.rs:329-338) where the options carry one, else the parameters' own, else the file's
+  // embedded one (enable_granular_playback, voice.rs:353-360) — source frames over the FILE's frame count, as f32
+  pg_granular_params q = gopt->params;
+  const float total = (float)sb.n_frames;
+  if (opt->has_loop_range) { q.has_loop_range = 1; q.loop_start = (float)opt->loop_start / total; q.loop_end = (float)opt->loop_end / total; }
+  else if (!q.has_loop_range && sb.has_loop) { q.has_loop_range = 1; q.loop_start = (float)sb.loop_start / total; q.loop_end = (float)sb.loop_end / total; }
+  // a slot as the mixer sees it: a stereo source at the graph's rate that the mixer keeps, whose frames pg_grain_kernel stages; always `active` —
+  // whether the slot plays is the note layer's (PgGSampler::active), a free slot's staged frames are zero
+  pg_voice_options vo;
+  pg_voice_options_default(&vo);
+  vo.non_transient = 1; vo.start_time = opt->start_time;
+  PgVoice v;
+  voice_init_neutral(g, v, &vo, 1.0f, 0.0f);
+  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
+  v.current_speed = 1.0; v.target_speed = 1.0;
+  v.sched_class = -1;
+  if (graph_samp_reserve(g, g->samplers.size() + 1) || graph_gsamp_reserve(g, g->samplers.size() + 1) || graph_gran_reserve(g, g->gran_n + (size_t)n)) return -graph_fail(g, PG_ERR_DEVICE);
+  {  // the launch lists hold every granular sampler's record and slots: graph_gsampler_upload_live runs inside write and must not allocate
+    size_t slots = (size_t)n;
+    for (const HostSampler& hs : g->samplers) if (hs.granular) slots += (size_t)hs.n_voices;
+    if (g->d_gsamp_live.reserve(g->n_gsamplers + 1) || g->d_gsamp_grains.reserve(slots)) return -graph_fail(g, PG_ERR_DEVICE);
+    g->gsamp_live.reserve(g->d_gsamp_live.cap); g->gsamp_grains.reserve(g->d_gsamp_grains.cap);
+  }
+  if (!g->gran_voices.empty()) g->gran_live_dirty = true;   // (graph_gran_reserve may have moved the lone voices' launch list: it is uploaded again)
+  std::vector<void*> stages;
+  auto release = [&]() { for (void* p : stages) (void)pg_free(p); };
+  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
+  for (int k = 0; k < n; ++k) {
+    void* p = nullptr;
+    if (pg_malloc(&p, stage_bytes) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler allocation failed")); }
+    stages.push_back(p);
+    if (pg_memset(p, 0, stage_bytes) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler allocation failed")); }
+  }
+  int voice0 = -1;
+  for (int k = 0; k < n; ++k) {
+    int di = -1;
+    const int rc = g->d_voices.push(v, &di);
+    if (rc || (k > 0 && di != voice0 + k)) { release(); return -graph_fail(g, rc ? rc : set_error(PG_ERR_STATE, "pool voices are not contiguous")); }
+    if (k == 0) voice0 = di;
+  }
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + (size_t)n, (size_t)(voice0 + n)))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
+  (void)hipSetDevice(g->device);
+  auto fail_upload = [&]() { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler upload failed")); };
+  // the slots' grain records: GrainPool::new (granular.rs:384-429) and, with a matrix, create_matrix (voice.rs:341-373) per slot — no note yet
+  const int grain0 = (int)g->gran_n;
+  std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
+  for (int k = 0; k < n; ++k) {
+    memset(r.get(), 0, sizeof(PgGrainVoice));
+    grain_params_to_device(q, r->params);
+    PgGrainPool& pool = r->pool;
+    if (gopt->rng_states) memcpy(pool.rng, gopt->rng_states + ((size_t)k * 3 + 0) * 4, sizeof pool.rng);
+    else pg_granular_sampler_rng_state(q.rng_state, (uint32_t)k, 0, pool.rng);
+    if ((pool.rng[0] | pool.rng[1] | pool.rng[2] | pool.rng[3]) == 0) rng_state_from(pool.rng, pool.rng);
+    pool.trigger_new_grains = 1; pool.trigger_phase = 0.0f;
+    pool.speed = 1.0; pool.volume = 1.0f; pool.panning = 0.0f;
+    pool.playhead = 0.0f; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;
+    for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
+    r->pcm = sb.d_mono; r->n_frames = (uint64_t)sb.mono_frames; r->staged = (float*)stages[(size_t)k]; r->stage_pos = 0;
+    r->start_time = UINT64_MAX;   // a free slot
+    r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = voice0 + k; r->has_env = 0;
+    if (gopt->modulation) {
+      const pg_modulation_params* p = gopt->modulation;
+      PgGrainMod& m = r->mod;
+      m.on = 1;
+      for (int l = 0; l < 2; ++l) {
+        PgModLfo& o = m.lfo[l];
+        if (gopt->rng_states) memcpy(o.rng, gopt->rng_states + ((size_t)k * 3 + 1 + (size_t)l) * 4, sizeof o.rng);
+        else pg_granular_sampler_rng_state(p->lfo[l].rng_state, (uint32_t)k, 1 + (uint32_t)l, o.rng);
+        if ((o.rng[0] | o.rng[1] | o.rng[2] | o.rng[3]) == 0) rng_state_from(o.rng, o.rng);
+        o.phase = 0.0f;   // Lfo::new (lfo.rs:70-86) draws its three random values, then the parameter updates in front of the first note
+        o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
+        o.phase_inc = (float)((double)mod_clamp_rate(p->lfo[l].rate_hz) / (double)g->sample_rate);
+        o.waveform = p->lfo[l].waveform;
+      }
+      for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {
+        const pg_mod_route& rt = p->routes[s][t];
+        if (fabsf(rt.amount) >= 0.001f) { m.amount[s][t] = rt.amount; m.bipolar[s][t] = rt.bipolar ? 1 : 0; }
+      }
+      m.velocity = 0.0f; m.note_pitch = 60.0f / 127.0f;   // the two static sources before the slot's first note (processor.rs:236-244, :292-298)
+    }
+    const int32_t rec = grain0 + k;
+    if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
+        pg_memcpy(g->d_grain_of_voice + voice0 + k, &rec, sizeof rec, hipMemcpyHostToDevice) != hipSuccess) return fail_upload();
+    g->gran_ended[(size_t)rec] = 0;
+  }
+  g->gran_n += (size_t)n;
+  // the note layer's record; the PgSamplerRec of the same index stays inert (n_voices 0): the unit kernel's sampler_command leaves the commands alone
+  std::unique_ptr<PgGSampler> gs(new PgGSampler);
+  memset(gs.get(), 0, sizeof(PgGSampler));
+  gs->note.unit = g->mixers[mixer_id].unit_slot; gs->note.voice0 = voice0; gs->note.n_voices = n; gs->note.has_envelope = opt->has_envelope ? 1 : 0; gs->note.transient = opt->transient ? 1 : 0;
+  gs->note.base_volume = 1.0f; gs->note.base_panning = 0.0f; gs->note.pitch_factor = std::pow(2.0, 0.0 / 12.0 + 0.0 / 1200.0);
+  for (int k = 0; k < PG_SAMPLER_MAX_VOICES; ++k) { gs->note.slots[k].release_start_frame = UINT64_MAX; gs->note.slots[k].note = 60; gs->note.slots[k].note_volume = 1.0f; }   // SamplerVoice::new (voice.rs:51-55)
+  gs->grain0 = grain0; gs->index = sampler_id; gs->start_time = opt->start_time; gs->span_t0 = UINT64_MAX;
+  if (opt->has_envelope) gs->env_params = ahdsr_build_params(opt->envelope, g->sample_rate);   // (every slot's envelope: Idle until its first note_on)
+  std::unique_ptr<PgSamplerRec> inert(new PgSamplerRec);
+  memset(inert.get(), 0, sizeof(PgSamplerRec));
+  inert->unit = -1;
+  if (pg_memcpy(g->d_gsamp + sampler_id, gs.get(), sizeof(PgGSampler), hipMemcpyHostToDevice) != hipSuccess ||
+      pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, inert.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess ||
+      samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess || graph_env_head_refresh(g)) return fail_upload();
+  g->samp_stopped[(size_t)sampler_id] = 0;
+  // the last slot goes in first, so that the mixer meets — and sums — the pool in slot order (sampler.rs:989-1006; mixed.rs:324-329)
+  HostSampler hs;
+  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
+  hs.granular = true; hs.with_mod = gopt->modulation != nullptr; hs.grain0 = grain0;
+  for (int k = n - 1; k >= 0; --k) {
+    HostVoice hv;
+    hv.sbuf = buffer_id; hv.sampler = sampler_id; hv.d_stage = stages[(size_t)k];
+    stages[(size_t)k] = nullptr;   // (the voice owns it from here on)
+    hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
+    g->sample_buffers[buffer_id].use_count += 1;
+    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
+    if (id < 0) { release(); return id; }
+    if (k == 0) hs.voice_id_slot0 = id;
+  }
+  g->samplers.push_back(hs);
+  g->n_gsamplers += 1;
+  g->gsamp_dirty = true;
+  if (!g->sampler_alive_tab.append(2)) return -set_error(PG_ERR_STATE, "too many samplers");   // (2: alive and granular, readable from any thread)
+  return sampler_id;
+}
+int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  const int pi = find_granular_param(fourcc);
+  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown granular playback parameter 0x%08x", fourcc);
+  if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  if (g->sampler_alive_tab.get((size_t)sampler_id) != 2) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no granular parameters", sampler_id);
+  float raw;
+  if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) return PG_OK;   // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = pgc::CT_SAMPLER_GRAIN_PARAM; m.id = sampler_id; m.param = pi; m.value = raw; m.sample_time = sample_time;
+  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
+  return PG_OK;
+}
+// The granular sampler behind `sampler_id` for a read-back (as pg_graph_sampler_state finds it) and the grain record of its slot; < 0: -PG_ERR_*
+static int gsampler_slot_record(pg_graph* g, int sampler_id, int slot, const void* out, bool need_mod) {
+  if (!out) return -set_error(PG_ERR_PARAMETER, "output is null");
+  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
+    return -set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  const HostSampler& hs = g->samplers[sampler_id];
+  if (!hs.granular) return -set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no grain pools", sampler_id);
+  if (slot < 0 || slot >= hs.n_voices) return -set_error(PG_ERR_PARAMETER, "Invalid slot: %d. The sampler has %d", slot, hs.n_voices);
+  if (need_mod && !hs.with_mod) return -set_error(PG_ERR_STATE, "Sampler with id %d has no modulation matrix", sampler_id);
+  return hs.grain0 + slot;
+}
+int pg_graph_sampler_voice_grain_state(pg_graph* g, int sampler_id, int slot, pg_grain_state* out) {
+  const int rec = gsampler_slot_record(g, sampler_id, slot, out, false);
+  return rec < 0 ? -rec : grain_state_read(g, rec, out);
+}
+int pg_graph_sampler_voice_modulation_state(pg_graph* g, int sampler_id, int slot, pg_modulation_state* out) {
+  const int rec = gsampler_slot_record(g, sampler_id, slot, out, true);
+  return rec < 0 ? -rec : modulation_state_read(g, rec, out);
+}
+int pg_graph_sampler_granular_params(pg_graph* g, int sampler_id, pg_granular_params* out) {   // (every slot holds the sampler's one parameter set)
+  const int rec = gsampler_slot_record(g, sampler_id, 0, out, false);
+  return rec < 0 ? -rec : granular_params_read(g, rec, out);
 }
 
 }  // extern "C"

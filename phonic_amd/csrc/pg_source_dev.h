@@ -1087,6 +1087,8 @@ DEVO int voice_write(PgVoice* v, float* out, int frames, int pending_stop, const
     for (int i = tid; i < 2 * frames; i += nt) out[i] = staged_ok ? src[i] : 0.0f;
     __syncthreads();
     if (env != nullptr) ahdsr_apply(v, env, out, frames, S);
+    // (a slot of a granular-mode sampler never ends HERE: pg_gsampler_kernel's closing launch, in front of every unit kernel of the chunk, has freed
+    // each slot whose pool ran dry and set its exhausted_at back to UINT64_MAX — gs_close, pg_gsampler_dev.h — so the test below finds nothing)
     if (tid == 0 && ask_ends && gr->exhausted_at < src_time + (uint64_t)frames) v->finished = 1;
     __syncthreads();
     return frames * 2;

@@ -75,6 +75,38 @@ class Graph(GraphHandle):
         """Sampler::stop: all notes off; a transient sampler stops for good once its last voice has ended."""
         self._check(self._lib.pg_graph_sampler_stop(self._h, sampler, sample_time))
 
+    # -- granular-mode samplers: Sampler::with_granular_playback — pools of granular voices that notes start, steal and release ----------
+    def add_granular_sampler(self, mixer_id, buffer_id, params=None, modulation=None, rng_states=None, options=None, **kw):
+        """A pool of `voice_count` granular voices over sample buffer `buffer_id`'s granular mono buffer in sub-mixer `mixer_id`. params: a
+        _capi.GranularParams (default: GranularParameters::default()); modulation: a _capi.ModulationParams (every slot gets such a matrix) or
+        None (no matrix); rng_states: None, or per slot three Xoshiro256++ states (pool, LFO 1, LFO 2); `options` / keywords as for add_sampler.
+        Every sampler_* call works on the returned id."""
+        o = options if options is not None else _capi.sampler_options(**kw)
+        go = _capi.granular_sampler_options(params if params is not None else _capi.granular_params(), modulation, rng_states)
+        return self._id(self._lib.pg_graph_add_granular_sampler(self._h, mixer_id, buffer_id, C.byref(o), C.byref(go)))
+
+    def sampler_set_granular_parameter(self, sampler, id4, value, sample_time=0, normalized=False):
+        """Sampler::set_granular_parameter for one of _capi.GRANULAR_PARAM_IDS, in front of frame sample_time: every slot, playing or free."""
+        self._check(self._lib.pg_graph_sampler_set_granular_parameter(self._h, sampler, _capi.fourcc(id4), float(value), 1 if normalized else 0, sample_time))
+
+    def sampler_voice_grain_state(self, sampler, slot):
+        """Slot `slot`'s GrainPool as _capi.grain_state_dict gives it (debug read-back: waits for the graph's work)."""
+        st = _capi.GrainState()
+        self._check(self._lib.pg_graph_sampler_voice_grain_state(self._h, sampler, slot, C.byref(st)))
+        return _capi.grain_state_dict(st)
+
+    def sampler_voice_modulation_state(self, sampler, slot):
+        """Slot `slot`'s modulation matrix as _capi.modulation_state_dict gives it."""
+        st = _capi.ModulationState()
+        self._check(self._lib.pg_graph_sampler_voice_modulation_state(self._h, sampler, slot, C.byref(st)))
+        return _capi.modulation_state_dict(st)
+
+    def sampler_granular_params(self, sampler):
+        """The sampler's granular parameters and loop range as _capi.granular_params_dict gives them."""
+        p = _capi.GranularParams()
+        self._check(self._lib.pg_graph_sampler_granular_params(self._h, sampler, C.byref(p)))
+        return _capi.granular_params_dict(p)
+
     def sampler_state(self, sampler):
         """The slot table and the sampler's own state as a dict (debug read-back: waits for the graph's work)."""
         st = _capi.SamplerState()
