@@ -598,8 +598,9 @@ int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_sta
  * The sharded handle has NO sampler entry points yet (tests/test_host_sharded_routing.py counts the header's handle-taking pg_sharded_* functions
  * against its fixed program): they follow in a change that may touch that program.
  * OUT OF SCOPE: samplers on the main mixer (its sources are one unit, one workgroup, each; the pool needs one workgroup that sees every slot — a
- * multi-voice source unit is the follow-up); AMP_* envelope-parameter changes while playing; playback status events of sampler voices
- * and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101).
+ * multi-voice source unit is the follow-up); the AMP_* envelope ids through pg_graph_sampler_set_parameter (they have a call and a table of
+ * their own: pg_graph_sampler_set_envelope_parameter, below); SetLoopRange on a file sampler while it plays; playback status events of sampler
+ * voices and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101).
  * (Granular-mode samplers, Sampler::with_granular_playback: pg_graph_add_granular_sampler, below.) */
 #define PG_SAMPLER_MAX_VOICES 64
 typedef struct pg_sampler_options {
@@ -679,10 +680,41 @@ int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out);
  * pg_graph_sampler_voice_grain_state / _voice_modulation_state: slot `slot`'s pool and matrix (PG_ERR_STATE: a file sampler, no matrix;
  * PG_ERR_PARAMETER: no such slot); pg_graph_sampler_granular_params: the sampler's parameters and loop range.
  * Exact / not exact: DESIGN.md. The sub-mixer that holds such a sampler counts it as a source that delivered a full block for as long as it lives.
- * OUT OF SCOPE: granular samplers on the main mixer; the sharded handle; modulation messages to a sampler while it plays (routes, LFO rate and
- * waveform: the matrix is what creation gave it); set_loop_range while playing; AMP_* changes while playing; playback status events of sampler
- * voices and the sampler's own Stopped event; GeneratorPlaybackOptions::volume and ::panning; the reference's 54-entry message queue (the
- * control ring and PG_ERR_QUEUE_FULL stand in for it). */
+ * Messages that change what EVERY voice of the pool does while notes sound (Sampler::process_playback_messages, sampler.rs:656-731). Any thread,
+ * through the control ring, with the sample_time, start-time and same-frame ordering rules of the other sampler messages (a message stamped before
+ * the start time acts at the start time); dropped while the sampler stops (:663-664); PG_ERR_NOT_FOUND for an unknown or removed id; argument
+ * checks first, a null handle last.
+ *   pg_graph_sampler_set_envelope_parameter   SetParameter(AMP_*) -> set_envelope_parameter (:184-217, :1122-1131) on a file sampler AND a granular
+ *       one: AATK Attack, AHLD Hold, ADCY Decay, AREL Release (0..=10 s, Exponential(2.0), defaults 0.001 / 0.75 / 0.5 / 1.0) and ASTN Sustain
+ *       (0..=1, linear, 0.75) of the pool's ONE AhdsrParameters. Raw values are clamped, normalized ones clamped to 0..=1 and denormalized
+ *       (:862-883). PG_ERR_PARAMETER: an unknown FourCC, a NaN, a sampler without an envelope (the reference's "Invalid or unknown sampler
+ *       parameter", :1128-1131, :1189). The setters are not independent (ahdsr.rs:143-249): set_sustain_level leaves decay_rate as it is,
+ *       set_decay_time divides (1 - sustain) as it holds THEN, a zero time is a rate of f32::MAX, a Hold in progress keeps its remaining samples.
+ *       Messages may be sent out of time order, so the host resolves each one where its event leaves the mixer's sorted list: an ADCY sent first
+ *       but due behind an ASTN sees the new sustain. A time goes through Duration::from_secs_f32(s.max(0.0)).as_secs_f32() (:191-208):
+ *       nanoseconds rounded to nearest (ties to even), then `secs as f32 + nanos as f32 / 1e9f32` — 4e-10 s is a zero Duration and a rate of
+ *       f32::MAX, 0.6e-9 s is 1 ns. That rounding rule is the standard library documentation's; it is UNVERIFIED against the library's source,
+ *       which this project does not hold. pg_graph_sampler_set_parameter does NOT take these ids: the two calls have disjoint tables.
+ *   pg_sampler_envelope_param_count / pg_sampler_envelope_param   the five descriptors in Sampler::envelope_parameters() order (:173-181).
+ *   pg_graph_sampler_set_modulation / _clear_modulation / _set_lfo_rate / _set_lfo_waveform   SetModulation / ClearModulation and
+ *       SetParameter(ML1R | ML2R | ML1W | ML2W) (:704-720, :1148-1186, :1210-1244) for the matrix of every slot, playing or free; sources, targets,
+ *       LFO indices, waveforms, the amount range, the 0.001 threshold and the rate clamp are pg_graph_set_voice_modulation's / _lfo_rate's /
+ *       _lfo_waveform's. A rate or waveform changes nothing else of the LFO (no draw, no phase change); a later note_on resets both LFOs and keeps
+ *       the rate, waveform and routes a message gave them. PG_ERR_STATE: a file sampler ("only available when granular playback is enabled"),
+ *       a granular sampler created with modulation == NULL (it has no matrix to route in: that mode is this implementation's).
+ *   pg_graph_sampler_set_loop_range   SamplerMessage::SetLoopRange (:1246-1271, voice.rs:312-339) on a granular sampler: source frames of the
+ *       sampler's buffer, normalised as at creation (`start as f32 / frame_count as f32`); has_loop_range == 0 is SetLoopRange(None): NO loop,
+ *       not the buffer's embedded one. Every slot's pool takes it; playing_loop_range, the playhead and living grains keep what they have
+ *       (granular.rs:516-518). PG_ERR_PARAMETER: start >= end, start >= frame_count, end > frame_count. PG_ERR_STATE: a file sampler.
+ *   pg_graph_sampler_envelope_params   debug read-back (waits for the graph's work): the AhdsrParameters as the device holds them — for a file
+ *       sampler slot `slot`'s own copy, for a granular one the sampler's one set (`slot` must still name a slot: PG_ERR_PARAMETER).
+ *       PG_ERR_STATE: a sampler without an envelope. zero_times: bit 0 hold, bit 1 decay, bit 2 release time is zero.
+ * OUT OF SCOPE: granular samplers on the main mixer; the sharded handle; modulation messages to a sampler created WITHOUT a matrix (with one:
+ * pg_graph_sampler_set_modulation and the LFO calls above); set_loop_range while playing on FILE samplers (it would move where a playing
+ * PreloadedFileSource wraps; granular ones: pg_graph_sampler_set_loop_range); the AMP_* ids through pg_graph_sampler_set_parameter (their call is
+ * pg_graph_sampler_set_envelope_parameter); playback status events of sampler voices and the sampler's own Stopped event;
+ * GeneratorPlaybackOptions::volume and ::panning; the reference's 54-entry message queue (the control ring and PG_ERR_QUEUE_FULL stand in for
+ * it). */
 typedef struct pg_granular_sampler_options {
   pg_granular_params params;
   const pg_modulation_params* modulation;   /* NULL: no matrix */
@@ -696,6 +728,22 @@ int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_
 int pg_graph_sampler_voice_grain_state(pg_graph* g, int sampler_id, int slot, pg_grain_state* out);
 int pg_graph_sampler_voice_modulation_state(pg_graph* g, int sampler_id, int slot, pg_modulation_state* out);
 int pg_graph_sampler_granular_params(pg_graph* g, int sampler_id, pg_granular_params* out);
+typedef struct pg_sampler_envelope_state {   /* AhdsrParameters after set_sample_rate(graph rate), as the device holds them */
+  float attack_rate, decay_rate, release_rate;   /* per frame; a zero time: FLT_MAX */
+  float sustain_level;
+  float hold_samples;                            /* hold_time.as_secs_f32() * sample_rate as f32 */
+  float attack_scaling, decay_scaling, release_scaling;
+  int32_t zero_times;                            /* bit 0: hold_time, bit 1: decay_time, bit 2: release_time is zero */
+} pg_sampler_envelope_state;
+int pg_sampler_envelope_param_count(void);
+int pg_sampler_envelope_param(int index, pg_param_desc* out);
+int pg_graph_sampler_set_envelope_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time);
+int pg_graph_sampler_envelope_params(pg_graph* g, int sampler_id, int slot, pg_sampler_envelope_state* out);
+int pg_graph_sampler_set_modulation(pg_graph* g, int sampler_id, int source, int target, float amount, int bipolar, uint64_t sample_time);
+int pg_graph_sampler_clear_modulation(pg_graph* g, int sampler_id, int source, int target, uint64_t sample_time);
+int pg_graph_sampler_set_lfo_rate(pg_graph* g, int sampler_id, int lfo, float rate_hz, uint64_t sample_time);
+int pg_graph_sampler_set_lfo_waveform(pg_graph* g, int sampler_id, int lfo, int waveform, uint64_t sample_time);
+int pg_graph_sampler_set_loop_range(pg_graph* g, int sampler_id, int has_loop_range, uint64_t loop_start, uint64_t loop_end, uint64_t sample_time);
 
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and

@@ -384,6 +384,25 @@ def sampler_state_dict(st):
                 finetune=int(st.finetune), volume=np.float32(st.volume), panning=np.float32(st.panning), slots=slots)
 
 
+SAMPLER_ENVELOPE_PARAM_IDS = ("AATK", "AHLD", "ADCY", "ASTN", "AREL")   # Sampler::envelope_parameters() order (reference src/generator/sampler.rs:173-181)
+ENV_HOLD_ZERO, ENV_DECAY_ZERO, ENV_RELEASE_ZERO = 1, 2, 4                # pg_sampler_envelope_state.zero_times
+
+
+class SamplerEnvelopeState(C.Structure):
+    """pg_sampler_envelope_state: a sampler's AhdsrParameters as the device holds them (rates per frame; a zero time is a rate of f32::MAX)."""
+    _fields_ = [("attack_rate", C.c_float), ("decay_rate", C.c_float), ("release_rate", C.c_float), ("sustain_level", C.c_float), ("hold_samples", C.c_float),
+                ("attack_scaling", C.c_float), ("decay_scaling", C.c_float), ("release_scaling", C.c_float), ("zero_times", C.c_int32)]
+
+
+def sampler_envelope_state_dict(st):
+    """A SamplerEnvelopeState as numpy scalars."""
+    import numpy as np
+
+    d = {k: np.float32(getattr(st, k)) for k, _ in SamplerEnvelopeState._fields_[:-1]}
+    d["zero_times"] = int(st.zero_times)
+    return d
+
+
 class GranularSamplerOptions(C.Structure):
     """pg_granular_sampler_options: the GranularParameters of Sampler::with_granular_playback, an optional matrix for every slot, an optional table
     of Xoshiro256++ states (voice_count x 3 x 4 words: slot k's pool, LFO 1, LFO 2)."""
@@ -568,6 +587,14 @@ GRAPH_ONLY_CALLS = (
     ("sampler_voice_grain_state", _int, [_int, _int, _P(GrainState)]),
     ("sampler_voice_modulation_state", _int, [_int, _int, _P(ModulationState)]),
     ("sampler_granular_params", _int, [_int, _P(GranularParams)]),
+    # what changes every voice of a pool while notes sound: the envelope's knobs, the matrix, the loop range
+    ("sampler_set_envelope_parameter", _int, [_int, _u32, _f32, _int, _u64]),
+    ("sampler_envelope_params", _int, [_int, _int, _P(SamplerEnvelopeState)]),
+    ("sampler_set_modulation", _int, [_int, _int, _int, _f32, _int, _u64]),
+    ("sampler_clear_modulation", _int, [_int, _int, _int, _u64]),
+    ("sampler_set_lfo_rate", _int, [_int, _int, _f32, _u64]),
+    ("sampler_set_lfo_waveform", _int, [_int, _int, _int, _u64]),
+    ("sampler_set_loop_range", _int, [_int, _int, _u64, _u64, _u64]),
 )
 
 # what only the sharded handle has (pg_sharded_create and _destroy: in load)
@@ -602,6 +629,8 @@ PLAIN_CALLS = (
     ("pg_sampler_options_check", _int, [_P(SamplerOptions)]),
     ("pg_sampler_param_count", _int, []),
     ("pg_sampler_param", _int, [_int, _P(ParamDesc)]),
+    ("pg_sampler_envelope_param_count", _int, []),
+    ("pg_sampler_envelope_param", _int, [_int, _P(ParamDesc)]),
     ("pg_granular_sampler_options_default", None, [_P(GranularSamplerOptions)]),
     ("pg_granular_sampler_options_check", _int, [_P(GranularSamplerOptions)]),
     ("pg_granular_sampler_rng_state", None, [_P(_u64), _u32, _u32, _P(_u64)]),

@@ -45,6 +45,12 @@ enum CtrlType : int32_t {
   CT_SAMPLER_STOP = 22,
   CT_SAMPLER_REMOVE = 23,         // RemoveSource: a message, not an event
   CT_SAMPLER_GRAIN_PARAM = 24,    // a granular-mode sampler: param = index in Sampler::granular_parameters() order, value = resolved raw value
+  // what changes every voice of the pool while notes sound (Sampler::process_playback_messages, sampler.rs:656-731), events
+  CT_SAMPLER_ENV_PARAM = 25,      // param = index in Sampler::envelope_parameters() order, value = resolved raw value (seconds / sustain level)
+  CT_SAMPLER_MOD_ROUTE = 26,      // a granular-mode sampler with a matrix; as CT_VOICE_MOD_ROUTE
+  CT_SAMPLER_LFO_RATE = 27,       // ... as CT_VOICE_LFO_RATE
+  CT_SAMPLER_LFO_WAVEFORM = 28,   // ... as CT_VOICE_LFO_WAVEFORM
+  CT_SAMPLER_GRAIN_LOOP = 29,     // a granular-mode sampler; as CT_VOICE_GRAIN_LOOP
 };
 
 struct CtrlMsg {

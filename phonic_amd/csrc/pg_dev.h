@@ -558,7 +558,16 @@ enum PgCmdType {
   CMD_SAMPLER_STOP = 24,          //                                                                                            (Sampler::stop)
   // a granular-mode sampler only (pg_graph_add_granular_sampler; pg_gsampler_kernel applies it, the unit kernels ignore it but end a segment at it):
   CMD_SAMPLER_GRAIN_PARAM = 25,   // param = PG_GP_*, value = the resolved raw value (an enum's index as a float)               (Sampler::set_granular_parameter)
+  // what changes every voice of the pool while notes sound. The envelope command is a file sampler's (pg_unit_kernel) and a granular one's
+  // (pg_gsampler_kernel); the other four are a granular sampler's only and carry what the lone voices' commands of the same name carry:
+  CMD_SAMPLER_ENV_PARAM = 26,     // param = PG_SE_*, value = the field that changes (a rate, hold_samples, the sustain level), value64 = the new zero_times (AhdsrParameters::set_*)
+  CMD_SAMPLER_MOD_ROUTE = 27,     // as CMD_VOICE_MOD_ROUTE, for every slot                                                     (ModulationMatrixSlot::update_target)
+  CMD_SAMPLER_LFO_RATE = 28,      // as CMD_VOICE_LFO_RATE, for every slot                                                      (Lfo::set_rate)
+  CMD_SAMPLER_LFO_WAVEFORM = 29,  // as CMD_VOICE_LFO_WAVEFORM, for every slot                                                  (Lfo::set_waveform)
+  CMD_SAMPLER_GRAIN_LOOP = 30,    // as CMD_VOICE_GRAIN_LOOP, for every slot                                                    (GrainPool::set_loop_range)
 };
+// CMD_SAMPLER_ENV_PARAM's index: Sampler::envelope_parameters() (sampler.rs:173-181)
+enum { PG_SE_ATTACK = 0, PG_SE_HOLD, PG_SE_DECAY, PG_SE_SUSTAIN, PG_SE_RELEASE, PG_SE_COUNT };
 enum { PG_SP_TRANSPOSE = 0, PG_SP_FINETUNE, PG_SP_VOLUME, PG_SP_PANNING, PG_SP_COUNT };   // CMD_SAMPLER_PARAM's index: Sampler::base_parameters() (sampler.rs:120-127)
 // CMD_VOICE_GRAIN_PARAM's index: Sampler::granular_parameters() (sampler.rs:283-296)
 enum { PG_GP_OVERLAP_MODE = 0, PG_GP_WINDOW, PG_GP_SIZE, PG_GP_DENSITY, PG_GP_VARIATION, PG_GP_SPRAY, PG_GP_PAN_SPREAD, PG_GP_DIRECTION, PG_GP_POSITION, PG_GP_STEP, PG_GP_COUNT };

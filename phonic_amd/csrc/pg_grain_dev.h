@@ -158,6 +158,26 @@ DEVO void grain_set_parameter(PgGrainParams& p, uint32_t index, float value) {
     default: break;
   }
 }
+// What a matrix or loop-range command does, for a lone voice (CMD_VOICE_*, pg_grain_kernel) and for every slot of a granular sampler
+// (CMD_SAMPLER_*, pg_gsampler_kernel) alike: the two kinds carry the same words.
+// A route command's source and target, -1 when either is out of range (the host checks them: nothing out of range indexes the table)
+DEVO int grain_route_source(const PgCmd& c) { const uint32_t s = (uint32_t)(c.value64 & 0xff); return s < PG_GMOD_SOURCES ? (int)s : -1; }
+DEVO int grain_route_target(const PgCmd& c) { const uint32_t t = (uint32_t)((c.value64 >> 8) & 0xff); return t < PG_GMOD_TARGETS ? (int)t : -1; }
+// ModulationMatrixSlot::update_target (matrix.rs:60-83): the host has turned an amount below the threshold into 0.0, which removes the route
+DEVO void grain_route_apply(const PgCmd& c, float (*amount)[PG_GMOD_TARGETS], int32_t (*bipolar)[PG_GMOD_TARGETS]) {
+  const int sr = grain_route_source(c), tg = grain_route_target(c);
+  if (sr >= 0 && tg >= 0) { amount[sr][tg] = c.value; bipolar[sr][tg] = c.value != 0.0f && ((c.value64 >> 16) & 1) ? 1 : 0; }
+}
+// Lfo::set_rate / set_waveform (lfo.rs:102-119) of LFO `l`, if the command is that LFO's: nothing else of the LFO changes
+DEVO void grain_lfo_apply(const PgCmd& c, bool is_rate, int l, PgModLfo& m) {
+  if ((int)(c.value64 & 0xff) != l) return;
+  if (is_rate) m.phase_inc = c.value;
+  else { const uint32_t w = (uint32_t)((c.value64 >> 8) & 0xff); if (w < 7) m.waveform = (int32_t)w; }
+}
+// GrainPool::set_loop_range (granular.rs:516-518): playing_loop_range, the playhead and living grains keep what they have
+DEVO void grain_loop_apply(const PgCmd& c, PgGrainParams& p) {
+  p.has_loop = (int32_t)(c.value64 & 1); p.loop_start = c.value; p.loop_end = __uint_as_float((uint32_t)(c.value64 >> 32));
+}
 // One slot's contribution to a target's sum (ModulationMatrix::output, matrix.rs:201-231): LFOs are bipolar sources, velocity and keytracking
 // unipolar ones.
 DEV float mod_bipolar_source(float v, int bipolar) { return bipolar ? v : (v + 1.0f) / 2.0f; }

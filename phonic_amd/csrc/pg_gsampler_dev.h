@@ -5,7 +5,8 @@
 //              frames, then the voice's end: the pool ran dry inside the span or the envelope ended it Idle -> the slot is free and its pool reset;
 //              a stopping sampler without an active slot is stopped; the staged frames of a slot that was free over the span become zero;
 //   gs_open    process_playback_messages in front of the span that begins: note-on with next_free_voice_index, note-off, the per-note setters,
-//              the base parameters, the granular parameters, stop.
+//              the base parameters, the granular parameters, stop — and what changes every voice while notes sound: the envelope's parameters,
+//              the matrix's routes and LFOs, the loop range.
 // One workgroup per sampler. Decisions take one lane per slot (wave 0); a record is changed by one lane (or one lane per slot / per grain) and
 // read again only behind a barrier.
 #pragma once
@@ -28,7 +29,7 @@ struct GsShared {
   int32_t result;
 };
 
-DEVO bool gs_cmd_is_message(int type) { return (type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_STOP) || type == CMD_SAMPLER_GRAIN_PARAM; }
+DEVO bool gs_cmd_is_message(int type) { return (type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_STOP) || (type >= CMD_SAMPLER_GRAIN_PARAM && type <= CMD_SAMPLER_GRAIN_LOOP); }
 DEVO PgGrainVoice* gs_grain(const PgGSamplerLaunch& L, const PgGSampler& r, int slot) { return L.grains + r.grain0 + slot; }
 // The record as the host describes it lies inside the tables: anything else is left alone
 DEVO bool gs_pool_ok(const PgGSamplerLaunch& L, const PgGSampler& r) {
@@ -143,6 +144,20 @@ DEVO void gs_open(const PgGSamplerLaunch& L, PgGSampler& r, GsShared& S) {
     }
     if (cmd.type == CMD_SAMPLER_GRAIN_PARAM) {   // Sampler::set_granular_parameter (:299-360): the sampler's ONE parameter set — here every slot's copy of it
       if (tid < n) { PgGrainParams p = gs_grain(L, r, tid)->params; grain_set_parameter(p, (uint32_t)cmd.param, cmd.value); gs_grain(L, r, tid)->params = p; }
+    } else if (cmd.type == CMD_SAMPLER_MOD_ROUTE || cmd.type == CMD_SAMPLER_LFO_RATE || cmd.type == CMD_SAMPLER_LFO_WAVEFORM) {
+      // SetModulation / ClearModulation, ML1R / ML2R / ML1W / ML2W (:704-720, :1148-1186, :1210-1244): the matrix of EVERY voice, playing or free. The LFOs
+      // draw nothing and keep their phases; a later note's reset keeps what is written here.
+      if (tid < n) {
+        PgGrainMod& m = gs_grain(L, r, tid)->mod;
+        if (m.on) {
+          if (cmd.type == CMD_SAMPLER_MOD_ROUTE) grain_route_apply(cmd, m.amount, m.bipolar);
+          else for (int l = 0; l < 2; ++l) grain_lfo_apply(cmd, cmd.type == CMD_SAMPLER_LFO_RATE, l, m.lfo[l]);
+        }
+      }
+    } else if (cmd.type == CMD_SAMPLER_GRAIN_LOOP) {   // SamplerMessage::SetLoopRange (:1246-1271, voice.rs:312-339): every voice's pool
+      if (tid < n) { PgGrainParams p = gs_grain(L, r, tid)->params; grain_loop_apply(cmd, p); gs_grain(L, r, tid)->params = p; }
+    } else if (cmd.type == CMD_SAMPLER_ENV_PARAM) {   // set_envelope_parameter (:184-217, :1122-1131): the pool's one AhdsrParameters; gs_close reads it once per span
+      if (tid == 0 && r.note.has_envelope) { PgEnvParams p = r.env_params; ahdsr_set_param(p, cmd); r.env_params = p; }
     } else if (tid == 0) {
       if (cmd.type == CMD_SAMPLER_ALL_NOTES_OFF) {
         for (int i = 0; i < n; ++i) gs_voice_stop(L, r, i, now);

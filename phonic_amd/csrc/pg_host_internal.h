@@ -265,6 +265,8 @@ struct HostVoice {
   uint64_t file_samples = 0;                   // ... and its buffer().len() (voice.rs:463)
   int sampler = -1;                // a pool voice of pg_graph::samplers[sampler] (pg_graph_add_sampler): no public id, its unit stays on the exact kernel
 };
+// What a sampler id stands for, as the message calls of any thread see it (pg_graph::sampler_alive_tab): one of the first two, plus what it was created with
+enum : int8_t { SAMPLER_TAB_FILE = 1, SAMPLER_TAB_GRANULAR = 2, SAMPLER_TAB_ENVELOPE = 4, SAMPLER_TAB_MATRIX = 8 };
 // A sampler (pg_graph_add_sampler): the pool's place in the graph; the note layer's state is the device's (PgSamplerRec `rec` of pg_graph::d_samp)
 struct HostSampler {
   int mixer = -1, rec = -1;
@@ -274,6 +276,7 @@ struct HostSampler {
   uint64_t start_time = 0;         // the mixer does not call the sampler before this frame: messages due earlier are held until it (sampler_drain_message)
   bool alive = true;               // until pg_graph_remove_sampler / the removal of its mixer / `stopped` has been seen
   int transpose = 0, finetune = 0; // the base pitch as of the last event STAGED (events are staged in time order): what the next pitch factor is made of
+  PgEnvParams env = {};            // has_envelope: the pool's AhdsrParameters as of the last event STAGED — the sustain level an ADCY divides by, the zero times
   // a granular-mode sampler (pg_graph_add_granular_sampler): its note layer is PgGSampler `rec` of pg_graph::d_gsamp (PgSamplerRec `rec` is inert),
   // slot k renders through PgGrainVoice record grain0 + k; with_mod: every slot has a modulation matrix
   bool granular = false, with_mod = false;
@@ -503,7 +506,8 @@ struct pg_graph {
   // reached by the exact kernel through the envelope table's header; speed_from_note's table; one `stopped` word per record in mapped host
   // memory (polled at the top of a write)
   std::vector<HostSampler> samplers;     // by sampler id (ids are never reused)
-  pgc::ChunkTable<int8_t> sampler_alive_tab;   // sampler id -> 1 while it takes messages (readable from any thread)
+  pgc::ChunkTable<int8_t> sampler_alive_tab;   // sampler id -> SAMPLER_TAB_* while it takes messages, 0 from then on (readable from any thread)
+  pgc::ChunkTable<uint64_t> sampler_frames_tab; // sampler id -> frames of its sample buffer: what a loop range is checked against (appended first)
   PgSamplerTab* d_samp = nullptr;
   size_t samp_cap = 0;                   // records d_samp has room for
   double* d_speed_tab = nullptr;
@@ -588,7 +592,7 @@ void graph_sampler_release(pg_graph* g);
 void graph_sampler_poll(pg_graph* g);                  // top of a write: voices whose `ended` word is set leave the exact kernel / pg_grain_kernel; stopped samplers leave their mixer
 void push_event(pg_graph* g, int mixer, uint64_t sample_time, const PgCmd& cmd, uint64_t stamp = UINT64_MAX);   // (pg_host.hip) one event into a mixer's sorted list; stamp: Event::stamp, default = sample_time
 bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m);   // drain_control_messages: a sampler's message -> an event of its mixer (false: not a sampler message)
-void sampler_stage_command(pg_graph* g, PgCmd& c);     // an event leaves its mixer's list for a launch (in time order): a base-pitch command gets its pitch factor
+void sampler_stage_command(pg_graph* g, PgCmd& c);     // an event leaves its mixer's list for a launch (in time order): a base-pitch command gets its pitch factor, an envelope command the field its setter writes
 void samplers_of_removed_mixers(pg_graph* g);          // pg_graph_remove_mixer: their ids are dead from here on
 int graph_gran_upload_live(pg_graph* g, hipStream_t stream);
 int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream);

@@ -31,9 +31,6 @@ __device__ __forceinline__ bool grain_cmd_matches(const PgCmd& c, int voice) {
                                c.type == CMD_VOICE_MOD_ROUTE || c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM || c.type == CMD_VOICE_GRAIN_PARAM ||
                                c.type == CMD_VOICE_GRAIN_LOOP);
 }
-// A route command's source and target, -1 when either is out of range (the host checks them: nothing out of range indexes the table)
-__device__ __forceinline__ int grain_route_source(const PgCmd& c) { const uint32_t s = (uint32_t)(c.value64 & 0xff); return s < PG_GMOD_SOURCES ? (int)s : -1; }
-__device__ __forceinline__ int grain_route_target(const PgCmd& c) { const uint32_t t = (uint32_t)((c.value64 >> 8) & 0xff); return t < PG_GMOD_TARGETS ? (int)t : -1; }
 
 __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
   __shared__ float s_lut[PG_GRAIN_LUT_N];
@@ -145,8 +142,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
             const PgCmd c = L.cmds[ci];
             if (c.frame > lf) break;
             ++lfo_cursor;
-            if (c.type == CMD_VOICE_LFO_RATE && (int)(c.value64 & 0xff) == l) m.phase_inc = c.value;
-            else if (c.type == CMD_VOICE_LFO_WAVEFORM && (int)(c.value64 & 0xff) == l) { const uint32_t w = (uint32_t)((c.value64 >> 8) & 0xff); if (w < 7) m.waveform = (int32_t)w; }
+            if (c.type == CMD_VOICE_LFO_RATE || c.type == CMD_VOICE_LFO_WAVEFORM) grain_lfo_apply(c, c.type == CMD_VOICE_LFO_RATE, l, m);
           }
           if (tile_t + (uint64_t)f >= start_time) s_lfo[l][f] = mod_lfo_run(m);
         }
@@ -160,11 +156,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
           const int ci = peek_cmd(route_cursor);
           if (ci < 0 || L.cmds[ci].frame > base + (uint32_t)seg0) break;
           ++route_cursor;
-          if (tid == 0 && L.cmds[ci].type == CMD_VOICE_MOD_ROUTE) {
-            const PgCmd c = L.cmds[ci];
-            const int sr = grain_route_source(c), tg = grain_route_target(c);
-            if (sr >= 0 && tg >= 0) { s_ramt[sr][tg] = c.value; s_rbip[sr][tg] = c.value != 0.0f && ((c.value64 >> 16) & 1) ? 1 : 0; }
-          }
+          if (tid == 0 && L.cmds[ci].type == CMD_VOICE_MOD_ROUTE) grain_route_apply(L.cmds[ci], s_ramt, s_rbip);
         }
         int seg1 = tn;
         for (int cur = route_cursor;;) {  // the next route command inside the tile ends the segment
@@ -213,9 +205,7 @@ __global__ void __launch_bounds__(256) pg_grain_kernel(PgGrainLaunch L) {
             grain_set_parameter(S.p, (uint32_t)c.value64, c.value);
             // in front of the note: GrainPool::start reads the position at note-on (:487)
             if ((uint32_t)c.value64 == PG_GP_POSITION && L.t0 + (uint64_t)c.frame < start_time) S.pool.playhead = c.value;
-          } else if (c.type == CMD_VOICE_GRAIN_LOOP) {  // GrainPool::set_loop_range (:516-518): playing_loop_range, the playhead and living grains keep what they have
-            S.p.has_loop = (int32_t)(c.value64 & 1); S.p.loop_start = c.value; S.p.loop_end = __uint_as_float((uint32_t)(c.value64 >> 32));
-          }
+          } else if (c.type == CMD_VOICE_GRAIN_LOOP) grain_loop_apply(c, S.p);
           // (the modulation matrix's commands were taken in phase 0)
         }
         if (t < start_time) { s_act[f].slot = -1; continue; }

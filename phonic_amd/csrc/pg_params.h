@@ -136,6 +136,19 @@ static const ParamSpec SAMPLER_PARAMS[PG_SP_COUNT] = {
     {FCC('S', 'V', 'O', 'L'), PG_PARAM_FLOAT, 0.000001f, 15.848932f, 1.0f, PG_SCALE_DECIBEL, -60.0f, 24.0f, 0, "Volume", S_NONE, 0},
     {FCC('S', 'P', 'A', 'N'), PG_PARAM_FLOAT, -1.0f, 1.0f, 0.0f, 0, 0, 0, 0, "Panning", S_NONE, 0},
 };
+// The Sampler's envelope parameters in Sampler::envelope_parameters() order (src/generator/sampler.rs:130-181): the index is CMD_SAMPLER_ENV_PARAM's
+// (PG_SE_*). A table of its own: pg_graph_sampler_set_parameter does not take these ids.
+static const ParamSpec SAMPLER_ENV_PARAMS[PG_SE_COUNT] = {
+    {FCC('A', 'A', 'T', 'K'), PG_PARAM_FLOAT, 0.0f, 10.0f, 0.001f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Attack", S_NONE, 0},
+    {FCC('A', 'H', 'L', 'D'), PG_PARAM_FLOAT, 0.0f, 10.0f, 0.75f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Hold", S_NONE, 0},
+    {FCC('A', 'D', 'C', 'Y'), PG_PARAM_FLOAT, 0.0f, 10.0f, 0.5f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Decay", S_NONE, 0},
+    {FCC('A', 'S', 'T', 'N'), PG_PARAM_FLOAT, 0.0f, 1.0f, 0.75f, 0, 0, 0, 0, "Sustain", S_NONE, 0},
+    {FCC('A', 'R', 'E', 'L'), PG_PARAM_FLOAT, 0.0f, 10.0f, 1.0f, PG_SCALE_EXPONENTIAL, 2.0f, 0, 0, "Release", S_NONE, 0},
+};
+inline int find_sampler_env_param(uint32_t fourcc) {
+  for (int i = 0; i < PG_SE_COUNT; ++i) if (SAMPLER_ENV_PARAMS[i].fourcc == fourcc) return i;
+  return -1;
+}
 inline int find_sampler_param(uint32_t fourcc) {
   for (int i = 0; i < PG_SP_COUNT; ++i) if (SAMPLER_PARAMS[i].fourcc == fourcc) return i;
   return -1;

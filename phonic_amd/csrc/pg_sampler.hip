@@ -615,7 +615,7 @@ static HostSampler* sampler_find(pg_graph* g, int sampler_id) {   // owner threa
   if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || !g->samplers[sampler_id].alive) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return nullptr; }
   return &g->samplers[sampler_id];
 }
-static bool cmd_is_sampler_event(int cmd_type) { return (cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP) || cmd_type == CMD_SAMPLER_GRAIN_PARAM; }
+static bool cmd_is_sampler_event(int cmd_type) { return (cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP) || (cmd_type >= CMD_SAMPLER_GRAIN_PARAM && cmd_type <= CMD_SAMPLER_GRAIN_LOOP); }
 // The pool leaves its mixer (RemoveSource, a mixer that drops an exhausted generator: mixed.rs:612-616): its voices are retired like removed
 // sources — their buffer references return when their memory is released — and what is still queued for it finds no source when it comes due
 static void sampler_retire(pg_graph* g, int sampler_id) {
@@ -689,9 +689,15 @@ static const SamplerEvent SAMPLER_EVENTS[] = {
   {pgc::CT_SAMPLER_PARAM, CMD_SAMPLER_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},   // (the pitch factor: sampler_stage_command)
   {pgc::CT_SAMPLER_STOP, CMD_SAMPLER_STOP, [](const pgc::CtrlMsg&, PgCmd&) {}},
   {pgc::CT_SAMPLER_GRAIN_PARAM, CMD_SAMPLER_GRAIN_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},
+  {pgc::CT_SAMPLER_ENV_PARAM, CMD_SAMPLER_ENV_PARAM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; }},   // (the field it changes: sampler_stage_command)
+  // the words of the lone voices' commands of the same name (pg_host.hip: VOICE_EVENTS); the call has turned an LFO's rate into its phase increment
+  {pgc::CT_SAMPLER_MOD_ROUTE, CMD_SAMPLER_MOD_ROUTE, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_SAMPLER_LFO_RATE, CMD_SAMPLER_LFO_RATE, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_SAMPLER_LFO_WAVEFORM, CMD_SAMPLER_LFO_WAVEFORM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value64 = (uint64_t)(uint32_t)m.param; }},
+  {pgc::CT_SAMPLER_GRAIN_LOOP, CMD_SAMPLER_GRAIN_LOOP, [](const pgc::CtrlMsg& m, PgCmd& c) { uint32_t end; memcpy(&end, &m.value2, 4); c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)end << 32); }},
 };
 bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
-  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_GRAIN_PARAM) return false;
+  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_GRAIN_LOOP) return false;
   if (m.id < 0 || m.id >= (int)g->samplers.size() || !g->samplers[m.id].alive) return true;   // gone in the meantime: dropped
   if (m.type == pgc::CT_SAMPLER_REMOVE) { sampler_retire(g, m.id); return true; }
   const HostSampler& hs = g->samplers[m.id];
@@ -718,7 +724,37 @@ bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
 // The pitch factor of a base-pitch command is 2^(transpose / 12 + finetune / 1200) of the pair that holds once the command is applied
 // (voice.rs:144-148), with this host's libm. Messages may be sent out of time order, so the pair is tracked here, where a mixer's events leave its
 // sorted list one by one.
+//
+// An envelope command is resolved here for the same reason: AhdsrParameters' setters are not independent (ahdsr.rs:143-249). set_sustain_level
+// stores the level and leaves decay_rate alone; set_decay_time divides (1 - sustain_level) as it holds THEN; a zero time is a rate of f32::MAX.
+// The command gets the one field its setter writes and the zero times that hold behind it.
+// Duration::from_secs_f32(seconds).as_secs_f32() (sampler.rs:191-208): nanoseconds rounded to nearest, ties to even, then
+// `secs as f32 + nanos as f32 / 1e9f32`. The rounding rule is how the standard library's documentation describes try_from_secs_f32; it is
+// UNVERIFIED against the library's source, which this project does not hold. f32 x 1e9 is exact in f64 (24 + 21 bits).
+static float duration_round_trip(float seconds, bool& is_zero) {
+  const uint64_t total = (uint64_t)std::nearbyint((double)(seconds > 0.0f ? seconds : 0.0f) * 1e9);
+  is_zero = total == 0;
+  return (float)(total / 1000000000ull) + (float)(uint32_t)(total % 1000000000ull) / 1e9f;
+}
+static void sampler_stage_envelope(pg_graph* g, PgCmd& c) {
+  if (c.target < 0 || c.target >= (int)g->samplers.size()) return;
+  PgEnvParams& p = g->samplers[c.target].env;
+  const float sr = (float)g->sample_rate;
+  if (c.param == PG_SE_SUSTAIN) p.sustain_level = c.value;
+  else {
+    bool zero = false;
+    const float secs = duration_round_trip(c.value, zero);
+    int bit = 0;
+    if (c.param == PG_SE_ATTACK) c.value = p.attack_rate = secs == 0.0f ? FLT_MAX : 1.0f / (secs * sr);
+    else if (c.param == PG_SE_HOLD) { c.value = p.hold_samples = secs * sr; bit = PG_AHDSR_HOLD_ZERO; }
+    else if (c.param == PG_SE_DECAY) { c.value = p.decay_rate = zero ? FLT_MAX : (1.0f - p.sustain_level) / (secs * sr); bit = PG_AHDSR_DECAY_ZERO; }
+    else if (c.param == PG_SE_RELEASE) { c.value = p.release_rate = secs == 0.0f ? FLT_MAX : 1.0f / (secs * sr); bit = PG_AHDSR_RELEASE_ZERO; }
+    p.zero_times = (p.zero_times & ~bit) | (zero ? bit : 0);
+  }
+  c.value64 = (uint64_t)(uint32_t)p.zero_times;
+}
 void sampler_stage_command(pg_graph* g, PgCmd& c) {
+  if (c.type == CMD_SAMPLER_ENV_PARAM) { sampler_stage_envelope(g, c); return; }
   if (c.type != CMD_SAMPLER_PARAM || (c.param != PG_SP_TRANSPOSE && c.param != PG_SP_FINETUNE)) return;
   for (HostSampler& hs : g->samplers) if (hs.rec == c.target) {
     if (c.param == PG_SP_TRANSPOSE) hs.transpose = (int)c.value; else hs.finetune = (int)c.value;
@@ -831,8 +867,9 @@ int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_samp
     if (id < 0) return id;
     if (k == 0) hs.voice_id_slot0 = id;
   }
+  if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
   g->samplers.push_back(hs);
-  if (!g->sampler_alive_tab.append(1)) return -set_error(PG_ERR_STATE, "too many samplers");
+  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) || !g->sampler_alive_tab.append((int8_t)(SAMPLER_TAB_FILE | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
   return sampler_id;
 }
 int pg_graph_remove_sampler(pg_graph* g, int sampler_id) {
@@ -1151,10 +1188,12 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
     if (id < 0) { release(); return id; }
     if (k == 0) hs.voice_id_slot0 = id;
   }
+  if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
   g->samplers.push_back(hs);
   g->n_gsamplers += 1;
   g->gsamp_dirty = true;
-  if (!g->sampler_alive_tab.append(2)) return -set_error(PG_ERR_STATE, "too many samplers");   // (2: alive and granular, readable from any thread)
+  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) ||
+      !g->sampler_alive_tab.append((int8_t)(SAMPLER_TAB_GRANULAR | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0) | (gopt->modulation ? SAMPLER_TAB_MATRIX : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
   return sampler_id;
 }
 int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
@@ -1163,13 +1202,109 @@ int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_
   if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
   if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  if (g->sampler_alive_tab.get((size_t)sampler_id) != 2) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no granular parameters", sampler_id);
+  if (!(g->sampler_alive_tab.get((size_t)sampler_id) & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no granular parameters", sampler_id);
   float raw;
   if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) return PG_OK;   // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
   pgc::CtrlMsg m;
   memset(&m, 0, sizeof m);
   m.type = pgc::CT_SAMPLER_GRAIN_PARAM; m.id = sampler_id; m.param = pi; m.value = raw; m.sample_time = sample_time;
   if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
+  return PG_OK;
+}
+// ---- what changes every voice of the pool while notes sound: the envelope's knobs, the matrix, the loop range (Sampler::process_playback_messages,
+// sampler.rs:656-731: SetParameter(AMP_* | ML1R | ML2R | ML1W | ML2W), SetModulation, ClearModulation, SamplerMessage::SetLoopRange). Any thread:
+// what a call must know of the sampler stands in sampler_alive_tab / sampler_frames_tab. ----
+// The sampler's SAMPLER_TAB_* word while it takes messages; 0: PG_ERR_PARAMETER (null handle) or PG_ERR_NOT_FOUND is set
+static int sampler_tab_word(pg_graph* g, int sampler_id) {
+  if (!g) { set_error(PG_ERR_PARAMETER, "graph handle is null"); return 0; }
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return 0; }
+  return g->sampler_alive_tab.get((size_t)sampler_id);
+}
+static int sampler_push(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int param, float value, float value2 = 0.0f) {
+  pgc::CtrlMsg m;
+  memset(&m, 0, sizeof m);
+  m.type = type; m.id = sampler_id; m.param = param; m.value = value; m.value2 = value2; m.sample_time = sample_time;
+  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
+  return PG_OK;
+}
+// ... of a granular sampler with a matrix (the reference: "only available when granular playback is enabled"; a pool without a matrix is this implementation's)
+static int sampler_matrix_message(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int param, float value) {
+  const int w = sampler_tab_word(g, sampler_id);
+  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!(w & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: modulation is only available when granular playback is enabled", sampler_id);
+  if (!(w & SAMPLER_TAB_MATRIX)) return set_error(PG_ERR_STATE, "Sampler with id %d has no modulation matrix", sampler_id);
+  return sampler_push(g, sampler_id, type, sample_time, param, value);
+}
+int pg_sampler_envelope_param_count(void) { return PG_SE_COUNT; }
+int pg_sampler_envelope_param(int index, pg_param_desc* out) {   // Sampler::envelope_parameters() (sampler.rs:173-181)
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (index < 0 || index >= PG_SE_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
+  const ParamSpec& p = SAMPLER_ENV_PARAMS[index];
+  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
+  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  return PG_OK;
+}
+int pg_graph_sampler_set_envelope_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
+  const int pi = find_sampler_env_param(fourcc);
+  if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown envelope parameter 0x%08x", fourcc);
+  if (value != value) return set_error(PG_ERR_PARAMETER, "Envelope parameter '%s' is not a number", SAMPLER_ENV_PARAMS[pi].name);
+  float raw = 0.0f;
+  (void)resolve_update(SAMPLER_ENV_PARAMS[pi], value, is_normalized != 0, raw);   // parameter_update_value (:862-883): clamped, or clamped to 0..=1 and denormalized
+  const int w = sampler_tab_word(g, sampler_id);
+  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!(w & SAMPLER_TAB_ENVELOPE)) return set_error(PG_ERR_PARAMETER, "Invalid or unknown sampler parameter 0x%08x: sampler %d has no envelope", fourcc, sampler_id);   // (:1128-1131, :1189)
+  return sampler_push(g, sampler_id, pgc::CT_SAMPLER_ENV_PARAM, sample_time, pi, raw);
+}
+int pg_graph_sampler_set_modulation(pg_graph* g, int sampler_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
+  { const int rc = mod_check_route(source, target, amount); if (rc) return rc; }
+  const bool keep = fabsf(amount) >= 0.001f;   // update_target's threshold (matrix.rs:61), as pg_graph_set_voice_modulation has it
+  return sampler_matrix_message(g, sampler_id, pgc::CT_SAMPLER_MOD_ROUTE, sample_time, source | (target << 8) | ((keep && bipolar) ? 1 << 16 : 0), keep ? amount : 0.0f);
+}
+int pg_graph_sampler_clear_modulation(pg_graph* g, int sampler_id, int source, int target, uint64_t sample_time) {
+  return pg_graph_sampler_set_modulation(g, sampler_id, source, target, 0.0f, 0, sample_time);
+}
+int pg_graph_sampler_set_lfo_rate(pg_graph* g, int sampler_id, int lfo, float rate_hz, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (rate_hz != rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", lfo + 1);
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  const float phase_inc = (float)((double)mod_clamp_rate(rate_hz) / (double)g->sample_rate);   // Lfo::set_rate (lfo.rs:102-104)
+  return sampler_matrix_message(g, sampler_id, pgc::CT_SAMPLER_LFO_RATE, sample_time, lfo, phase_inc);
+}
+int pg_graph_sampler_set_lfo_waveform(pg_graph* g, int sampler_id, int lfo, int waveform, uint64_t sample_time) {
+  if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
+  if (waveform < 0 || waveform > 6) return set_error(PG_ERR_PARAMETER, "Invalid LFO %d waveform: %d", lfo + 1, waveform);
+  return sampler_matrix_message(g, sampler_id, pgc::CT_SAMPLER_LFO_WAVEFORM, sample_time, lfo | (waveform << 8), 0.0f);
+}
+int pg_graph_sampler_set_loop_range(pg_graph* g, int sampler_id, int has_loop_range, uint64_t loop_start, uint64_t loop_end, uint64_t sample_time) {
+  if (has_loop_range && loop_start >= loop_end) return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu", (unsigned long long)loop_start, (unsigned long long)loop_end);
+  const int w = sampler_tab_word(g, sampler_id);
+  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!(w & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: its loop range is set when it is created", sampler_id);
+  const uint64_t frames = g->sampler_frames_tab.get((size_t)sampler_id);
+  if (has_loop_range && (loop_start >= frames || loop_end > frames))   // (:1251-1269)
+    return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%llu", (unsigned long long)loop_start, (unsigned long long)loop_end, (unsigned long long)frames);
+  // SamplerVoice::set_loop_range (voice.rs:329-338): source frames over the FILE's frame count, as f32 — as at creation. None is no loop at all.
+  const float total = (float)frames;
+  return sampler_push(g, sampler_id, pgc::CT_SAMPLER_GRAIN_LOOP, sample_time, has_loop_range ? 1 : 0, has_loop_range ? (float)loop_start / total : 0.0f, has_loop_range ? (float)loop_end / total : 0.0f);
+}
+int pg_graph_sampler_envelope_params(pg_graph* g, int sampler_id, int slot, pg_sampler_envelope_state* out) {
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
+    return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  const HostSampler& hs = g->samplers[sampler_id];
+  if (slot < 0 || slot >= hs.n_voices) return set_error(PG_ERR_PARAMETER, "Invalid slot: %d. The sampler has %d", slot, hs.n_voices);
+  if (!hs.has_envelope) return set_error(PG_ERR_STATE, "Sampler with id %d has no envelope", sampler_id);
+  PgEnvParams p;
+  (void)hipSetDevice(g->device);
+  if (hs.granular) { const int rc = graph_read_back(g, &p, (const char*)(g->d_gsamp + hs.rec) + offsetof(PgGSampler, env_params), sizeof p); if (rc) return rc; }
+  else {   // slot 0's voice has the pool's first record, the slots follow it (pg_graph_add_sampler)
+    const int voice0 = g->voices[hs.voice_id_slot0].dev_index;
+    const int rc = graph_read_back(g, &p, (const char*)(g->d_env + voice0 + slot) + offsetof(PgEnv, params), sizeof p);
+    if (rc) return rc;
+  }
+  out->attack_rate = p.attack_rate; out->decay_rate = p.decay_rate; out->release_rate = p.release_rate; out->sustain_level = p.sustain_level; out->hold_samples = p.hold_samples;
+  out->attack_scaling = p.attack_scaling; out->decay_scaling = p.decay_scaling; out->release_scaling = p.release_scaling; out->zero_times = p.zero_times;
   return PG_OK;
 }
 // The granular sampler behind `sampler_id` for a read-back (as pg_graph_sampler_state finds it) and the grain record of its slot; < 0: -PG_ERR_*

@@ -1,5 +1,5 @@
 // The Sampler's note layer on the device (src/generator/sampler.rs:656-860, src/generator/sampler/voice.rs:122-310): note-on with voice
-// allocation and stealing, note-off, the per-note setters, the base parameters and stop, applied by the exact kernel (pg_unit_kernel) in its
+// allocation and stealing, note-off, the per-note setters, the base and the envelope parameters and stop, applied by the exact kernel (pg_unit_kernel) in its
 // command loop, in front of the frame a message lands on. The workgroup that renders the sampler's sub-mixer renders all of its pool voices, so
 // in front of that frame the records it reads here hold exactly what the reference's Sampler sees at the top of the `write` the owning mixer
 // cut at the message's sample time: which slots are active, which envelopes are in Release, which faders run.
@@ -34,6 +34,19 @@ DEVO void ahdsr_note_on(PgEnvState& st, const PgEnvParams& p, float volume) {
     if (!(p.zero_times & PG_AHDSR_HOLD_ZERO)) { st.stage = PG_AHDSR_HOLD; st.hold_samples_remaining = p.hold_samples; }
     else st.stage = PG_AHDSR_DECAY;
   } else { st.output = 0.0f; st.stage = PG_AHDSR_ATTACK; }
+}
+
+// AhdsrParameters::set_attack_time / set_hold_time / set_decay_time / set_sustain_level / set_release_time (ahdsr.rs:143-249) as the host has
+// resolved them in time order (pg_sampler.hip: sampler_stage_command): the one field the setter writes, and which of the times are zero now.
+// Nothing of a running envelope's state changes: a Hold in progress keeps its hold_samples_remaining.
+DEVO void ahdsr_set_param(PgEnvParams& p, const PgCmd& cmd) {
+  if (cmd.param == PG_SE_ATTACK) p.attack_rate = cmd.value;
+  else if (cmd.param == PG_SE_HOLD) p.hold_samples = cmd.value;
+  else if (cmd.param == PG_SE_DECAY) p.decay_rate = cmd.value;
+  else if (cmd.param == PG_SE_SUSTAIN) p.sustain_level = cmd.value;
+  else if (cmd.param == PG_SE_RELEASE) p.release_rate = cmd.value;
+  else return;
+  p.zero_times = (int32_t)(cmd.value64 & (PG_AHDSR_HOLD_ZERO | PG_AHDSR_DECAY_ZERO | PG_AHDSR_RELEASE_ZERO));
 }
 
 // Sampler::next_free_voice_index (sampler.rs:826-860), one lane per slot (all lanes of the wave call; every lane gets the result):
@@ -119,6 +132,11 @@ DEVO void sampler_command(const PgLaunch& L, const PgCmd& cmd, uint64_t now) {
   if (!lane0) return;
   if (cmd.type == CMD_SAMPLER_ALL_NOTES_OFF) {
     for (int i = 0; i < r.n_voices; ++i) sampler_voice_stop(&L.voices[r.voice0 + i], sampler_env(L, r, i), r.slots[i], now);
+  } else if (cmd.type == CMD_SAMPLER_ENV_PARAM) {   // set_envelope_parameter (:184-217, :1122-1131): the pool's one AhdsrParameters — here every slot's copy, playing or free
+    for (int i = 0; i < r.n_voices; ++i) {
+      PgEnv* const e = sampler_env(L, r, i);
+      if (e) { PgEnvParams p = e->params; ahdsr_set_param(p, cmd); e->params = p; }
+    }
   } else if (cmd.type == CMD_SAMPLER_PARAM) {   // process_parameter_update (:1076-1120): the stored base value, then every ACTIVE voice
     if (cmd.param == PG_SP_TRANSPOSE || cmd.param == PG_SP_FINETUNE) {
       if (cmd.param == PG_SP_TRANSPOSE) r.transpose = (int)cmd.value; else r.finetune = (int)cmd.value;

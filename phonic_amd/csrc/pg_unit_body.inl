@@ -550,7 +550,7 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
       }
       int flush = 0;
       __syncthreads();
-      if (!FAST_ONLY && cmd.type >= CMD_SAMPLER_NOTE_ON && cmd.type <= CMD_SAMPLER_STOP) {
+      if (!FAST_ONLY && ((cmd.type >= CMD_SAMPLER_NOTE_ON && cmd.type <= CMD_SAMPLER_STOP) || cmd.type == CMD_SAMPLER_ENV_PARAM)) {
         // a sampler's message (pg_sampler_dev.h): wave 0, one lane per slot of the pool where a voice is allocated
         if (tid == 0) ctl[2] = 0;
         if (tid < 64) sampler_command(L, cmd, pos0 + (uint64_t)frame0);

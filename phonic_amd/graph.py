@@ -107,6 +107,39 @@ class Graph(GraphHandle):
         self._check(self._lib.pg_graph_sampler_granular_params(self._h, sampler, C.byref(p)))
         return _capi.granular_params_dict(p)
 
+    # -- what changes every voice of a pool while notes sound (SetParameter(AMP_* | ML1R ..), SetModulation, ClearModulation, SetLoopRange) ----------
+    def sampler_set_envelope_parameter(self, sampler, id4, value, sample_time=0, normalized=False):
+        """One of _capi.SAMPLER_ENVELOPE_PARAM_IDS (AATK, AHLD, ADCY, ASTN, AREL) of the pool's one AhdsrParameters, in front of frame sample_time.
+        File samplers and granular ones; the sampler must have an envelope."""
+        self._check(self._lib.pg_graph_sampler_set_envelope_parameter(self._h, sampler, _capi.fourcc(id4), float(value), 1 if normalized else 0, sample_time))
+
+    def sampler_envelope_params(self, sampler, slot=0):
+        """The AhdsrParameters as the device holds them (_capi.sampler_envelope_state_dict): slot `slot`'s copy of a file sampler, a granular
+        sampler's one set. Debug read-back: waits for the graph's work."""
+        st = _capi.SamplerEnvelopeState()
+        self._check(self._lib.pg_graph_sampler_envelope_params(self._h, sampler, slot, C.byref(st)))
+        return _capi.sampler_envelope_state_dict(st)
+
+    def sampler_set_modulation(self, sampler, source, target, amount, bipolar=False, sample_time=0):
+        """SetModulation for the matrix of every slot of a granular sampler, playing or free (|amount| < 0.001 removes the route)."""
+        self._check(self._lib.pg_graph_sampler_set_modulation(self._h, sampler, int(source), int(target), float(amount), 1 if bipolar else 0, sample_time))
+
+    def sampler_clear_modulation(self, sampler, source, target, sample_time=0):
+        self._check(self._lib.pg_graph_sampler_clear_modulation(self._h, sampler, int(source), int(target), sample_time))
+
+    def sampler_set_lfo_rate(self, sampler, lfo, rate_hz, sample_time=0):
+        """ML1R / ML2R: every slot's LFO `lfo` (0, 1), clamped to 0.01..20 Hz; phase and draws stay."""
+        self._check(self._lib.pg_graph_sampler_set_lfo_rate(self._h, sampler, int(lfo), float(rate_hz), sample_time))
+
+    def sampler_set_lfo_waveform(self, sampler, lfo, waveform, sample_time=0):
+        """ML1W / ML2W: an index into _capi.LFO_WAVEFORMS."""
+        self._check(self._lib.pg_graph_sampler_set_lfo_waveform(self._h, sampler, int(lfo), int(waveform), sample_time))
+
+    def sampler_set_loop_range(self, sampler, loop_range, sample_time=0):
+        """SamplerMessage::SetLoopRange on a granular sampler: (start, end) in source frames of its buffer, or None for NO loop."""
+        has = loop_range is not None
+        self._check(self._lib.pg_graph_sampler_set_loop_range(self._h, sampler, 1 if has else 0, int(loop_range[0]) if has else 0, int(loop_range[1]) if has else 0, sample_time))
+
     def sampler_state(self, sampler):
         """The slot table and the sampler's own state as a dict (debug read-back: waits for the graph's work)."""
         st = _capi.SamplerState()
@@ -271,6 +304,19 @@ def sampler_parameters():
     for i in range(lib.pg_sampler_param_count()):
         d = _capi.ParamDesc()
         if lib.pg_sampler_param(i, C.byref(d)) != 0:
+            raise PhonicError(_capi.PG_ERR_NOT_FOUND, "parameter")
+        out.append(dict(fourcc=d.fourcc, type=d.type, min=d.min, max=d.max, default=d.default_value, scaling=d.scaling,
+                        scaling_args=(d.scaling_arg0, d.scaling_arg1), n_values=d.n_values, name=d.name.decode()))
+    return out
+
+
+def sampler_envelope_parameters():
+    """The five envelope parameter descriptors of the Sampler (Sampler::envelope_parameters()), as effect_parameters returns them."""
+    lib = _capi.load()
+    out = []
+    for i in range(lib.pg_sampler_envelope_param_count()):
+        d = _capi.ParamDesc()
+        if lib.pg_sampler_envelope_param(i, C.byref(d)) != 0:
             raise PhonicError(_capi.PG_ERR_NOT_FOUND, "parameter")
         out.append(dict(fourcc=d.fourcc, type=d.type, min=d.min, max=d.max, default=d.default_value, scaling=d.scaling,
                         scaling_args=(d.scaling_arg0, d.scaling_arg1), n_values=d.n_values, name=d.name.decode()))
