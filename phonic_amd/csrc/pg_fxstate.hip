@@ -320,9 +320,7 @@ int pg_effect_kind_weight(int kind) { return (kind >= 0 && kind < PG_FX_KIND_COU
 int pg_effect_kind_param_count(int kind) { return (kind >= 0 && kind < PG_FX_KIND_COUNT) ? KINDS[kind].n_params : -1; }
 int pg_effect_kind_param(int kind, int index, pg_param_desc* out) {
   if (kind < 0 || kind >= PG_FX_KIND_COUNT || index < 0 || index >= KINDS[kind].n_params) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
-  const ParamSpec& p = KINDS[kind].params[index];
-  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
-  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  param_desc_from_spec(KINDS[kind].params[index], out);
   return PG_OK;
 }
 // Sampler::granular_parameters() (sampler.rs:283-296): the same record, no device
@@ -330,9 +328,7 @@ int pg_granular_param_count(void) { return PG_GP_COUNT; }
 int pg_granular_param(int index, pg_param_desc* out) {
   if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
   if (index < 0 || index >= PG_GP_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
-  const ParamSpec& p = GRANULAR_PARAMS[index];
-  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
-  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  param_desc_from_spec(GRANULAR_PARAMS[index], out);
   return PG_OK;
 }
 void pg_voice_options_default(pg_voice_options* o) {  // FilePlaybackOptions::default()  file.rs:94-112

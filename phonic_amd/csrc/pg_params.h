@@ -24,6 +24,11 @@ struct ParamSpec {
   int smooth;       // SmoothSpec
   float smooth_arg; // exp: inertia (0 = default 1/256), lin: step, spring: duration
 };
+// A descriptor as the ABI hands it out (pg_effect_kind_param, pg_granular_param, pg_sampler_param, pg_sampler_envelope_param)
+inline void param_desc_from_spec(const ParamSpec& p, pg_param_desc* out) {
+  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
+  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+}
 
 #define FCC(a, b, c, d) PG_FOURCC(a, b, c, d)
 

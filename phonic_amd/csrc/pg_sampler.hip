@@ -1,8 +1,16 @@
 // Host side of the sampler voices: per-voice AHDSR envelopes (src/utils/ahdsr.rs, src/generator/sampler/voice.rs:181-212), granular voices
 // (src/generator/sampler/granular.rs; rendered by pg_grain_kernel, pg_k_grain.hip), their modulation matrix (src/modulation/matrix.rs,
 // src/generator/sampler/modulation.rs), the granular parameters that change while a voice plays (src/generator/sampler.rs:299-360), sample
-// buffers, and the samplers: pools of file voices whose note, allocation and stealing layer runs on the device (pg_sampler_dev.h).
+// buffers, and the samplers: pools of file voices whose note, allocation and stealing layer runs on the device (pg_sampler_dev.h), and the
+// granular-mode samplers: pools of grain records under a note layer of their own kernel (pg_gsampler_dev.h).
 // The graph, the control ring's drain and the write path are pg_host.hip's; what crosses between the two files stands in pg_host_internal.h.
+//
+// Every record has ONE builder and every kind of call one path; where a lone voice and a pool slot start differently, the difference is an argument
+// at the call site. Records: grain_rec_init (PgGrainVoice), mod_matrix_init (PgGrainMod), note_rec_init (PgSamplerRec, PgGSampler::note),
+// voice_init_grain_staged (a granular voice's or slot's PgVoice). A pool: sampler_pool_check -> sampler_pool_push -> sampler_pool_register, with the
+// kind's own tables and uploads between them. A message: sampler_tab_word (does the id take messages, what kind is it) -> sampler_message. A
+// read-back: sampler_for_readback. A grain launch: launch_grain_list. The four grow-by-doubling tables (graph_*_reserve) stay four functions: they
+// differ in what rides along — three side arrays, a launch list, a header in front, no words at all — more than they agree.
 #include "pg_host_internal.h"
 #include "pg_grain_dev.h"   // mod_lfo_reset: the note_on of a voice's modulation matrix runs on the host
 
@@ -116,16 +124,21 @@ int graph_gran_upload_live(pg_graph* g, hipStream_t stream) {
   g->gran_live_dirty = false;   // (a failure is the graph's: it renders nothing from then on)
   return g->d_gran_live.upload_async(g->gran_live, stream);
 }
-// pg_grain_kernel for frames [t0, t0 + n) of the chunk that began at chunk_t0, in front of the unit kernels that take its frames.
-int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
-  if (g->gran_voices.empty()) return PG_OK;
+// One pg_grain_kernel launch over the `n_live` records of launch list `live`, frames [t0, t0 + n) of the chunk that began at chunk_t0 (inside
+// write: nothing allocates)
+static int launch_grain_list(pg_graph* g, const int32_t* live, size_t n_live, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
   PgGrainLaunch L;
   memset(&L, 0, sizeof L);
-  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gran_voices.size(); L.live = g->d_gran_live.d;
+  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)n_live; L.live = live;
   L.voices = g->d_voices.d; L.cmds = d_cmds; L.n_cmds = n_cmds; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->gran_ended.d;
   L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
   HIP_TRY(pg_launch_grain(L, stream));
   return PG_OK;
+}
+// ... for the lone granular voices, in front of the unit kernels that take its frames: each picks its voice's commands from the piece's list
+int launch_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, const PgCmd* d_cmds, int n_cmds, hipStream_t stream) {
+  if (g->gran_voices.empty()) return PG_OK;
+  return launch_grain_list(g, g->d_gran_live.d, g->gran_voices.size(), t0, n, chunk_t0, d_cmds, n_cmds, stream);
 }
 void graph_sampler_release(pg_graph* g) {
   if (g->d_env_tab) (void)pg_free(g->d_env_tab);
@@ -148,10 +161,11 @@ bool voice_has_rendered(const pg_graph* g, const HostVoice& hv) {
   return false;
 }
 // The Xoshiro256++ state an `rng_state` input stands for (pg_granular_params, pg_mod_lfo): all-zero = SplitMix64 of the fixed seed, four times
+static uint64_t splitmix64_next(uint64_t& z) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); }
 static void rng_state_from(const uint64_t in[4], uint64_t out[4]) {
-  if ((in[0] | in[1] | in[2] | in[3]) != 0) { memcpy(out, in, 4 * sizeof(uint64_t)); return; }
+  if ((in[0] | in[1] | in[2] | in[3]) != 0) { memmove(out, in, 4 * sizeof(uint64_t)); return; }
   uint64_t z = 0x5EED0000ull;
-  for (int i = 0; i < 4; ++i) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; out[i] = x ^ (x >> 31); }
+  for (int i = 0; i < 4; ++i) out[i] = splitmix64_next(z);
 }
 // pg_granular_params <-> the device's PgGrainParams (rng_state is the pool's, not a parameter: it reads 0 on the way back)
 static void grain_params_to_device(const pg_granular_params& p, PgGrainParams& q) {
@@ -302,6 +316,37 @@ int pg_granular_params_check(const pg_granular_params* p) {  // GranularParamete
   return PG_OK;
 }
 }  // extern "C"
+// A granular voice as its mixer sees it — a lone one or a slot of a granular-mode sampler: a stereo source at the graph's rate whose frames
+// pg_grain_kernel stages; AmplifiedSource / PannedSource / fader are neutral — the granular branch of SamplerVoice::process does not pass them
+// (voice.rs:412-427)
+static void voice_init_grain_staged(const pg_graph* g, PgVoice& v, const pg_voice_options* opt) {
+  voice_init_neutral(g, v, opt, 1.0f, 0.0f);
+  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
+  v.current_speed = 1.0; v.target_speed = 1.0;
+  v.sched_class = -1;
+}
+// The staging buffer of a granular record (PgGrainVoice::staged), zeroed; on a failure *p is null or what the caller has to free
+static hipError_t grain_stage_alloc(void** p) {
+  const size_t bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
+  const hipError_t err = pg_malloc(p, bytes);
+  return err != hipSuccess ? err : pg_memset(*p, 0, bytes);
+}
+// The ONE builder of a granular record: GrainPool::new (granular.rs:384-429) over `n_frames` mono frames at `pcm`, rendering into `staged` for the
+// voice with device index `voice`. `rng`: an rng_state input (all-zero = the fixed seed). What a lone voice and a sampler's slot start with
+// differently are the arguments in the middle; each call site says where its values come from. No envelope and no matrix yet.
+static void grain_rec_init(PgGrainVoice& r, const pg_granular_params& p, const uint64_t rng[4], double speed, float volume, float panning, float trigger_phase, float playhead,
+                           const float* pcm, uint64_t n_frames, void* staged, uint64_t start_time, int voice) {
+  memset(&r, 0, sizeof r);
+  grain_params_to_device(p, r.params);
+  PgGrainPool& pool = r.pool;
+  rng_state_from(rng, pool.rng);
+  pool.trigger_new_grains = 1; pool.trigger_phase = trigger_phase;
+  pool.speed = speed; pool.volume = volume; pool.panning = panning;
+  pool.playhead = playhead; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
+  for (int i = 0; i < PG_GRAIN_POOL; ++i) { r.grains[i].volume = 1.0f; r.grains[i].window_mode = 2; }   // Grain::new (:995-1008)
+  r.pcm = pcm; r.n_frames = n_frames; r.staged = (float*)staged; r.stage_pos = 0;
+  r.start_time = start_time; r.stop_time = UINT64_MAX; r.exhausted_at = UINT64_MAX; r.voice = voice; r.has_env = 0;
+}
 // pg_graph_add_granular_voice / _from_buffer: `mono_pcm` (copied to the device, owned by the voice) or, with mono_pcm null, the granular mono
 // buffer of sample buffer `sbuf` (made already; n_frames is its length)
 static int graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono_pcm, int sbuf, size_t n_frames, const pg_granular_params* p, const pg_voice_options* opt) {
@@ -315,18 +360,12 @@ static int graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono
   if (!(opt->speed > 0.0)) return -set_error(PG_ERR_PARAMETER, "speed must be > 0");
   if (opt->volume < 0.0f || opt->panning < -1.0f || opt->panning > 1.0f) return -set_error(PG_ERR_PARAMETER, "invalid volume or panning");
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
-  // the voice as the mixer sees it: a stereo source at the graph's rate whose frames pg_grain_kernel renders; AmplifiedSource / PannedSource /
-  // fader are neutral — the granular branch of SamplerVoice::process does not pass them (voice.rs:412-427)
   PgVoice v;
-  voice_init_neutral(g, v, opt, 1.0f, 0.0f);
-  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
-  v.current_speed = 1.0; v.target_speed = 1.0;
-  v.sched_class = -1;
+  voice_init_grain_staged(g, v, opt);
   HostVoice hv;
   auto release = [&]() { if (hv.d_pcm) (void)pg_free(hv.d_pcm); if (hv.d_stage) (void)pg_free(hv.d_stage); };
-  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
   if ((sbuf < 0 && (pg_malloc(&hv.d_pcm, n_frames * sizeof(float)) != hipSuccess || pg_memcpy(hv.d_pcm, mono_pcm, n_frames * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) ||
-      pg_malloc(&hv.d_stage, stage_bytes) != hipSuccess || pg_memset(hv.d_stage, 0, stage_bytes) != hipSuccess) {
+      grain_stage_alloc(&hv.d_stage) != hipSuccess) {
     release();
     return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular voice allocation failed"));
   }
@@ -335,18 +374,11 @@ static int graph_add_granular_voice(pg_graph* g, int mixer_id, const float* mono
   int rc = g->d_voices.push(v, &dev_index);
   if (rc) { release(); return -graph_fail(g, rc); }
   if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + 1, (size_t)dev_index + 1))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
-  // GrainPool::new + start(parameters, speed, volume, panning) (granular.rs:384-429, :474-489)
+  // GrainPool::new, then start(parameters, speed, volume, panning) (granular.rs:474-489) with the options' three: the trigger phase is 1.0 — the
+  // first frame triggers a grain — and the playhead stands at the parameters' position; the voice starts at the options' start time
   std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
-  memset(r.get(), 0, sizeof(PgGrainVoice));
-  grain_params_to_device(*p, r->params);
-  PgGrainPool& pool = r->pool;
-  rng_state_from(p->rng_state, pool.rng);
-  pool.trigger_new_grains = 1; pool.trigger_phase = 1.0f;
-  pool.speed = opt->speed; pool.volume = opt->volume; pool.panning = opt->panning;
-  pool.playhead = p->position; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;   // (Cloud: GrainPool::new, granular.rs:399)
-  for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
-  r->pcm = sbuf >= 0 ? g->sample_buffers[sbuf].d_mono : (const float*)hv.d_pcm; r->n_frames = n_frames; r->staged = (float*)hv.d_stage; r->stage_pos = 0;
-  r->start_time = opt->start_time; r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = dev_index; r->has_env = 0;
+  grain_rec_init(*r, *p, p->rng_state, opt->speed, opt->volume, opt->panning, /*trigger_phase*/ 1.0f, /*playhead*/ p->position,
+                 sbuf >= 0 ? g->sample_buffers[sbuf].d_mono : (const float*)hv.d_pcm, n_frames, hv.d_stage, opt->start_time, dev_index);
   const int32_t rec = (int32_t)g->gran_n;
   (void)hipSetDevice(g->device);
   if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
@@ -513,6 +545,7 @@ int pg_graph_voice_granular_params(pg_graph* g, int voice_id, pg_granular_params
 // ---- the modulation matrix of a granular voice (src/modulation/matrix.rs, src/generator/sampler/modulation.rs; phase 0 of pg_grain_kernel) ----
 static_assert(PG_MOD_SOURCES == PG_GMOD_SOURCES && PG_MOD_TARGETS == PG_GMOD_TARGETS, "the header's and the device's matrix agree");
 static float mod_clamp_rate(float rate_hz) { return rate_hz < 0.01f ? 0.01f : (rate_hz > 20.0f ? 20.0f : rate_hz); }   // FloatParameter::clamp_value of ML1R / ML2R (sampler.rs:369-384)
+static float mod_phase_inc(float rate_hz, uint32_t sample_rate) { return (float)((double)mod_clamp_rate(rate_hz) / (double)sample_rate); }   // Lfo::set_rate (lfo.rs:102-104)
 void pg_modulation_params_default(pg_modulation_params* p) {  // Sampler::modulation_config (sampler.rs:369-427), a note at full velocity
   if (!p) return;
   memset(p, 0, sizeof *p);
@@ -537,6 +570,28 @@ int pg_modulation_params_check(const pg_modulation_params* p) {
   for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) { const int rc = mod_check_route(s, t, p->routes[s][t].amount); if (rc) return rc; }
   return PG_OK;
 }
+// The ONE builder of a matrix, as create_matrix leaves it before any note (voice.rs:341-373): each Lfo::new(sample_rate, default rate, default
+// waveform) draws its three random values from its generator (state.rs:96-113, lfo.rs:70-86) — `rng0` / `rng1`: an rng_state input per LFO,
+// all-zero = the fixed seed —, then the parameter updates in front of the first note, set_rate / set_waveform (lfo.rs:102-119), then the routes.
+// The two static sources stand where they stand before a note (processor.rs:236-244, :292-298); note_on — mod_lfo_reset, velocity, note pitch — is
+// the caller's, where it has a note.
+static void mod_matrix_init(PgGrainMod& m, const pg_modulation_params& p, uint32_t sample_rate, const uint64_t rng0[4], const uint64_t rng1[4]) {
+  memset(&m, 0, sizeof m);
+  m.on = 1;
+  for (int l = 0; l < 2; ++l) {
+    PgModLfo& o = m.lfo[l];
+    rng_state_from(l ? rng1 : rng0, o.rng);
+    o.phase = 0.0f;
+    o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
+    o.phase_inc = mod_phase_inc(p.lfo[l].rate_hz, sample_rate);
+    o.waveform = p.lfo[l].waveform;
+  }
+  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {  // update_target on an empty slot (matrix.rs:75-82)
+    const pg_mod_route& r = p.routes[s][t];
+    if (fabsf(r.amount) >= 0.001f) { m.amount[s][t] = r.amount; m.bipolar[s][t] = r.bipolar ? 1 : 0; }
+  }
+  m.velocity = 0.0f; m.note_pitch = 60.0f / 127.0f;
+}
 int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_modulation_params* p) {
   { const int rc = pg_modulation_params_check(p); if (rc) return rc; }
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
@@ -549,24 +604,8 @@ int pg_graph_set_voice_modulation_matrix(pg_graph* g, int voice_id, const pg_mod
   if (voice_has_rendered(g, hv)) return set_error(PG_ERR_STATE, "Source with id %d has rendered frames already: the modulation matrix is attached before the voice starts", voice_id);
   if (graph_quiesce(g)) return graph_fail(g, PG_ERR_DEVICE);
   PgGrainMod m;
-  memset(&m, 0, sizeof m);
-  m.on = 1;
-  for (int l = 0; l < 2; ++l) {
-    PgModLfo& o = m.lfo[l];
-    const pg_mod_lfo& in = p->lfo[l];
-    rng_state_from(in.rng_state, o.rng);
-    // create_matrix: Lfo::new(sample_rate, default rate, default waveform) (state.rs:96-113, lfo.rs:70-86)
-    o.phase = 0.0f;
-    o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
-    // the parameter updates in front of the note: set_rate / set_waveform (lfo.rs:102-119)
-    o.phase_inc = (float)((double)mod_clamp_rate(in.rate_hz) / (double)g->sample_rate);
-    o.waveform = in.waveform;
-  }
-  for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {  // update_target on an empty slot (matrix.rs:75-82)
-    const pg_mod_route& r = p->routes[s][t];
-    if (fabsf(r.amount) >= 0.001f) { m.amount[s][t] = r.amount; m.bipolar[s][t] = r.bipolar ? 1 : 0; }
-  }
-  // SamplerVoiceModulationState::start(note, velocity) = ModulationMatrix::note_on (matrix.rs:394-408)
+  mod_matrix_init(m, *p, g->sample_rate, p->lfo[0].rng_state, p->lfo[1].rng_state);
+  // the voice's note is known here: SamplerVoiceModulationState::start(note, velocity) = ModulationMatrix::note_on (matrix.rs:394-408)
   for (int l = 0; l < 2; ++l) mod_lfo_reset(m.lfo[l]);
   m.velocity = p->velocity;
   m.note_pitch = (float)p->note / 127.0f;
@@ -763,16 +802,101 @@ void sampler_stage_command(pg_graph* g, PgCmd& c) {
     return;
   }
 }
-// One sampler message into the control ring (any thread)
-static int sampler_message(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int64_t note_id = 0, float value = 0.0f, float value2 = 0.0f, double dvalue = 0.0) {
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+// ---- the message calls' one path (any thread): what a call must know of the sampler stands in sampler_alive_tab / sampler_frames_tab ----
+// The sampler's SAMPLER_TAB_* word while it takes messages; 0: PG_ERR_PARAMETER (null handle) or PG_ERR_NOT_FOUND is set ...
+static int sampler_tab_word(pg_graph* g, int sampler_id) {
+  if (!g) { set_error(PG_ERR_PARAMETER, "graph handle is null"); return 0; }
+  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return 0; }
+  return g->sampler_alive_tab.get((size_t)sampler_id);
+}
+static int sampler_tab_error(const pg_graph* g) { return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER; }   // ... and the code it set
+// One message for a sampler that takes messages into the control ring. `param`: a note id as note_param narrows it, or the call's own word.
+static int sampler_message(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int param = 0, float value = 0.0f, float value2 = 0.0f, double dvalue = 0.0) {
+  if (!sampler_tab_word(g, sampler_id)) return sampler_tab_error(g);
   pgc::CtrlMsg m;
   memset(&m, 0, sizeof m);
-  // (a note id this graph never handed out plays nowhere: 0 is no note's id)
-  m.type = type; m.id = sampler_id; m.param = (note_id > 0 && note_id <= INT32_MAX) ? (int32_t)note_id : 0; m.value = value; m.value2 = value2; m.dvalue = dvalue; m.sample_time = sample_time;
+  m.type = type; m.id = sampler_id; m.param = param; m.value = value; m.value2 = value2; m.dvalue = dvalue; m.sample_time = sample_time;
   if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
   return PG_OK;
+}
+// A note id as a message carries it: one this graph never handed out plays nowhere, and 0 is no note's id
+static int note_param(int64_t note_id) { return (note_id > 0 && note_id <= INT32_MAX) ? (int32_t)note_id : 0; }
+// The sampler behind `sampler_id` for a read-back (owner thread): while it lives, and a transient one that has stopped — it keeps its records, so
+// the state that says so stays readable until the id is removed or its mixer goes. Else null (PG_ERR_NOT_FOUND is set).
+static const HostSampler* sampler_for_readback(pg_graph* g, int sampler_id) {
+  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0))) {
+    set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+    return nullptr;
+  }
+  return &g->samplers[sampler_id];
+}
+
+// ---- a pool's construction: what pg_graph_add_sampler and pg_graph_add_granular_sampler share, in three steps with each kind's own work between them ----
+// 1. The checks, in the order the calls make them: the options, a granular sampler's own options, the handle, the mixer, the buffer, the loop range.
+static int sampler_pool_check(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, bool granular, const pg_granular_sampler_options* gopt) {
+  { const int rc = pg_sampler_options_check(opt); if (rc) return rc; }
+  if (granular) { const int rc = pg_granular_sampler_options_check(gopt); if (rc) return rc; }
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  if (mixer_id == PG_MAIN_MIXER) return set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, %s",
+                                                  granular ? "the pool is one source of one mixer" : "the pool needs one workgroup that sees all of its voices");
+  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
+  const SampleBuffer* sb = sample_buffer_find(g, buffer_id);
+  if (!sb) return PG_ERR_NOT_FOUND;
+  if (opt->has_loop_range && (opt->loop_start >= sb->n_frames || opt->loop_end > sb->n_frames)) return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%zu", (unsigned long long)opt->loop_start, (unsigned long long)opt->loop_end, sb->n_frames);
+  return PG_OK;
+}
+// What every pool voice is added with: a source its mixer keeps, from the sampler's start time on
+static pg_voice_options sampler_pool_voice_options(const pg_sampler_options* opt) {
+  pg_voice_options vo;
+  pg_voice_options_default(&vo);
+  vo.non_transient = 1; vo.start_time = opt->start_time;
+  return vo;
+}
+// 2. `n` copies of the caller's voice record `v` at consecutive device indices from *voice0 on, room for them in the envelope table; the device is
+// set for the uploads that follow. A failure is the graph's.
+static int sampler_pool_push(pg_graph* g, const PgVoice& v, int n, int* voice0) {
+  for (int k = 0; k < n; ++k) {
+    int di = -1;
+    const int rc = g->d_voices.push(v, &di);
+    if (rc || (k > 0 && di != *voice0 + k)) return graph_fail(g, rc ? rc : set_error(PG_ERR_STATE, "pool voices are not contiguous"));
+    if (k == 0) *voice0 = di;
+  }
+  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + (size_t)n, (size_t)(*voice0 + n)))) return graph_fail(g, PG_ERR_DEVICE);
+  (void)hipSetDevice(g->device);
+  return PG_OK;
+}
+// The note layer's record before any note: the file sampler's PgSamplerRec, the granular one's PgGSampler::note
+static void note_rec_init(PgSamplerRec& r, int unit, int voice0, int n, const pg_sampler_options* opt) {
+  memset(&r, 0, sizeof r);
+  r.unit = unit; r.voice0 = voice0; r.n_voices = n; r.has_envelope = opt->has_envelope ? 1 : 0; r.transient = opt->transient ? 1 : 0;
+  r.base_volume = 1.0f; r.base_panning = 0.0f; r.pitch_factor = std::pow(2.0, 0.0 / 12.0 + 0.0 / 1200.0);
+  for (int k = 0; k < PG_SAMPLER_MAX_VOICES; ++k) { r.slots[k].release_start_frame = UINT64_MAX; r.slots[k].note = 60; r.slots[k].note_volume = 1.0f; }   // SamplerVoice::new (voice.rs:51-55)
+}
+// 3. The records are on the device: the sampler's place in the graph. `hs` arrives with what is its kind's (a granular sampler's grain records),
+// `tab_kind` with its kind's SAMPLER_TAB_* bits, `stages` with a granular sampler's staging buffers, one per slot: each passes to its slot's voice,
+// and a failure frees those no voice owns yet. Returns the sampler's id (< 0: -PG_ERR_*).
+static int sampler_pool_register(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_voice_options& vo, int voice0, HostSampler hs, int tab_kind, std::vector<void*>* stages) {
+  const int n = (int)opt->voice_count, sampler_id = (int)g->samplers.size();
+  const SampleBuffer& sb = g->sample_buffers[buffer_id];
+  g->samp_stopped[(size_t)sampler_id] = 0;
+  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
+  // the mixer's list inserts a new source in FRONT of those with the same start time (mixed.rs:324-329): the last slot goes in first, so that the
+  // mixer — and the kernel that sums the pool — meets it in slot order (sampler.rs:989-1006)
+  for (int k = n - 1; k >= 0; --k) {
+    HostVoice hv;
+    hv.sbuf = buffer_id; hv.sampler = sampler_id;
+    if (stages) { hv.d_stage = (*stages)[(size_t)k]; (*stages)[(size_t)k] = nullptr; }   // (the voice owns it from here on)
+    hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
+    g->sample_buffers[buffer_id].use_count += 1;
+    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
+    if (id < 0) { if (stages) for (void* p : *stages) if (p) (void)pg_free(p); return id; }
+    if (k == 0) hs.voice_id_slot0 = id;
+  }
+  if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
+  g->samplers.push_back(hs);
+  if (hs.granular) { g->n_gsamplers += 1; g->gsamp_dirty = true; }
+  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) || !g->sampler_alive_tab.append((int8_t)(tab_kind | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
+  return sampler_id;
 }
 
 extern "C" {
@@ -794,29 +918,20 @@ int pg_sampler_param_count(void) { return PG_SP_COUNT; }
 int pg_sampler_param(int index, pg_param_desc* out) {   // Sampler::base_parameters() (sampler.rs:120-127)
   if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
   if (index < 0 || index >= PG_SP_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
-  const ParamSpec& p = SAMPLER_PARAMS[index];
-  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
-  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  param_desc_from_spec(SAMPLER_PARAMS[index], out);
   return PG_OK;
 }
 int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt) {
   pg_sampler_options def;
   if (!opt) { pg_sampler_options_default(&def); opt = &def; }
-  { const int rc = pg_sampler_options_check(opt); if (rc) return -rc; }
-  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (mixer_id == PG_MAIN_MIXER) return -set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, the pool needs one workgroup that sees all of its voices");
-  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
-  if (!sample_buffer_find(g, buffer_id)) return -PG_ERR_NOT_FOUND;
-  const SampleBuffer sb = g->sample_buffers[buffer_id];
-  if (opt->has_loop_range && (opt->loop_start >= sb.n_frames || opt->loop_end > sb.n_frames)) return -set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%zu", (unsigned long long)opt->loop_start, (unsigned long long)opt->loop_end, sb.n_frames);
+  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, false, nullptr); if (rc) return -rc; }
   drain_control_messages(g);
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
+  const SampleBuffer sb = g->sample_buffers[buffer_id];
   const int n = (int)opt->voice_count, sampler_id = (int)g->samplers.size();
   // a pool voice: PreloadedFileSource::from_shared_buffer(buffer, FilePlaybackOptions::default().fade_out(50 ms), rate) behind AmplifiedSource(1.0) /
   // PannedSource(0.0) (sampler.rs:505-530, voice.rs:60-65) — a source its mixer keeps, with no note yet: inactive, delivering nothing
-  pg_voice_options vo;
-  pg_voice_options_default(&vo);
-  vo.non_transient = 1; vo.start_time = opt->start_time;
+  const pg_voice_options vo = sampler_pool_voice_options(opt);
   PgVoice v;
   voice_init_neutral(g, v, &vo, 1.0f, 0.0f);
   v.active = 0;
@@ -831,14 +946,7 @@ int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_samp
   v.sched_class = -1;   // (always on the exact kernel, every note at a speed of its own: no shared resampler schedule)
   if (graph_samp_reserve(g, g->samplers.size() + 1)) return -graph_fail(g, PG_ERR_DEVICE);
   int voice0 = -1;
-  for (int k = 0; k < n; ++k) {
-    int di = -1;
-    const int rc = g->d_voices.push(v, &di);
-    if (rc || (k > 0 && di != voice0 + k)) return -graph_fail(g, rc ? rc : set_error(PG_ERR_STATE, "pool voices are not contiguous"));
-    if (k == 0) voice0 = di;
-  }
-  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + (size_t)n, (size_t)(voice0 + n)))) return -graph_fail(g, PG_ERR_DEVICE);
-  (void)hipSetDevice(g->device);
+  { const int rc = sampler_pool_push(g, v, n, &voice0); if (rc) return -rc; }
   if (opt->has_envelope) {
     PgEnv e;
     memset(&e, 0, sizeof e);
@@ -847,30 +955,10 @@ int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_samp
     if (pg_memcpy(g->d_env + voice0, es.data(), es.size() * sizeof(PgEnv), hipMemcpyHostToDevice) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
   }
   std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
-  memset(r.get(), 0, sizeof(PgSamplerRec));
-  r->unit = g->mixers[mixer_id].unit_slot; r->voice0 = voice0; r->n_voices = n; r->has_envelope = opt->has_envelope ? 1 : 0; r->transient = opt->transient ? 1 : 0;
-  r->base_volume = 1.0f; r->base_panning = 0.0f; r->pitch_factor = std::pow(2.0, 0.0 / 12.0 + 0.0 / 1200.0);
-  for (int k = 0; k < PG_SAMPLER_MAX_VOICES; ++k) { r->slots[k].release_start_frame = UINT64_MAX; r->slots[k].note = 60; r->slots[k].note_volume = 1.0f; }   // SamplerVoice::new (voice.rs:51-55)
+  note_rec_init(*r, g->mixers[mixer_id].unit_slot, voice0, n, opt);
   if (pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, r.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess || samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess ||
       graph_env_head_refresh(g)) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
-  g->samp_stopped[(size_t)sampler_id] = 0;
-  // the mixer's list inserts a new source in FRONT of those with the same start time (mixed.rs:324-329): the last slot goes in first, so that the
-  // kernel meets — and sums — the pool in slot order (sampler.rs:989-1006)
-  HostSampler hs;
-  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
-  for (int k = n - 1; k >= 0; --k) {
-    HostVoice hv;
-    hv.sbuf = buffer_id; hv.sampler = sampler_id;
-    hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
-    g->sample_buffers[buffer_id].use_count += 1;
-    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
-    if (id < 0) return id;
-    if (k == 0) hs.voice_id_slot0 = id;
-  }
-  if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
-  g->samplers.push_back(hs);
-  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) || !g->sampler_alive_tab.append((int8_t)(SAMPLER_TAB_FILE | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
-  return sampler_id;
+  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, HostSampler(), SAMPLER_TAB_FILE, nullptr);
 }
 int pg_graph_remove_sampler(pg_graph* g, int sampler_id) {
   const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_REMOVE, 0);
@@ -880,85 +968,69 @@ int pg_graph_remove_sampler(pg_graph* g, int sampler_id) {
 int64_t pg_graph_sampler_note_on(pg_graph* g, int sampler_id, uint8_t note, float volume, float panning, uint64_t sample_time) {
   if (!(volume >= 0.0f) || !std::isfinite(volume)) return -set_error(PG_ERR_PARAMETER, "Invalid note volume: %g. Must be finite and >= 0", (double)volume);
   if (!std::isfinite(panning)) return -set_error(PG_ERR_PARAMETER, "Invalid note panning: %g. Must be finite", (double)panning);
-  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return -set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
+  if (!sampler_tab_word(g, sampler_id)) return -sampler_tab_error(g);   // (no id is used up for a sampler that is not there)
   const int64_t note_id = g->next_note_id.fetch_add(1, std::memory_order_relaxed);
   if (note_id > INT32_MAX) return -set_error(PG_ERR_STATE, "note ids are used up");
-  const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_ON, sample_time, note_id, volume, panning, (double)note);
+  const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_ON, sample_time, note_param(note_id), volume, panning, (double)note);
   return rc ? -rc : note_id;
 }
-int pg_graph_sampler_note_off(pg_graph* g, int sampler_id, int64_t note_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_OFF, sample_time, note_id); }
+int pg_graph_sampler_note_off(pg_graph* g, int sampler_id, int64_t note_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_OFF, sample_time, note_param(note_id)); }
 int pg_graph_sampler_all_notes_off(pg_graph* g, int sampler_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_ALL_NOTES_OFF, sample_time); }
 int pg_graph_sampler_set_note_speed(pg_graph* g, int sampler_id, int64_t note_id, double speed, float glide, uint64_t sample_time) {
   if (!(speed > 0.0) || !std::isfinite(speed)) return set_error(PG_ERR_PARAMETER, "speed must be > 0");
-  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_SPEED, sample_time, note_id, glide > 0.0f ? glide : 0.0f, 0.0f, speed);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_SPEED, sample_time, note_param(note_id), glide > 0.0f ? glide : 0.0f, 0.0f, speed);
 }
 int pg_graph_sampler_set_note_volume(pg_graph* g, int sampler_id, int64_t note_id, float volume, uint64_t sample_time) {
   if (!(volume >= 0.0f) || !std::isfinite(volume)) return set_error(PG_ERR_PARAMETER, "Invalid note volume: %g. Must be finite and >= 0", (double)volume);
-  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_VOLUME, sample_time, note_id, volume);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_VOLUME, sample_time, note_param(note_id), volume);
 }
 int pg_graph_sampler_set_note_panning(pg_graph* g, int sampler_id, int64_t note_id, float panning, uint64_t sample_time) {
   if (!std::isfinite(panning)) return set_error(PG_ERR_PARAMETER, "Invalid note panning: %g. Must be finite", (double)panning);
-  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_PAN, sample_time, note_id, panning);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_NOTE_PAN, sample_time, note_param(note_id), panning);
 }
 int pg_graph_sampler_set_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
   const int pi = find_sampler_param(fourcc);
   if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown sampler parameter 0x%08x", fourcc);
   if (value != value) return set_error(PG_ERR_PARAMETER, "Sampler parameter '%s' is not a number", SAMPLER_PARAMS[pi].name);
+  // (this call refuses a normalized value outside 0..1 where the envelope's and the granular parameters' calls clamp it: the difference is kept as it
+  // was found — UNVERIFIED against the reference which of the two its handle does)
   if (is_normalized && !(value >= 0.0f && value <= 1.0f)) return set_error(PG_ERR_PARAMETER, "Invalid parameter update: value should be a normalized value, but is: '%g'", (double)value);
   float raw = 0.0f;
   (void)resolve_update(SAMPLER_PARAMS[pi], value, is_normalized != 0, raw);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = pgc::CT_SAMPLER_PARAM; m.id = sampler_id; m.param = pi; m.value = raw; m.sample_time = sample_time;
-  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
-  return PG_OK;
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_PARAM, sample_time, pi, raw);
 }
 int pg_graph_sampler_stop(pg_graph* g, int sampler_id, uint64_t sample_time) { return sampler_message(g, sampler_id, pgc::CT_SAMPLER_STOP, sample_time); }
 int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out) {
   if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  // (a transient sampler that has stopped keeps its record: the state that says so stays readable until the id is removed or its mixer goes)
-  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
-    return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  const HostSampler& hs = g->samplers[sampler_id];
+  const HostSampler* hs = sampler_for_readback(g, sampler_id);
+  if (!hs) return PG_ERR_NOT_FOUND;
   (void)hipSetDevice(g->device);
   if (g->d_voices.flush()) return PG_ERR_DEVICE;   // (pool voices no write has carried to the device yet)
-  if (hs.granular) {   // the note layer's record is pg_gsampler_kernel's: which slot is active and where its envelope stands is written there
-    std::unique_ptr<PgGSampler> q(new PgGSampler);
-    { const int rc = graph_read_back(g, q.get(), g->d_gsamp + hs.rec, sizeof(PgGSampler)); if (rc) return rc; }
-    memset(out, 0, sizeof *out);
-    out->voice_count = hs.n_voices; out->stopping = q->note.stopping; out->stopped = q->note.stopped;
-    out->transpose = q->note.transpose; out->finetune = q->note.finetune; out->volume = q->note.base_volume; out->panning = q->note.base_panning;
-    for (int k = 0; k < hs.n_voices; ++k) {
-      const bool active = q->active[k] != 0;
-      pg_sampler_slot_state& o = out->slots[k];
-      o.note_id = active ? (int64_t)q->note.slots[k].note_id : 0;
-      o.release_start_frame = active ? q->note.slots[k].release_start_frame : UINT64_MAX;
-      o.note = q->note.slots[k].note; o.note_volume = q->note.slots[k].note_volume; o.note_panning = q->note.slots[k].note_panning;
-      o.envelope_stage = hs.has_envelope ? (int)q->env[k].stage : -1;
-      out->active_voices += active ? 1 : 0;
-    }
-    return PG_OK;
+  // The note layer's record (a file sampler's PgSamplerRec is read into q->note) and the two things a slot's state needs besides: whether it is
+  // active and where its envelope stands. A granular sampler's record holds both, written by pg_gsampler_kernel; a file sampler's slot is active
+  // as its voice says — SamplerVoice::is_active (pg_sampler_dev.h: sampler_slot_active) — and its envelope is its voice's PgEnv.
+  std::unique_ptr<PgGSampler> q(new PgGSampler);
+  std::vector<PgVoice> vs;
+  std::vector<PgEnv> es;
+  if (hs->granular) { const int rc = graph_read_back(g, q.get(), g->d_gsamp + hs->rec, sizeof(PgGSampler)); if (rc) return rc; }
+  else {
+    vs.resize((size_t)hs->n_voices); es.resize((size_t)hs->n_voices);
+    { const int rc = graph_read_back(g, &q->note, (const PgSamplerRec*)(g->d_samp + 1) + hs->rec, sizeof(PgSamplerRec)); if (rc) return rc; }
+    { const int rc = graph_read_back(g, vs.data(), g->d_voices.d + q->note.voice0, vs.size() * sizeof(PgVoice)); if (rc) return rc; }
+    if (hs->has_envelope) { const int rc = graph_read_back(g, es.data(), g->d_env + q->note.voice0, es.size() * sizeof(PgEnv)); if (rc) return rc; }
   }
-  std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
-  std::vector<PgVoice> vs((size_t)hs.n_voices);
-  std::vector<PgEnv> es((size_t)hs.n_voices);
-  { const int rc = graph_read_back(g, r.get(), (const PgSamplerRec*)(g->d_samp + 1) + hs.rec, sizeof(PgSamplerRec)); if (rc) return rc; }
-  { const int rc = graph_read_back(g, vs.data(), g->d_voices.d + r->voice0, vs.size() * sizeof(PgVoice)); if (rc) return rc; }
-  if (hs.has_envelope) { const int rc = graph_read_back(g, es.data(), g->d_env + r->voice0, es.size() * sizeof(PgEnv)); if (rc) return rc; }
+  const PgSamplerRec& r = q->note;
   memset(out, 0, sizeof *out);
-  out->voice_count = hs.n_voices; out->stopping = r->stopping; out->stopped = r->stopped;
-  out->transpose = r->transpose; out->finetune = r->finetune; out->volume = r->base_volume; out->panning = r->base_panning;
-  for (int k = 0; k < hs.n_voices; ++k) {
-    const bool active = vs[(size_t)k].active != 0 && vs[(size_t)k].finished == 0;   // SamplerVoice::is_active (pg_sampler_dev.h: sampler_slot_active)
+  out->voice_count = hs->n_voices; out->stopping = r.stopping; out->stopped = r.stopped;
+  out->transpose = r.transpose; out->finetune = r.finetune; out->volume = r.base_volume; out->panning = r.base_panning;
+  for (int k = 0; k < hs->n_voices; ++k) {
+    const bool active = hs->granular ? q->active[k] != 0 : (vs[(size_t)k].active != 0 && vs[(size_t)k].finished == 0);
     pg_sampler_slot_state& o = out->slots[k];
-    o.note_id = active ? (int64_t)r->slots[k].note_id : 0;
-    o.release_start_frame = active ? r->slots[k].release_start_frame : UINT64_MAX;   // SamplerVoice::reset clears it (voice.rs:234-235)
-    o.note = r->slots[k].note; o.note_volume = r->slots[k].note_volume; o.note_panning = r->slots[k].note_panning;
-    o.envelope_stage = hs.has_envelope ? (int)es[(size_t)k].state.stage : -1;
+    o.note_id = active ? (int64_t)r.slots[k].note_id : 0;
+    o.release_start_frame = active ? r.slots[k].release_start_frame : UINT64_MAX;   // SamplerVoice::reset clears it (voice.rs:234-235)
+    o.note = r.slots[k].note; o.note_volume = r.slots[k].note_volume; o.note_panning = r.slots[k].note_panning;
+    o.envelope_stage = !hs->has_envelope ? -1 : hs->granular ? (int)q->env[k].stage : (int)es[(size_t)k].state.stage;
     out->active_voices += active ? 1 : 0;
   }
   return PG_OK;
@@ -1007,13 +1079,7 @@ int launch_gsampler_boundary(pg_graph* g, uint64_t t, uint32_t frame, const PgCm
 }
 int launch_gsampler_grains(pg_graph* g, uint64_t t0, uint32_t n, uint64_t chunk_t0, hipStream_t stream) {
   if (g->gsamp_grains.empty() || n == 0) return PG_OK;
-  PgGrainLaunch L;
-  memset(&L, 0, sizeof L);
-  L.recs = g->d_gran; L.n_recs = (uint32_t)g->gran_n; L.n_live = (uint32_t)g->gsamp_grains.size(); L.live = g->d_gsamp_grains.d;
-  L.voices = g->d_voices.d; L.cmds = nullptr; L.n_cmds = 0; L.sample_rate = g->sample_rate; L.lut = g->d_grain_lut; L.ended = g->gran_ended.d;   // (everything a slot takes is applied at a span's edge, by pg_gsampler_kernel)
-  L.t0 = t0; L.n = n; L.chunk_t0 = chunk_t0;
-  HIP_TRY(pg_launch_grain(L, stream));
-  return PG_OK;
+  return launch_grain_list(g, g->d_gsamp_grains.d, g->gsamp_grains.size(), t0, n, chunk_t0, nullptr, 0, stream);   // (no commands: everything a slot takes is applied at a span's edge, by pg_gsampler_kernel)
 }
 // Room for `n` records, indexed like the samplers. The graph is quiescent. A failure leaves the graph on its old records.
 static int graph_gsamp_reserve(pg_graph* g, size_t n) {
@@ -1029,7 +1095,6 @@ static int graph_gsamp_reserve(pg_graph* g, size_t n) {
   g->d_gsamp = nt; g->gsamp_cap = cap;
   return PG_OK;
 }
-static uint64_t splitmix64_next(uint64_t& z) { z += 0x9E3779B97F4A7C15ull; uint64_t x = z; x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull; x = (x ^ (x >> 27)) * 0x94D049BB133111EBull; return x ^ (x >> 31); }
 static uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
 
 extern "C" {
@@ -1058,16 +1123,7 @@ void pg_granular_sampler_rng_state(const uint64_t given[4], uint32_t slot, uint3
 int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt) {
   pg_sampler_options def;
   if (!opt) { pg_sampler_options_default(&def); opt = &def; }
-  { const int rc = pg_sampler_options_check(opt); if (rc) return -rc; }
-  { const int rc = pg_granular_sampler_options_check(gopt); if (rc) return -rc; }
-  if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (mixer_id == PG_MAIN_MIXER) return -set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, the pool is one source of one mixer");
-  if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return -set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
-  if (!sample_buffer_find(g, buffer_id)) return -PG_ERR_NOT_FOUND;
-  {
-    const SampleBuffer& b0 = g->sample_buffers[buffer_id];
-    if (opt->has_loop_range && (opt->loop_start >= b0.n_frames || opt->loop_end > b0.n_frames)) return -set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%zu", (unsigned long long)opt->loop_start, (unsigned long long)opt->loop_end, b0.n_frames);
-  }
+  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, true, gopt); if (rc) return -rc; }
   { const int rc = pg_graph_prepare_granular_buffer(g, buffer_id); if (rc) return -rc; }   // Sampler::create_granular_sample_buffer, shared by all slots
   drain_control_messages(g);
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
@@ -1081,14 +1137,9 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
   else if (!q.has_loop_range && sb.has_loop) { q.has_loop_range = 1; q.loop_start = (float)sb.loop_start / total; q.loop_end = (float)sb.loop_end / total; }
   // a slot as the mixer sees it: a stereo source at the graph's rate that the mixer keeps, whose frames pg_grain_kernel stages; always `active` —
   // whether the slot plays is the note layer's (PgGSampler::active), a free slot's staged frames are zero
-  pg_voice_options vo;
-  pg_voice_options_default(&vo);
-  vo.non_transient = 1; vo.start_time = opt->start_time;
+  const pg_voice_options vo = sampler_pool_voice_options(opt);
   PgVoice v;
-  voice_init_neutral(g, v, &vo, 1.0f, 0.0f);
-  v.channels = 2; v.src_rate = g->sample_rate; v.out_rate = g->sample_rate; v.ratio = 1.0f;
-  v.current_speed = 1.0; v.target_speed = 1.0;
-  v.sched_class = -1;
+  voice_init_grain_staged(g, v, &vo);
   if (graph_samp_reserve(g, g->samplers.size() + 1) || graph_gsamp_reserve(g, g->samplers.size() + 1) || graph_gran_reserve(g, g->gran_n + (size_t)n)) return -graph_fail(g, PG_ERR_DEVICE);
   {  // the launch lists hold every granular sampler's record and slots: graph_gsampler_upload_live runs inside write and must not allocate
     size_t slots = (size_t)n;
@@ -1099,59 +1150,32 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
   if (!g->gran_voices.empty()) g->gran_live_dirty = true;   // (graph_gran_reserve may have moved the lone voices' launch list: it is uploaded again)
   std::vector<void*> stages;
   auto release = [&]() { for (void* p : stages) (void)pg_free(p); };
-  const size_t stage_bytes = (size_t)PG_MAX_FRAMES * 2 * sizeof(float);
   for (int k = 0; k < n; ++k) {
     void* p = nullptr;
-    if (pg_malloc(&p, stage_bytes) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler allocation failed")); }
-    stages.push_back(p);
-    if (pg_memset(p, 0, stage_bytes) != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler allocation failed")); }
+    const hipError_t err = grain_stage_alloc(&p);
+    if (p) stages.push_back(p);
+    if (err != hipSuccess) { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler allocation failed")); }
   }
   int voice0 = -1;
-  for (int k = 0; k < n; ++k) {
-    int di = -1;
-    const int rc = g->d_voices.push(v, &di);
-    if (rc || (k > 0 && di != voice0 + k)) { release(); return -graph_fail(g, rc ? rc : set_error(PG_ERR_STATE, "pool voices are not contiguous")); }
-    if (k == 0) voice0 = di;
-  }
-  if (graph_env_reserve(g, std::max<size_t>(g->voices.size() + (size_t)n, (size_t)(voice0 + n)))) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
-  (void)hipSetDevice(g->device);
+  { const int rc = sampler_pool_push(g, v, n, &voice0); if (rc) { release(); return -rc; } }
   auto fail_upload = [&]() { release(); return -graph_fail(g, set_error(PG_ERR_DEVICE, "granular sampler upload failed")); };
-  // the slots' grain records: GrainPool::new (granular.rs:384-429) and, with a matrix, create_matrix (voice.rs:341-373) per slot — no note yet
+  // The slots' grain records: GrainPool::new and, with a matrix, create_matrix per slot — no note yet, so no start() and no note_on: the trigger
+  // phase and the playhead stand at 0, speed / volume / panning are neutral until a note's GrainPool::start, and a start time of UINT64_MAX says the
+  // slot is free. Generator 0 of a slot is the pool's, 1 and 2 are its LFOs'.
+  auto slot_rng = [&](int k, int generator, const uint64_t given[4], uint64_t out[4]) {
+    if (gopt->rng_states) memcpy(out, gopt->rng_states + ((size_t)k * 3 + (size_t)generator) * 4, 4 * sizeof(uint64_t));
+    else pg_granular_sampler_rng_state(given, (uint32_t)k, (uint32_t)generator, out);
+  };
   const int grain0 = (int)g->gran_n;
   std::unique_ptr<PgGrainVoice> r(new PgGrainVoice);
   for (int k = 0; k < n; ++k) {
-    memset(r.get(), 0, sizeof(PgGrainVoice));
-    grain_params_to_device(q, r->params);
-    PgGrainPool& pool = r->pool;
-    if (gopt->rng_states) memcpy(pool.rng, gopt->rng_states + ((size_t)k * 3 + 0) * 4, sizeof pool.rng);
-    else pg_granular_sampler_rng_state(q.rng_state, (uint32_t)k, 0, pool.rng);
-    if ((pool.rng[0] | pool.rng[1] | pool.rng[2] | pool.rng[3]) == 0) rng_state_from(pool.rng, pool.rng);
-    pool.trigger_new_grains = 1; pool.trigger_phase = 0.0f;
-    pool.speed = 1.0; pool.volume = 1.0f; pool.panning = 0.0f;
-    pool.playhead = 0.0f; pool.playing_loop_range = 0; pool.primary = -1; pool.overlap_mode = 0;
-    for (int i = 0; i < PG_GRAIN_POOL; ++i) { r->grains[i].volume = 1.0f; r->grains[i].window_mode = 2; }   // Grain::new (:995-1008)
-    r->pcm = sb.d_mono; r->n_frames = (uint64_t)sb.mono_frames; r->staged = (float*)stages[(size_t)k]; r->stage_pos = 0;
-    r->start_time = UINT64_MAX;   // a free slot
-    r->stop_time = UINT64_MAX; r->exhausted_at = UINT64_MAX; r->voice = voice0 + k; r->has_env = 0;
+    uint64_t rng[3][4];
+    slot_rng(k, 0, q.rng_state, rng[0]);
+    grain_rec_init(*r, q, rng[0], /*speed*/ 1.0, /*volume*/ 1.0f, /*panning*/ 0.0f, /*trigger_phase*/ 0.0f, /*playhead*/ 0.0f,
+                   sb.d_mono, (uint64_t)sb.mono_frames, stages[(size_t)k], /*start_time*/ UINT64_MAX, voice0 + k);
     if (gopt->modulation) {
-      const pg_modulation_params* p = gopt->modulation;
-      PgGrainMod& m = r->mod;
-      m.on = 1;
-      for (int l = 0; l < 2; ++l) {
-        PgModLfo& o = m.lfo[l];
-        if (gopt->rng_states) memcpy(o.rng, gopt->rng_states + ((size_t)k * 3 + 1 + (size_t)l) * 4, sizeof o.rng);
-        else pg_granular_sampler_rng_state(p->lfo[l].rng_state, (uint32_t)k, 1 + (uint32_t)l, o.rng);
-        if ((o.rng[0] | o.rng[1] | o.rng[2] | o.rng[3]) == 0) rng_state_from(o.rng, o.rng);
-        o.phase = 0.0f;   // Lfo::new (lfo.rs:70-86) draws its three random values, then the parameter updates in front of the first note
-        o.sample_hold = lfo_random_bipolar(o.rng); o.jitter_current = lfo_random_bipolar(o.rng); o.jitter_target = lfo_random_bipolar(o.rng);
-        o.phase_inc = (float)((double)mod_clamp_rate(p->lfo[l].rate_hz) / (double)g->sample_rate);
-        o.waveform = p->lfo[l].waveform;
-      }
-      for (int s = 0; s < PG_MOD_SOURCES; ++s) for (int t = 0; t < PG_MOD_TARGETS; ++t) {
-        const pg_mod_route& rt = p->routes[s][t];
-        if (fabsf(rt.amount) >= 0.001f) { m.amount[s][t] = rt.amount; m.bipolar[s][t] = rt.bipolar ? 1 : 0; }
-      }
-      m.velocity = 0.0f; m.note_pitch = 60.0f / 127.0f;   // the two static sources before the slot's first note (processor.rs:236-244, :292-298)
+      for (int l = 0; l < 2; ++l) slot_rng(k, 1 + l, gopt->modulation->lfo[l].rng_state, rng[1 + l]);
+      mod_matrix_init(r->mod, *gopt->modulation, g->sample_rate, rng[1], rng[2]);
     }
     const int32_t rec = grain0 + k;
     if (pg_memcpy(g->d_gran + rec, r.get(), sizeof(PgGrainVoice), hipMemcpyHostToDevice) != hipSuccess ||
@@ -1162,9 +1186,7 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
   // the note layer's record; the PgSamplerRec of the same index stays inert (n_voices 0): the unit kernel's sampler_command leaves the commands alone
   std::unique_ptr<PgGSampler> gs(new PgGSampler);
   memset(gs.get(), 0, sizeof(PgGSampler));
-  gs->note.unit = g->mixers[mixer_id].unit_slot; gs->note.voice0 = voice0; gs->note.n_voices = n; gs->note.has_envelope = opt->has_envelope ? 1 : 0; gs->note.transient = opt->transient ? 1 : 0;
-  gs->note.base_volume = 1.0f; gs->note.base_panning = 0.0f; gs->note.pitch_factor = std::pow(2.0, 0.0 / 12.0 + 0.0 / 1200.0);
-  for (int k = 0; k < PG_SAMPLER_MAX_VOICES; ++k) { gs->note.slots[k].release_start_frame = UINT64_MAX; gs->note.slots[k].note = 60; gs->note.slots[k].note_volume = 1.0f; }   // SamplerVoice::new (voice.rs:51-55)
+  note_rec_init(gs->note, g->mixers[mixer_id].unit_slot, voice0, n, opt);
   gs->grain0 = grain0; gs->index = sampler_id; gs->start_time = opt->start_time; gs->span_t0 = UINT64_MAX;
   if (opt->has_envelope) gs->env_params = ahdsr_build_params(opt->envelope, g->sample_rate);   // (every slot's envelope: Idle until its first note_on)
   std::unique_ptr<PgSamplerRec> inert(new PgSamplerRec);
@@ -1173,75 +1195,36 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
   if (pg_memcpy(g->d_gsamp + sampler_id, gs.get(), sizeof(PgGSampler), hipMemcpyHostToDevice) != hipSuccess ||
       pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, inert.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess ||
       samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess || graph_env_head_refresh(g)) return fail_upload();
-  g->samp_stopped[(size_t)sampler_id] = 0;
-  // the last slot goes in first, so that the mixer meets — and sums — the pool in slot order (sampler.rs:989-1006; mixed.rs:324-329)
   HostSampler hs;
-  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
   hs.granular = true; hs.with_mod = gopt->modulation != nullptr; hs.grain0 = grain0;
-  for (int k = n - 1; k >= 0; --k) {
-    HostVoice hv;
-    hv.sbuf = buffer_id; hv.sampler = sampler_id; hv.d_stage = stages[(size_t)k];
-    stages[(size_t)k] = nullptr;   // (the voice owns it from here on)
-    hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
-    g->sample_buffers[buffer_id].use_count += 1;
-    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
-    if (id < 0) { release(); return id; }
-    if (k == 0) hs.voice_id_slot0 = id;
-  }
-  if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
-  g->samplers.push_back(hs);
-  g->n_gsamplers += 1;
-  g->gsamp_dirty = true;
-  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) ||
-      !g->sampler_alive_tab.append((int8_t)(SAMPLER_TAB_GRANULAR | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0) | (gopt->modulation ? SAMPLER_TAB_MATRIX : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
-  return sampler_id;
+  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, hs, SAMPLER_TAB_GRANULAR | (gopt->modulation ? SAMPLER_TAB_MATRIX : 0), &stages);
 }
 int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
   const int pi = find_granular_param(fourcc);
   if (pi < 0) return set_error(PG_ERR_PARAMETER, "Invalid/unknown granular playback parameter 0x%08x", fourcc);
   if (value != value) return set_error(PG_ERR_PARAMETER, "Granular playback parameter '%s' is not a number", GRANULAR_PARAMS[pi].name);
-  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  if (!(g->sampler_alive_tab.get((size_t)sampler_id) & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no granular parameters", sampler_id);
+  const int w = sampler_tab_word(g, sampler_id);
+  if (!w) return sampler_tab_error(g);
+  if (!(w & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no granular parameters", sampler_id);
   float raw;
   if (!resolve_update(GRANULAR_PARAMS[pi], value, is_normalized != 0, raw)) return PG_OK;   // a raw enum index out of range: logged + ignored in the reference (enum.rs:256-290)
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = pgc::CT_SAMPLER_GRAIN_PARAM; m.id = sampler_id; m.param = pi; m.value = raw; m.sample_time = sample_time;
-  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
-  return PG_OK;
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_GRAIN_PARAM, sample_time, pi, raw);
 }
 // ---- what changes every voice of the pool while notes sound: the envelope's knobs, the matrix, the loop range (Sampler::process_playback_messages,
-// sampler.rs:656-731: SetParameter(AMP_* | ML1R | ML2R | ML1W | ML2W), SetModulation, ClearModulation, SamplerMessage::SetLoopRange). Any thread:
-// what a call must know of the sampler stands in sampler_alive_tab / sampler_frames_tab. ----
-// The sampler's SAMPLER_TAB_* word while it takes messages; 0: PG_ERR_PARAMETER (null handle) or PG_ERR_NOT_FOUND is set
-static int sampler_tab_word(pg_graph* g, int sampler_id) {
-  if (!g) { set_error(PG_ERR_PARAMETER, "graph handle is null"); return 0; }
-  if (sampler_id < 0 || (size_t)sampler_id >= g->sampler_alive_tab.size() || !g->sampler_alive_tab.get((size_t)sampler_id)) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return 0; }
-  return g->sampler_alive_tab.get((size_t)sampler_id);
-}
-static int sampler_push(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int param, float value, float value2 = 0.0f) {
-  pgc::CtrlMsg m;
-  memset(&m, 0, sizeof m);
-  m.type = type; m.id = sampler_id; m.param = param; m.value = value; m.value2 = value2; m.sample_time = sample_time;
-  if (!g->ctrl.push(m)) return set_error(PG_ERR_QUEUE_FULL, "mixer's message queue is full");
-  return PG_OK;
-}
+// sampler.rs:656-731: SetParameter(AMP_* | ML1R | ML2R | ML1W | ML2W), SetModulation, ClearModulation, SamplerMessage::SetLoopRange). Any thread. ----
 // ... of a granular sampler with a matrix (the reference: "only available when granular playback is enabled"; a pool without a matrix is this implementation's)
 static int sampler_matrix_message(pg_graph* g, int sampler_id, int type, uint64_t sample_time, int param, float value) {
   const int w = sampler_tab_word(g, sampler_id);
-  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!w) return sampler_tab_error(g);
   if (!(w & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: modulation is only available when granular playback is enabled", sampler_id);
   if (!(w & SAMPLER_TAB_MATRIX)) return set_error(PG_ERR_STATE, "Sampler with id %d has no modulation matrix", sampler_id);
-  return sampler_push(g, sampler_id, type, sample_time, param, value);
+  return sampler_message(g, sampler_id, type, sample_time, param, value);
 }
 int pg_sampler_envelope_param_count(void) { return PG_SE_COUNT; }
 int pg_sampler_envelope_param(int index, pg_param_desc* out) {   // Sampler::envelope_parameters() (sampler.rs:173-181)
   if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
   if (index < 0 || index >= PG_SE_COUNT) return set_error(PG_ERR_NOT_FOUND, "no such parameter");
-  const ParamSpec& p = SAMPLER_ENV_PARAMS[index];
-  out->fourcc = p.fourcc; out->type = p.type; out->min = p.min; out->max = p.max; out->default_value = p.def;
-  out->scaling = p.scaling; out->scaling_arg0 = p.sa; out->scaling_arg1 = p.sb; out->n_values = p.n_values; out->name = p.name;
+  param_desc_from_spec(SAMPLER_ENV_PARAMS[index], out);
   return PG_OK;
 }
 int pg_graph_sampler_set_envelope_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
@@ -1251,9 +1234,9 @@ int pg_graph_sampler_set_envelope_parameter(pg_graph* g, int sampler_id, uint32_
   float raw = 0.0f;
   (void)resolve_update(SAMPLER_ENV_PARAMS[pi], value, is_normalized != 0, raw);   // parameter_update_value (:862-883): clamped, or clamped to 0..=1 and denormalized
   const int w = sampler_tab_word(g, sampler_id);
-  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!w) return sampler_tab_error(g);
   if (!(w & SAMPLER_TAB_ENVELOPE)) return set_error(PG_ERR_PARAMETER, "Invalid or unknown sampler parameter 0x%08x: sampler %d has no envelope", fourcc, sampler_id);   // (:1128-1131, :1189)
-  return sampler_push(g, sampler_id, pgc::CT_SAMPLER_ENV_PARAM, sample_time, pi, raw);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_ENV_PARAM, sample_time, pi, raw);
 }
 int pg_graph_sampler_set_modulation(pg_graph* g, int sampler_id, int source, int target, float amount, int bipolar, uint64_t sample_time) {
   { const int rc = mod_check_route(source, target, amount); if (rc) return rc; }
@@ -1267,8 +1250,7 @@ int pg_graph_sampler_set_lfo_rate(pg_graph* g, int sampler_id, int lfo, float ra
   if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
   if (rate_hz != rate_hz) return set_error(PG_ERR_PARAMETER, "LFO %d rate is not a number", lfo + 1);
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  const float phase_inc = (float)((double)mod_clamp_rate(rate_hz) / (double)g->sample_rate);   // Lfo::set_rate (lfo.rs:102-104)
-  return sampler_matrix_message(g, sampler_id, pgc::CT_SAMPLER_LFO_RATE, sample_time, lfo, phase_inc);
+  return sampler_matrix_message(g, sampler_id, pgc::CT_SAMPLER_LFO_RATE, sample_time, lfo, mod_phase_inc(rate_hz, g->sample_rate));
 }
 int pg_graph_sampler_set_lfo_waveform(pg_graph* g, int sampler_id, int lfo, int waveform, uint64_t sample_time) {
   if (lfo < 0 || lfo > 1) return set_error(PG_ERR_PARAMETER, "Invalid LFO index: %d", lfo);
@@ -1278,21 +1260,21 @@ int pg_graph_sampler_set_lfo_waveform(pg_graph* g, int sampler_id, int lfo, int 
 int pg_graph_sampler_set_loop_range(pg_graph* g, int sampler_id, int has_loop_range, uint64_t loop_start, uint64_t loop_end, uint64_t sample_time) {
   if (has_loop_range && loop_start >= loop_end) return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu", (unsigned long long)loop_start, (unsigned long long)loop_end);
   const int w = sampler_tab_word(g, sampler_id);
-  if (!w) return g ? PG_ERR_NOT_FOUND : PG_ERR_PARAMETER;
+  if (!w) return sampler_tab_error(g);
   if (!(w & SAMPLER_TAB_GRANULAR)) return set_error(PG_ERR_STATE, "Sampler with id %d plays files: its loop range is set when it is created", sampler_id);
   const uint64_t frames = g->sampler_frames_tab.get((size_t)sampler_id);
   if (has_loop_range && (loop_start >= frames || loop_end > frames))   // (:1251-1269)
     return set_error(PG_ERR_PARAMETER, "Invalid loop range: %llu..%llu not in range 0..%llu", (unsigned long long)loop_start, (unsigned long long)loop_end, (unsigned long long)frames);
   // SamplerVoice::set_loop_range (voice.rs:329-338): source frames over the FILE's frame count, as f32 — as at creation. None is no loop at all.
   const float total = (float)frames;
-  return sampler_push(g, sampler_id, pgc::CT_SAMPLER_GRAIN_LOOP, sample_time, has_loop_range ? 1 : 0, has_loop_range ? (float)loop_start / total : 0.0f, has_loop_range ? (float)loop_end / total : 0.0f);
+  return sampler_message(g, sampler_id, pgc::CT_SAMPLER_GRAIN_LOOP, sample_time, has_loop_range ? 1 : 0, has_loop_range ? (float)loop_start / total : 0.0f, has_loop_range ? (float)loop_end / total : 0.0f);
 }
 int pg_graph_sampler_envelope_params(pg_graph* g, int sampler_id, int slot, pg_sampler_envelope_state* out) {
   if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
-    return set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  const HostSampler& hs = g->samplers[sampler_id];
+  const HostSampler* found = sampler_for_readback(g, sampler_id);
+  if (!found) return PG_ERR_NOT_FOUND;
+  const HostSampler& hs = *found;
   if (slot < 0 || slot >= hs.n_voices) return set_error(PG_ERR_PARAMETER, "Invalid slot: %d. The sampler has %d", slot, hs.n_voices);
   if (!hs.has_envelope) return set_error(PG_ERR_STATE, "Sampler with id %d has no envelope", sampler_id);
   PgEnvParams p;
@@ -1311,9 +1293,9 @@ int pg_graph_sampler_envelope_params(pg_graph* g, int sampler_id, int slot, pg_s
 static int gsampler_slot_record(pg_graph* g, int sampler_id, int slot, const void* out, bool need_mod) {
   if (!out) return -set_error(PG_ERR_PARAMETER, "output is null");
   if (!g) return -set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || (!g->samplers[sampler_id].alive && !(g->samplers[sampler_id].transient && g->samp_stopped[(size_t)sampler_id] != 0)))
-    return -set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id);
-  const HostSampler& hs = g->samplers[sampler_id];
+  const HostSampler* found = sampler_for_readback(g, sampler_id);
+  if (!found) return -PG_ERR_NOT_FOUND;
+  const HostSampler& hs = *found;
   if (!hs.granular) return -set_error(PG_ERR_STATE, "Sampler with id %d plays files: it has no grain pools", sampler_id);
   if (slot < 0 || slot >= hs.n_voices) return -set_error(PG_ERR_PARAMETER, "Invalid slot: %d. The sampler has %d", slot, hs.n_voices);
   if (need_mod && !hs.with_mod) return -set_error(PG_ERR_STATE, "Sampler with id %d has no modulation matrix", sampler_id);
