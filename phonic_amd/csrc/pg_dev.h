@@ -265,7 +265,7 @@ struct PgEnvTable {
 };
 static_assert(sizeof(PgEnv) == 64 && sizeof(PgEnvTable) == 64, "the entries follow the header, 16-byte aligned");
 
-// ---- the Sampler's note layer (pg_graph_add_sampler; pg_sampler_dev.h): notes, voice allocation and stealing (src/generator/sampler.rs) ----
+// ---- the Sampler's note layer (pg_graph_add_sampler; pg_note_dev.h, pg_sampler_dev.h): notes, voice allocation and stealing (src/generator/sampler.rs) ----
 // A sampler is a pool of n_voices file voices (ordinary PgVoice records, device indices voice0 .. voice0 + n_voices - 1, + a PgEnv each when it has
 // an envelope) in ONE sub-mixer unit: the exact kernel's workgroup of that unit applies the sampler's commands in front of their frames, from the
 // state its source stage left in the pool's voices. Slot i is ACTIVE (SamplerVoice::is_active, voice.rs:100-102) iff its voice is `active` and
@@ -546,9 +546,9 @@ enum PgCmdType {
   // kernels ignore them):
   CMD_VOICE_GRAIN_PARAM = 15,   // value = the raw value (an enum's index as a float), value64 = index in Sampler::granular_parameters() order   (Sampler::set_granular_parameter)
   CMD_VOICE_GRAIN_LOOP = 16,    // value = loop_start, value64 = has_loop | f32 bits of loop_end << 32                          (GrainPool::set_loop_range)
-  // the messages of a sampler (target = index of its PgSamplerRec; pg_sampler_dev.h applies them in pg_unit_kernel, in front of `frame`). A note id
+  // the messages of a sampler (target = index of its PgSamplerRec; pg_note_dev.h applies them, for a file sampler in pg_unit_kernel, in front of `frame`). A note id
   // travels in `param`: the host hands out ids below 2^31.
-  CMD_SAMPLER_NOTE_ON = 17,       // param = note id, value = volume, value64 = note | f32 bits of panning << 32                (Sampler::trigger_note_on)
+  CMD_SAMPLER_NOTE_ON = 17,       // param = note id, value = volume, value64 = pg_note_on_pack(note, panning)                  (Sampler::trigger_note_on)
   CMD_SAMPLER_NOTE_OFF = 18,      // param = note id                                                                            (trigger_note_off)
   CMD_SAMPLER_ALL_NOTES_OFF = 19, //                                                                                            (trigger_all_notes_off)
   CMD_SAMPLER_NOTE_SPEED = 20,    // param = note id, value = glide (semitones/s, <= 0: none), value64 = f64 bits of the speed  (trigger_set_speed)
@@ -578,6 +578,19 @@ struct PgCmd {
   float value;
   uint64_t value64;
 };
+#ifdef __HIP__
+#define PG_HD __host__ __device__
+#else
+#define PG_HD
+#endif
+// A sampler's message: every CMD_SAMPLER_* (the host retires them with their sampler, pg_gsampler_kernel filters its command list by it) ...
+PG_HD inline bool pg_cmd_is_sampler_message(int type) { return type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_GRAIN_LOOP; }
+// ... and the ones pg_unit_kernel's note layer applies to a file sampler: the granular-only ones are not among them
+PG_HD inline bool pg_cmd_is_unit_note_message(int type) { return (type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_STOP) || type == CMD_SAMPLER_ENV_PARAM; }
+// CMD_SAMPLER_NOTE_ON's value64: note | f32 bits of panning << 32
+PG_HD inline uint64_t pg_note_on_pack(int note, float panning) { uint32_t pan; __builtin_memcpy(&pan, &panning, 4); return (uint64_t)(note & 0xff) | ((uint64_t)pan << 32); }
+PG_HD inline int pg_note_on_note(uint64_t value64) { return (int)(value64 & 0xff); }
+PG_HD inline float pg_note_on_panning(uint64_t value64) { const uint32_t pan = (uint32_t)(value64 >> 32); float panning; __builtin_memcpy(&panning, &pan, 4); return panning; }
 
 // A round's command list as a kernel argument of the decision-scan kernel (rounds of at most PG_CMD_PACK commands: nearly all of them): the scan
 // reads its commands from here and leaves them in the device ring for the kernels behind it — no copy kernel in front of the round (5-6 us on

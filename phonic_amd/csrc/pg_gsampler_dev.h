@@ -1,4 +1,4 @@
-// The note layer of a granular-mode Sampler (Sampler::with_granular_playback, src/generator/sampler.rs:598-637) on the device: what
+// A granular-mode Sampler (Sampler::with_granular_playback, src/generator/sampler.rs:598-637) under the note layer (pg_note_dev.h) on the device: what
 // Sampler::write does around its voices' grain pools (sampler.rs:656-731, :974-1028; src/generator/sampler/voice.rs:122-310, :469-502), cut into
 // the two halves pg_gsampler_kernel (pg_k_gsampler.hip) runs between the grain launches of consecutive Sampler::write spans:
 //   gs_close   the end of SamplerVoice::process for every slot that was active over the span that ends — the AHDSR envelope over the span's staged
@@ -10,7 +10,7 @@
 // One workgroup per sampler. Decisions take one lane per slot (wave 0); a record is changed by one lane (or one lane per slot / per grain) and
 // read again only behind a barrier.
 #pragma once
-#include "pg_sampler_dev.h"   // ahdsr_note_on, sampler_clamp_pan; through pg_source_dev.h: ahdsr_sequence, ahdsr_scaled, ahdsr_note_off
+#include "pg_note_dev.h"      // note_alloc, note_slot_start, note_message, note_end_of_write; pg_source_dev.h: ahdsr_*
 #include "pg_grain_dev.h"     // mod_lfo_reset, grain_set_parameter
 
 namespace pgd {
@@ -29,7 +29,6 @@ struct GsShared {
   int32_t result;
 };
 
-DEVO bool gs_cmd_is_message(int type) { return (type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_STOP) || (type >= CMD_SAMPLER_GRAIN_PARAM && type <= CMD_SAMPLER_GRAIN_LOOP); }
 DEVO PgGrainVoice* gs_grain(const PgGSamplerLaunch& L, const PgGSampler& r, int slot) { return L.grains + r.grain0 + slot; }
 // The record as the host describes it lies inside the tables: anything else is left alone
 DEVO bool gs_pool_ok(const PgGSamplerLaunch& L, const PgGSampler& r) {
@@ -43,35 +42,35 @@ DEVO void gs_pool_reset(PgGrainVoice* V) {
   if (threadIdx.x == 0) { V->pool.primary = -1; V->pool.trigger_new_grains = 1; V->exhausted_at = PG_USIZE_MAX; V->stop_time = PG_USIZE_MAX; }
 }
 
-// Sampler::next_free_voice_index (sampler.rs:826-860) with one lane per slot, as sampler_alloc (pg_sampler_dev.h) has it for file voices: the first
-// slot that is not active; else — only with an envelope — the slot in Release with the smallest release_start_frame; else the active slot with the
-// smallest note id; ties go to the lower slot. Every lane of the workgroup calls and gets the result.
-DEVO int gs_alloc(const PgGSampler& r, GsShared& S) {
-  if (threadIdx.x < 64) {
-    const int lane = (int)threadIdx.x, n = r.note.n_voices;
-    const bool mine = lane < n;
-    bool active = false, releasing = false;
-    if (mine) {
-      active = r.active[lane] != 0;
-      releasing = active && r.note.has_envelope && r.env[lane].stage == PG_AHDSR_RELEASE && r.note.slots[lane].release_start_frame != PG_USIZE_MAX;
-    }
-    int slot;
-    const unsigned long long free_mask = __ballot(mine && !active);
-    if (free_mask) slot = __ffsll((long long)free_mask) - 1;
-    else {
-      const bool any_releasing = __ballot(releasing) != 0ull;
-      unsigned long long key = PG_USIZE_MAX;
-      if (mine && (any_releasing ? releasing : true)) key = any_releasing ? r.note.slots[lane].release_start_frame : r.note.slots[lane].note_id;
-      slot = mine ? lane : 64;
-      for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long ok = __shfl_xor(key, off, 64);
-        const int os = __shfl_xor(slot, off, 64);
-        if (ok < key || (ok == key && os < slot)) { key = ok; slot = os; }
-      }
-      if (slot >= n) slot = 0;
-    }
-    if (lane == 0) S.result = slot;
+// The note layer's view of the pool (pg_note_dev.h): slot i is grain record grain0 + i; its envelope and whether it plays are the sampler record's
+struct GrainPools {
+  const PgGSamplerLaunch& L;
+  PgGSampler& r;
+  DEVO PgSamplerRec& rec() const { return r.note; }
+  DEVO bool active(int i) const { return r.active[i] != 0; }
+  DEVO bool releasing(int i) const { return r.note.has_envelope && r.env[i].stage == PG_AHDSR_RELEASE; }
+  // SamplerVoice::stop (voice.rs:196-219): an active slot only; with an envelope note_off alone — the pool goes on triggering — without one
+  // GrainPool::stop (the file source behind the voice is never written in this mode: its stop() starts a fade that never runs, and it is
+  // never exhausted).
+  DEVO void stop(int i, uint64_t now) const {
+    if (r.active[i] == 0) return;
+    r.note.slots[i].release_start_frame = now;
+    if (r.note.has_envelope) { PgEnvState st = r.env[i]; ahdsr_note_off(st, r.env_params); r.env[i] = st; }
+    else gs_grain(L, r, i)->pool.trigger_new_grains = 0;
   }
+  // GrainPool::start / set_speed / set_volume / set_panning set the values directly: a pool has no smoothers and gets the speed without the glide
+  DEVO void set_speed(int i, double speed, float) const { gs_grain(L, r, i)->pool.speed = speed; }
+  DEVO void set_volume(int i, float v) const { gs_grain(L, r, i)->pool.volume = v; }
+  DEVO void set_panning(int i, float p) const { gs_grain(L, r, i)->pool.panning = p; }
+  DEVO void env_param(const PgCmd& cmd) const {   // gs_close reads the parameters once per span
+    if (r.note.has_envelope) { PgEnvParams p = r.env_params; ahdsr_set_param(p, cmd); r.env_params = p; }
+  }
+  DEVO double note_speed(int note) const { return L.speed_tab[note & 255]; }
+};
+
+// Sampler::next_free_voice_index with one lane per slot of wave 0 (note_alloc). Every lane of the workgroup calls and gets the result.
+DEVO int gs_alloc(const GrainPools& pool, GsShared& S) {
+  if (threadIdx.x < 64) { const int slot = note_alloc(pool); if (threadIdx.x == 0) S.result = slot; }
   __syncthreads();
   const int slot = S.result;
   __syncthreads();
@@ -79,110 +78,58 @@ DEVO int gs_alloc(const PgGSampler& r, GsShared& S) {
 }
 
 // SamplerVoice::start for a granular voice (voice.rs:122-193), every lane of the workgroup: reset() resets the pool only if the slot was active
-// (:222-236); GrainPool::start (granular.rs:474-489) sets its values directly — a pool has no smoothers; AhdsrEnvelope::note_on(params, 1.0);
+// (:222-236); GrainPool::start (granular.rs:474-489) sets its values directly; AhdsrEnvelope::note_on(params, 1.0);
 // ModulationMatrix::note_on(note, volume) (matrix.rs:394-408): both LFOs as Lfo::reset leaves them, velocity = the NOTE's volume, keytracking =
 // note / 127. The slot's three generators carry on where they are.
-DEVO void gs_voice_start(const PgGSamplerLaunch& L, PgGSampler& r, int slot, const PgCmd& cmd, uint64_t now) {
-  PgGrainVoice* const V = gs_grain(L, r, slot);
+DEVO void gs_voice_start(const GrainPools& pool, int slot, const PgCmd& cmd, uint64_t now) {
+  PgGSampler& r = pool.r;
+  PgGrainVoice* const V = gs_grain(pool.L, r, slot);
   if (r.active[slot] != 0) gs_pool_reset(V);
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int note = (int)(cmd.value64 & 0xff);
-    const float volume = cmd.value, panning = __uint_as_float((uint32_t)(cmd.value64 >> 32));
-    PgSamplerSlot& s = r.note.slots[slot];
-    s.note_id = (uint64_t)cmd.param; s.note = note; s.note_volume = volume; s.note_panning = panning; s.release_start_frame = PG_USIZE_MAX;
+    note_slot_start(pool, slot, cmd);
     PgGrainPool& P = V->pool;
     P.trigger_new_grains = 1; P.trigger_phase = 1.0f;
-    P.speed = L.speed_tab[note & 255] * r.note.pitch_factor;
-    P.volume = r.note.base_volume * volume;
-    P.panning = sampler_clamp_pan(r.note.base_panning + panning);
     P.playhead = V->params.position; P.playing_loop_range = 0;
     V->start_time = now; V->stop_time = PG_USIZE_MAX; V->exhausted_at = PG_USIZE_MAX;
     if (r.note.has_envelope) { PgEnvState st = r.env[slot]; ahdsr_note_on(st, r.env_params, 1.0f); r.env[slot] = st; }
     if (V->mod.on) {
       for (int l = 0; l < 2; ++l) { PgModLfo m = V->mod.lfo[l]; mod_lfo_reset(m); V->mod.lfo[l] = m; }
-      V->mod.velocity = volume;
-      V->mod.note_pitch = (float)note / 127.0f;
+      V->mod.velocity = cmd.value;
+      V->mod.note_pitch = (float)pg_note_on_note(cmd.value64) / 127.0f;
     }
     r.active[slot] = 1;
   }
   __syncthreads();
-}
-// SamplerVoice::stop (voice.rs:196-219) on one lane: an active slot only; with an envelope note_off alone — the pool goes on triggering — without
-// one GrainPool::stop (the file source behind the voice is never written in this mode: its stop() starts a fade that never runs, and it is
-// never exhausted).
-DEVO void gs_voice_stop(const PgGSamplerLaunch& L, PgGSampler& r, int slot, uint64_t now) {
-  if (r.active[slot] == 0) return;
-  r.note.slots[slot].release_start_frame = now;
-  if (r.note.has_envelope) { PgEnvState st = r.env[slot]; ahdsr_note_off(st, r.env_params); r.env[slot] = st; }
-  else gs_grain(L, r, slot)->pool.trigger_new_grains = 0;
-}
-// The first slot in index order that plays note `note_id` (sampler.rs:776-822), -1: none
-DEVO int gs_find(const PgGSampler& r, int note_id) {
-  for (int i = 0; i < r.note.n_voices; ++i) if (r.active[i] != 0 && r.note.slots[i].note_id == (uint64_t)note_id) return i;
-  return -1;
 }
 
 // process_playback_messages (sampler.rs:656-731) in front of frame L.t: the sampler's commands of that frame, in list order. Every lane of the
 // workgroup walks the list; a barrier stands behind every command.
 DEVO void gs_open(const PgGSamplerLaunch& L, PgGSampler& r, GsShared& S) {
   const int tid = (int)threadIdx.x, n = r.note.n_voices;
-  const uint64_t now = L.t;
+  const GrainPools pool{L, r};
   for (int ci = 0; ci < L.n_cmds; ++ci) {
     const PgCmd cmd = L.cmds[ci];
-    if (cmd.unit != r.note.unit || cmd.frame != L.frame || cmd.target != r.index || !gs_cmd_is_message(cmd.type)) continue;
-    if (cmd.type == CMD_SAMPLER_STOP) {   // Sampler::stop (:733-738): taken also while stopping
-      if (tid == 0) { r.note.stopping = r.note.transient; for (int i = 0; i < n; ++i) gs_voice_stop(L, r, i, now); }
-      __syncthreads();
-      continue;
-    }
-    if (r.note.stopping) continue;   // every trigger is dropped while the sampler stops (:663-664)
+    if (cmd.unit != r.note.unit || cmd.frame != L.frame || cmd.target != r.index || !pg_cmd_is_sampler_message(cmd.type)) continue;
+    if (note_dropped(r.note, cmd)) continue;   // (by every lane: no barrier behind a dropped message)
     if (cmd.type == CMD_SAMPLER_NOTE_ON) {
-      const int slot = gs_alloc(r, S);
-      gs_voice_start(L, r, slot, cmd, now);
+      const int slot = gs_alloc(pool, S);
+      gs_voice_start(pool, slot, cmd, L.t);
       continue;
     }
-    if (cmd.type == CMD_SAMPLER_GRAIN_PARAM) {   // Sampler::set_granular_parameter (:299-360): the sampler's ONE parameter set — here every slot's copy of it
-      if (tid < n) { PgGrainParams p = gs_grain(L, r, tid)->params; grain_set_parameter(p, (uint32_t)cmd.param, cmd.value); gs_grain(L, r, tid)->params = p; }
-    } else if (cmd.type == CMD_SAMPLER_MOD_ROUTE || cmd.type == CMD_SAMPLER_LFO_RATE || cmd.type == CMD_SAMPLER_LFO_WAVEFORM) {
-      // SetModulation / ClearModulation, ML1R / ML2R / ML1W / ML2W (:704-720, :1148-1186, :1210-1244): the matrix of EVERY voice, playing or free. The LFOs
-      // draw nothing and keep their phases; a later note's reset keeps what is written here.
-      if (tid < n) {
-        PgGrainMod& m = gs_grain(L, r, tid)->mod;
-        if (m.on) {
-          if (cmd.type == CMD_SAMPLER_MOD_ROUTE) grain_route_apply(cmd, m.amount, m.bipolar);
-          else for (int l = 0; l < 2; ++l) grain_lfo_apply(cmd, cmd.type == CMD_SAMPLER_LFO_RATE, l, m.lfo[l]);
-        }
-      }
-    } else if (cmd.type == CMD_SAMPLER_GRAIN_LOOP) {   // SamplerMessage::SetLoopRange (:1246-1271, voice.rs:312-339): every voice's pool
-      if (tid < n) { PgGrainParams p = gs_grain(L, r, tid)->params; grain_loop_apply(cmd, p); gs_grain(L, r, tid)->params = p; }
-    } else if (cmd.type == CMD_SAMPLER_ENV_PARAM) {   // set_envelope_parameter (:184-217, :1122-1131): the pool's one AhdsrParameters; gs_close reads it once per span
-      if (tid == 0 && r.note.has_envelope) { PgEnvParams p = r.env_params; ahdsr_set_param(p, cmd); r.env_params = p; }
-    } else if (tid == 0) {
-      if (cmd.type == CMD_SAMPLER_ALL_NOTES_OFF) {
-        for (int i = 0; i < n; ++i) gs_voice_stop(L, r, i, now);
-      } else if (cmd.type == CMD_SAMPLER_PARAM) {   // process_parameter_update (:1076-1120): the stored base value, then every ACTIVE voice's pool, directly
-        if (cmd.param == PG_SP_TRANSPOSE || cmd.param == PG_SP_FINETUNE) {
-          if (cmd.param == PG_SP_TRANSPOSE) r.note.transpose = (int)cmd.value; else r.note.finetune = (int)cmd.value;
-          r.note.pitch_factor = __longlong_as_double((long long)cmd.value64);
-        } else if (cmd.param == PG_SP_VOLUME) r.note.base_volume = cmd.value;
-        else if (cmd.param == PG_SP_PANNING) r.note.base_panning = cmd.value;
-        for (int i = 0; i < n; ++i) {
-          if (r.active[i] == 0) continue;
-          PgGrainPool& P = gs_grain(L, r, i)->pool;
-          if (cmd.param == PG_SP_TRANSPOSE || cmd.param == PG_SP_FINETUNE) P.speed = L.speed_tab[r.note.slots[i].note & 255] * r.note.pitch_factor;
-          else if (cmd.param == PG_SP_VOLUME) P.volume = r.note.base_volume * r.note.slots[i].note_volume;
-          else if (cmd.param == PG_SP_PANNING) P.panning = sampler_clamp_pan(r.note.base_panning + r.note.slots[i].note_panning);
-        }
-      } else {
-        const int i = gs_find(r, cmd.param);
-        if (i >= 0) {   // (an unknown or ended note: ignored)
-          PgGrainPool& P = gs_grain(L, r, i)->pool;
-          if (cmd.type == CMD_SAMPLER_NOTE_OFF) gs_voice_stop(L, r, i, now);
-          else if (cmd.type == CMD_SAMPLER_NOTE_SPEED) P.speed = __longlong_as_double((long long)cmd.value64) * r.note.pitch_factor;   // (no glide: the pool gets the speed alone)
-          else if (cmd.type == CMD_SAMPLER_NOTE_VOLUME) { r.note.slots[i].note_volume = cmd.value; P.volume = r.note.base_volume * cmd.value; }
-          else if (cmd.type == CMD_SAMPLER_NOTE_PAN) { r.note.slots[i].note_panning = cmd.value; P.panning = sampler_clamp_pan(r.note.base_panning + cmd.value); }
-        }
+    // the note layer's messages run on one lane; the granular-only ones change every slot's record, playing or free, one lane per slot
+    if (cmd.type < CMD_SAMPLER_GRAIN_PARAM || cmd.type == CMD_SAMPLER_ENV_PARAM) { if (tid == 0) note_message(pool, cmd, L.t); }
+    else if (tid < n) {
+      PgGrainVoice& V = *gs_grain(L, r, tid);
+      if (cmd.type == CMD_SAMPLER_GRAIN_PARAM) {   // Sampler::set_granular_parameter (:299-360): the sampler's ONE parameter set — here every slot's copy of it
+        PgGrainParams p = V.params; grain_set_parameter(p, (uint32_t)cmd.param, cmd.value); V.params = p;
+      } else if (cmd.type == CMD_SAMPLER_GRAIN_LOOP) {   // SamplerMessage::SetLoopRange (:1246-1271, voice.rs:312-339): every voice's pool
+        PgGrainParams p = V.params; grain_loop_apply(cmd, p); V.params = p;
+      } else if (V.mod.on) {
+        // SetModulation / ClearModulation, ML1R / ML2R / ML1W / ML2W (:704-720, :1148-1186, :1210-1244): the matrix of EVERY voice. The LFOs
+        // draw nothing and keep their phases; a later note's reset keeps what is written here.
+        if (cmd.type == CMD_SAMPLER_MOD_ROUTE) grain_route_apply(cmd, V.mod.amount, V.mod.bipolar);
+        else for (int l = 0; l < 2; ++l) grain_lfo_apply(cmd, cmd.type == CMD_SAMPLER_LFO_RATE, l, V.mod.lfo[l]);
       }
     }
     __syncthreads();
@@ -254,11 +201,7 @@ DEVO void gs_close(const PgGSamplerLaunch& L, PgGSampler& r, uint64_t t0, uint64
   }
   __syncthreads();
   // 4. the end of Sampler::write (sampler.rs:1008-1024): a sampler that was told to stop and has no active slot left is stopped
-  if (tid == 0 && r.note.stopping && !r.note.stopped) {
-    int active = 0;
-    for (int s = 0; s < n; ++s) active += r.active[s] != 0 ? 1 : 0;
-    if (active == 0) { r.note.stopped = 1; *(volatile int32_t*)(L.stopped + r.index) = 1; __threadfence_system(); }
-  }
+  if (tid == 0 && r.note.stopping && !r.note.stopped) note_end_of_write(GrainPools{L, r}, L.stopped + r.index);
   __syncthreads();
 }
 

@@ -654,7 +654,6 @@ static HostSampler* sampler_find(pg_graph* g, int sampler_id) {   // owner threa
   if (sampler_id < 0 || sampler_id >= (int)g->samplers.size() || !g->samplers[sampler_id].alive) { set_error(PG_ERR_NOT_FOUND, "Sampler with id %d not found", sampler_id); return nullptr; }
   return &g->samplers[sampler_id];
 }
-static bool cmd_is_sampler_event(int cmd_type) { return (cmd_type >= CMD_SAMPLER_NOTE_ON && cmd_type <= CMD_SAMPLER_STOP) || (cmd_type >= CMD_SAMPLER_GRAIN_PARAM && cmd_type <= CMD_SAMPLER_GRAIN_LOOP); }
 // The pool leaves its mixer (RemoveSource, a mixer that drops an exhausted generator: mixed.rs:612-616): its voices are retired like removed
 // sources — their buffer references return when their memory is released — and what is still queued for it finds no source when it comes due
 static void sampler_retire(pg_graph* g, int sampler_id) {
@@ -667,7 +666,7 @@ static void sampler_retire(pg_graph* g, int sampler_id) {
     g->voices[v].mixer = -1;
     g->retired_voices.push_back(v);
   }
-  for (Event& e : mx.events) if (cmd_is_sampler_event(e.cmd.type) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
+  for (Event& e : mx.events) if (pg_cmd_is_sampler_message(e.cmd.type) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
   hs.alive = false;
   if (hs.granular) g->gsamp_dirty = true;
   g->sampler_alive_tab.set((size_t)sampler_id, 0);
@@ -719,7 +718,7 @@ static hipError_t samp_head_upload(const pg_graph* g, size_t n) {
 // (pg_dev.h: PgCmdType). The ONE list of them: sampler_drain_message builds the events from it.
 struct SamplerEvent { int32_t msg, cmd; void (*fill)(const pgc::CtrlMsg& m, PgCmd& c); };
 static const SamplerEvent SAMPLER_EVENTS[] = {
-  {pgc::CT_SAMPLER_NOTE_ON, CMD_SAMPLER_NOTE_ON, [](const pgc::CtrlMsg& m, PgCmd& c) { uint32_t pan; memcpy(&pan, &m.value2, 4); c.param = m.param; c.value = m.value; c.value64 = (uint64_t)((int)m.dvalue & 0xff) | ((uint64_t)pan << 32); }},
+  {pgc::CT_SAMPLER_NOTE_ON, CMD_SAMPLER_NOTE_ON, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; c.value64 = pg_note_on_pack((int)m.dvalue, m.value2); }},
   {pgc::CT_SAMPLER_NOTE_OFF, CMD_SAMPLER_NOTE_OFF, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; }},
   {pgc::CT_SAMPLER_ALL_NOTES_OFF, CMD_SAMPLER_ALL_NOTES_OFF, [](const pgc::CtrlMsg&, PgCmd&) {}},
   {pgc::CT_SAMPLER_NOTE_SPEED, CMD_SAMPLER_NOTE_SPEED, [](const pgc::CtrlMsg& m, PgCmd& c) { c.param = m.param; c.value = m.value; memcpy(&c.value64, &m.dvalue, 8); }},

@@ -976,6 +976,27 @@ DEVO void ahdsr_sequence(PgEnvState& st, const PgEnvParams& p, float* dst, int n
   }
   st.stage = stage; st.output = out; st.target_volume = tv; st.hold_samples_remaining = hold;
 }
+// AhdsrEnvelope::note_on (ahdsr.rs:402-419)
+DEVO void ahdsr_note_on(PgEnvState& st, const PgEnvParams& p, float volume) {
+  st.target_volume = volume;
+  if (p.attack_rate == 3.402823466e+38f) {
+    st.output = volume;
+    if (!(p.zero_times & PG_AHDSR_HOLD_ZERO)) { st.stage = PG_AHDSR_HOLD; st.hold_samples_remaining = p.hold_samples; }
+    else st.stage = PG_AHDSR_DECAY;
+  } else { st.output = 0.0f; st.stage = PG_AHDSR_ATTACK; }
+}
+// AhdsrParameters::set_attack_time / set_hold_time / set_decay_time / set_sustain_level / set_release_time (ahdsr.rs:143-249) as the host has
+// resolved them in time order (pg_sampler.hip: sampler_stage_command): the one field the setter writes, and which of the times are zero now.
+// Nothing of a running envelope's state changes: a Hold in progress keeps its hold_samples_remaining.
+DEVO void ahdsr_set_param(PgEnvParams& p, const PgCmd& cmd) {
+  if (cmd.param == PG_SE_ATTACK) p.attack_rate = cmd.value;
+  else if (cmd.param == PG_SE_HOLD) p.hold_samples = cmd.value;
+  else if (cmd.param == PG_SE_DECAY) p.decay_rate = cmd.value;
+  else if (cmd.param == PG_SE_SUSTAIN) p.sustain_level = cmd.value;
+  else if (cmd.param == PG_SE_RELEASE) p.release_rate = cmd.value;
+  else return;
+  p.zero_times = (int32_t)(cmd.value64 & (PG_AHDSR_HOLD_ZERO | PG_AHDSR_DECAY_ZERO | PG_AHDSR_RELEASE_ZERO));
+}
 // AhdsrEnvelope::note_off (ahdsr.rs:422-436)
 DEVO void ahdsr_note_off(PgEnvState& st, const PgEnvParams& p) {
   if (!(p.zero_times & PG_AHDSR_RELEASE_ZERO)) {

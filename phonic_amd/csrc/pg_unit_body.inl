@@ -550,8 +550,8 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
       }
       int flush = 0;
       __syncthreads();
-      if (!FAST_ONLY && ((cmd.type >= CMD_SAMPLER_NOTE_ON && cmd.type <= CMD_SAMPLER_STOP) || cmd.type == CMD_SAMPLER_ENV_PARAM)) {
-        // a sampler's message (pg_sampler_dev.h): wave 0, one lane per slot of the pool where a voice is allocated
+      if (!FAST_ONLY && pg_cmd_is_unit_note_message(cmd.type)) {
+        // a sampler's message (pg_note_dev.h under pg_sampler_dev.h's pool): wave 0, one lane per slot of the pool where a voice is allocated
         if (tid == 0) ctl[2] = 0;
         if (tid < 64) sampler_command(L, cmd, pos0 + (uint64_t)frame0);
       } else if (tid == 0) {

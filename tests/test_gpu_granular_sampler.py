@@ -91,11 +91,11 @@ def test_note_placement_inside_pieces_and_on_edges():
 
 # ---- 3: stealing ----
 @pytest.mark.parametrize("envelope", [False, True], ids=["no_envelope", "envelope"])
-@pytest.mark.parametrize("voice_count", [1, 2, 3, 8, 33])
+@pytest.mark.parametrize("voice_count", [1, 2, 3, 8, 33, 64])
 def test_stealing(voice_count, envelope):
     """The pool is filled, then more notes come than it has slots: without an envelope the oldest id goes; with one, the earliest release, ties to the
     lower slot (two notes released on one frame). Then everything is released and runs out, and one more note takes slot 0: its third note, so
-    the generator the slot carries from note to note shows. With 33 slots the decision lies beyond lane 31."""
+    the generator the slot carries from note to note shows. With 33 slots the decision lies beyond lane 31; with 64 every lane of the wave holds a slot (no lane carries the "no slot" index 64)."""
     n = voice_count
     g, r = _single(n, envelope=R.ENV if envelope else None)
     for k in range(n):
