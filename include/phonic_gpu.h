@@ -597,10 +597,11 @@ int pg_graph_voice_modulation_state(pg_graph* g, int voice_id, pg_modulation_sta
  * A unit that holds a sampler is rendered by the exact kernel for as long as the sampler lives.
  * The sharded handle has NO sampler entry points yet (tests/test_host_sharded_routing.py counts the header's handle-taking pg_sharded_* functions
  * against its fixed program): they follow in a change that may touch that program.
- * OUT OF SCOPE: samplers on the main mixer (its sources are one unit, one workgroup, each; the pool needs one workgroup that sees every slot — a
- * multi-voice source unit is the follow-up); the AMP_* envelope ids through pg_graph_sampler_set_parameter (they have a call and a table of
- * their own: pg_graph_sampler_set_envelope_parameter, below); SetLoopRange on a file sampler while it plays; playback status events of sampler
- * voices and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning (identity at their defaults, smoothing.rs:60-71, :98-101).
+ * OUT OF SCOPE: the main mixer through THIS entry point (a sampler there is one source unit that holds the whole pool, behind the generator's
+ * output stage: pg_graph_add_sampler_to_main, below); the AMP_* envelope ids through pg_graph_sampler_set_parameter (they have a call and a table
+ * of their own: pg_graph_sampler_set_envelope_parameter, below); SetLoopRange on a file sampler while it plays; playback status events of sampler
+ * voices and the sampler's own Stopped event; GeneratorPlaybackOptions::volume / panning for a sampler in a sub-mixer (identity at their defaults,
+ * smoothing.rs:60-71, :98-101; with other values: pg_graph_add_sampler_to_main).
  * (Granular-mode samplers, Sampler::with_granular_playback: pg_graph_add_granular_sampler, below.) */
 #define PG_SAMPLER_MAX_VOICES 64
 typedef struct pg_sampler_options {
@@ -709,12 +710,14 @@ int pg_graph_sampler_state(pg_graph* g, int sampler_id, pg_sampler_state* out);
  *   pg_graph_sampler_envelope_params   debug read-back (waits for the graph's work): the AhdsrParameters as the device holds them — for a file
  *       sampler slot `slot`'s own copy, for a granular one the sampler's one set (`slot` must still name a slot: PG_ERR_PARAMETER).
  *       PG_ERR_STATE: a sampler without an envelope. zero_times: bit 0 hold, bit 1 decay, bit 2 release time is zero.
- * OUT OF SCOPE: granular samplers on the main mixer; the sharded handle; modulation messages to a sampler created WITHOUT a matrix (with one:
- * pg_graph_sampler_set_modulation and the LFO calls above); set_loop_range while playing on FILE samplers (it would move where a playing
- * PreloadedFileSource wraps; granular ones: pg_graph_sampler_set_loop_range); the AMP_* ids through pg_graph_sampler_set_parameter (their call is
- * pg_graph_sampler_set_envelope_parameter); playback status events of sampler voices and the sampler's own Stopped event;
- * GeneratorPlaybackOptions::volume and ::panning; the reference's 54-entry message queue (the control ring and PG_ERR_QUEUE_FULL stand in for
- * it). */
+ * OUT OF SCOPE: the main mixer through pg_graph_add_sampler / pg_graph_add_granular_sampler, which still refuse it (its entry points are
+ * pg_graph_add_sampler_to_main / pg_graph_add_granular_sampler_to_main, below); the sharded handle; modulation messages to a sampler created
+ * WITHOUT a matrix (with one: pg_graph_sampler_set_modulation and the LFO calls above); set_loop_range while playing on FILE samplers (it would
+ * move where a playing PreloadedFileSource wraps; granular ones: pg_graph_sampler_set_loop_range); the AMP_* ids through
+ * pg_graph_sampler_set_parameter (their call is pg_graph_sampler_set_envelope_parameter); playback status events of sampler voices and the
+ * sampler's own Stopped event; GeneratorPlaybackOptions::volume and ::panning for samplers in a SUB-mixer (there the pool is summed source by
+ * source and no sum of the sampler exists to scale: see pg_graph_add_sampler_to_main); the reference's 54-entry message queue (the control ring
+ * and PG_ERR_QUEUE_FULL stand in for it). */
 typedef struct pg_granular_sampler_options {
   pg_granular_params params;
   const pg_modulation_params* modulation;   /* NULL: no matrix */
@@ -744,6 +747,53 @@ int pg_graph_sampler_clear_modulation(pg_graph* g, int sampler_id, int source, i
 int pg_graph_sampler_set_lfo_rate(pg_graph* g, int sampler_id, int lfo, float rate_hz, uint64_t sample_time);
 int pg_graph_sampler_set_lfo_waveform(pg_graph* g, int sampler_id, int lfo, int waveform, uint64_t sample_time);
 int pg_graph_sampler_set_loop_range(pg_graph* g, int sampler_id, int has_loop_range, uint64_t loop_start, uint64_t loop_end, uint64_t sample_time);
+
+/* Samplers on the MAIN mixer, with the generator's volume and panning: what Player::play_generator / add_generator do by default
+ * (GeneratorPlaybackOptions::target_mixer = None, src/generator.rs:41-78; add_or_play_generator, src/player.rs:1048-1133): the Sampler goes to the
+ * main mixer as ONE source behind AmplifiedSource(options.volume) -> PannedSource(options.panning), and GeneratorPlaybackHandle::set_volume /
+ * set_panning drive those two at a sample time (src/player/handles/generator.rs:119-196). DESIGN.md, "Samplers on the main mixer".
+ * pg_generator_options: volume (default 1.0) and panning (default 0.0). _default / _check touch no graph and no device; _check: PG_OK or
+ * PG_ERR_PARAMETER with GeneratorPlaybackOptions::validate's text (generator.rs:120-140) for a negative or NaN volume ("playback options 'volume'
+ * value is '..'") and a panning outside [-1, 1] or NaN ("playback options 'panning' value is '..'"); null options are refused.
+ * pg_graph_add_sampler_to_main(g, buffer, opt, gen) / pg_graph_add_granular_sampler_to_main(g, buffer, opt, gopt, gen): `opt` / `gopt` as for
+ * pg_graph_add_sampler / pg_graph_add_granular_sampler (transient 1 = play_generator, 0 = add_generator; start_time as there); gen == NULL: the
+ * defaults. Checks in this order, the first three before the handle is looked at or a device touched: sampler options, granular options,
+ * generator options, handle, buffer, loop range. Returns a sampler id of the same id space: EVERY pg_graph_sampler_* call above takes it with
+ * unchanged rules (pg_graph_remove_sampler, the read-backs, the envelope, matrix, LFO, loop-range and granular-parameter messages included).
+ *   the unit    the whole pool is one source unit of the main mixer, one workgroup of the exact kernel, for as long as the sampler lives; a source
+ *               added later with the same start time stands in front of it in the mixer's sum (mixed.rs:324-329).
+ *   the grid    a message to such a sampler is an event of the MAIN mixer: it ends the main mixer's chunk at its frame and the next chunk begins
+ *               there, min(remaining, 4096) frames long (mixed.rs:659-719). Under a sub-mixer the parent's chunk simply goes on. So the ends of
+ *               Sampler::write — where a slot becomes free, what a later note of that slot finds — differ between the two placements.
+ *   the result  `produced_output` of the mixer is what Sampler::write returns: 0 when stopped, or when no voice is active and it is not stopping,
+ *               evaluated behind the messages of that write (sampler.rs:974-981); else the whole buffer, zeros included. A granular pool counts
+ *               as having delivered for as long as it lives (the deviation pg_graph_add_granular_sampler documents).
+ *   the stage   apply_smoothed_gain, then apply_smoothed_panning (smoothing.rs:59-125) over the samples written: while the volume ramps one
+ *               next() per interleaved SAMPLE, at rest a scale iff |1 - gain| > 1e-6; while the panning ramps one next() per FRAME, at rest the pan
+ *               law iff |pan| > 1e-6. Whether a smoother ramps is asked once per write. Both stand still over a write that returned 0.
+ *   end of life a transient sampler that has stopped leaves the mixer after the write in which it stopped (mixed.rs:612-615); its read-backs stay.
+ * pg_graph_sampler_set_volume / _set_panning: MixerMessage::SetSourceVolume / SetSourcePanning. Any thread, through the control ring
+ * (PG_ERR_QUEUE_FULL); sample_time 0 = the next write's first frame; a time before the start time acts at the start time. The target is set in
+ * front of the message's frame, which begins a chunk. Of several messages of one kind due on one frame the LAST one sent counts (the wrapper's
+ * one-slot queue, amplified.rs:33-35). PG_ERR_PARAMETER: a negative or non-finite volume, a non-finite panning (the bounds
+ * pg_graph_sampler_set_note_volume / _set_note_panning state); PG_ERR_NOT_FOUND: an unknown or removed id; PG_ERR_STATE: a sampler that lives in
+ * a sub-mixer — there the pool is summed source by source and no sum of the sampler exists to scale (OUT OF SCOPE, above).
+ * pg_graph_sampler_output_state: debug read-back of the two smoothers (waits for the graph's work): current, target, and whether need_ramp()
+ * holds. PG_ERR_STATE for a sampler in a sub-mixer.
+ * OUT OF SCOPE: the sharded handle; generator volume and panning for samplers in a sub-mixer; GeneratorPlaybackOptions::measure_cpu_load; playback
+ * status events of sampler voices and the sampler's Stopped; the FunDSP generator. */
+typedef struct pg_generator_options { float volume; float panning; } pg_generator_options;   /* GeneratorPlaybackOptions::volume / ::panning */
+typedef struct pg_sampler_output_state {
+  float volume_current, volume_target, panning_current, panning_target;
+  int32_t volume_ramping, panning_ramping;
+} pg_sampler_output_state;
+void pg_generator_options_default(pg_generator_options* opt);   /* 1.0, 0.0 */
+int pg_generator_options_check(const pg_generator_options* opt);
+int pg_graph_add_sampler_to_main(pg_graph* g, int buffer_id, const pg_sampler_options* opt, const pg_generator_options* gen);
+int pg_graph_add_granular_sampler_to_main(pg_graph* g, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt, const pg_generator_options* gen);
+int pg_graph_sampler_set_volume(pg_graph* g, int sampler_id, float volume, uint64_t sample_time);
+int pg_graph_sampler_set_panning(pg_graph* g, int sampler_id, float panning, uint64_t sample_time);
+int pg_graph_sampler_output_state(pg_graph* g, int sampler_id, pg_sampler_output_state* out);
 
 /* Per-mixer level metering: PlayerConfig::metering_interval (src/player.rs:162-217) wraps the main mixer and every sub-mixer in a MeteredSource
  * (src/player.rs:346-348, :784-786; src/source/mixed/submixer.rs:24); Player::audio_level / MixerHandle::audio_level return per-channel peak and

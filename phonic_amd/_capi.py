@@ -403,6 +403,37 @@ def sampler_envelope_state_dict(st):
     return d
 
 
+class GeneratorOptions(C.Structure):
+    """pg_generator_options: GeneratorPlaybackOptions::volume / ::panning of a sampler on the main mixer."""
+    _fields_ = [("volume", C.c_float), ("panning", C.c_float)]
+
+
+class SamplerOutputState(C.Structure):
+    """pg_sampler_output_state: the two smoothers of a main-mixer sampler's output stage."""
+    _fields_ = [("volume_current", C.c_float), ("volume_target", C.c_float), ("panning_current", C.c_float), ("panning_target", C.c_float),
+                ("volume_ramping", C.c_int32), ("panning_ramping", C.c_int32)]
+
+
+def generator_options(volume=None, panning=None):
+    """pg_generator_options_default with overrides."""
+    o = GeneratorOptions()
+    load().pg_generator_options_default(C.byref(o))
+    if volume is not None:
+        o.volume = volume
+    if panning is not None:
+        o.panning = panning
+    return o
+
+
+def sampler_output_state_dict(st):
+    """A pg_sampler_output_state as plain values (f32 values, booleans)."""
+    import numpy as np
+
+    d = {k: np.float32(getattr(st, k)) for k in ("volume_current", "volume_target", "panning_current", "panning_target")}
+    d["volume_ramping"], d["panning_ramping"] = bool(st.volume_ramping), bool(st.panning_ramping)
+    return d
+
+
 class GranularSamplerOptions(C.Structure):
     """pg_granular_sampler_options: the GranularParameters of Sampler::with_granular_playback, an optional matrix for every slot, an optional table
     of Xoshiro256++ states (voice_count x 3 x 4 words: slot k's pool, LFO 1, LFO 2)."""
@@ -595,6 +626,12 @@ GRAPH_ONLY_CALLS = (
     ("sampler_set_lfo_rate", _int, [_int, _int, _f32, _u64]),
     ("sampler_set_lfo_waveform", _int, [_int, _int, _int, _u64]),
     ("sampler_set_loop_range", _int, [_int, _int, _u64, _u64, _u64]),
+    # samplers on the main mixer, with the generator's volume and panning
+    ("add_sampler_to_main", _int, [_int, _P(SamplerOptions), _P(GeneratorOptions)]),
+    ("add_granular_sampler_to_main", _int, [_int, _P(SamplerOptions), _P(GranularSamplerOptions), _P(GeneratorOptions)]),
+    ("sampler_set_volume", _int, [_int, _f32, _u64]),
+    ("sampler_set_panning", _int, [_int, _f32, _u64]),
+    ("sampler_output_state", _int, [_int, _P(SamplerOutputState)]),
 )
 
 # what only the sharded handle has (pg_sharded_create and _destroy: in load)
@@ -634,6 +671,8 @@ PLAIN_CALLS = (
     ("pg_granular_sampler_options_default", None, [_P(GranularSamplerOptions)]),
     ("pg_granular_sampler_options_check", _int, [_P(GranularSamplerOptions)]),
     ("pg_granular_sampler_rng_state", None, [_P(_u64), _u32, _u32, _P(_u64)]),
+    ("pg_generator_options_default", None, [_P(GeneratorOptions)]),
+    ("pg_generator_options_check", _int, [_P(GeneratorOptions)]),
     ("pg_modulation_params_default", None, [_P(ModulationParams)]),
     ("pg_modulation_params_check", _int, [_P(ModulationParams)]),
     ("pg_debug_sample_buffer_times", _int, [_vp, _int, _P(_f32)]),

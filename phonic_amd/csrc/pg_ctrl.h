@@ -51,6 +51,9 @@ enum CtrlType : int32_t {
   CT_SAMPLER_LFO_RATE = 27,       // ... as CT_VOICE_LFO_RATE
   CT_SAMPLER_LFO_WAVEFORM = 28,   // ... as CT_VOICE_LFO_WAVEFORM
   CT_SAMPLER_GRAIN_LOOP = 29,     // a granular-mode sampler; as CT_VOICE_GRAIN_LOOP
+  // the generator's output stage of a sampler on the main mixer (GeneratorPlaybackHandle::set_volume / set_panning), events
+  CT_SAMPLER_OUT_VOLUME = 30,     // value                                                           (SetSourceVolume)
+  CT_SAMPLER_OUT_PAN = 31,        // value                                                           (SetSourcePanning)
 };
 
 struct CtrlMsg {

@@ -278,8 +278,19 @@ struct PgSamplerSlot {             // the per-note part of SamplerVoice (voice.r
   float note_volume, note_panning;
   int32_t note, pad;
 };
+// The generator's output stage of a sampler that sits on the MAIN mixer (pg_graph_add_sampler_to_main): AmplifiedSource(options.volume) and
+// PannedSource(options.panning) over the Sampler's sum (player.rs:1048-1133), rendered behind the voice loop of the sampler's source unit
+// (pg_sampler_dev.h: genout_*). `flags` is decided once per Sampler::write, in front of the source stage of the chunk's first piece.
+enum { PG_GENOUT_DELIVERS = 1,     // the write in progress returned its whole buffer (sampler.rs:974-981): the stage runs over it
+       PG_GENOUT_VOLUME_RAMPS = 2, // apply_smoothed_gain found need_ramp() at the top of the write: one next() per sample of the write
+       PG_GENOUT_PAN_RAMPS = 4 };  // apply_smoothed_panning likewise: one next() per frame
+struct PgGenOut {
+  PgSmooth volume, panning;
+  int32_t on;                      // 1: the sampler is a source of the main mixer; 0: a pool in a sub-mixer, which has no sum of its own to scale
+  int32_t flags;                   // PG_GENOUT_*
+};
 struct PgSamplerRec {
-  int32_t unit;                    // unit slot of the owning sub-mixer
+  int32_t unit;                    // unit slot of the owning sub-mixer; of the sampler's own source unit on the main mixer
   int32_t voice0, n_voices;
   int32_t has_envelope, transient;
   int32_t stopping, stopped;       // sampler.rs:733-738, :1011-1024
@@ -288,14 +299,17 @@ struct PgSamplerRec {
   int32_t pad;
   double pitch_factor;             // ... and 2^(transpose / 12 + finetune / 1200) as the host's libm gives it (voice.rs:146-147)
   PgSamplerSlot slots[PG_SAMPLER_MAX_VOICES];
+  PgGenOut out;                    // (a granular sampler's too: the record is inert for its notes, n_voices 0, but holds its output stage)
 };
+struct PgGSampler;
 struct PgSamplerTab {
   uint32_t n, pad;                 // records behind the header: no record at or beyond it is taken
   const double* speed_tab;         // speed_from_note(0 .. 255) (utils.rs:67-78), host-computed
   int32_t* stopped;                // mapped host memory, one word per record: set with PgSamplerRec::stopped
-  uint64_t pad_tab;
+  const PgGSampler* gsamp;         // the granular-mode samplers' records, indexed like the ones behind the header (nullptr: the graph has none)
 };
-static_assert(sizeof(PgSamplerSlot) == 32 && sizeof(PgSamplerRec) == 56 + 32 * PG_SAMPLER_MAX_VOICES && sizeof(PgSamplerTab) == 32, "host and device agree on the layout");
+static_assert(sizeof(PgSmooth) == 28 && sizeof(PgGenOut) == 64, "host and device agree on the layout");
+static_assert(sizeof(PgSamplerSlot) == 32 && sizeof(PgSamplerRec) == 56 + 32 * PG_SAMPLER_MAX_VOICES + 64 && sizeof(PgSamplerTab) == 32, "host and device agree on the layout");
 
 // ---- playback status events (pg_graph_set_voice_status; pg_k_status.hip) ----
 // PlaybackStatusEvent::Position / Stopped are decided once per Source::write call of the voice (src/source/file/preloaded.rs:396-475,
@@ -437,7 +451,8 @@ struct PgGSampler {
   uint64_t start_time;             // the mixer calls the sampler from here on
   uint64_t span_t0;                // first frame of the Sampler::write span that is open (UINT64_MAX: none)
   PgEnvParams env_params;          // with note.has_envelope
-  int32_t pad;
+  int32_t delivers;                // the Sampler::write that began at the last boundary returns its whole buffer (sampler.rs:974-981): not stopped, and a slot
+                                   // is active or the sampler is stopping, the messages of that frame applied. What the output stage of a main-mixer sampler asks.
   PgEnvState env[PG_SAMPLER_MAX_VOICES];
   int32_t active[PG_SAMPLER_MAX_VOICES];   // SamplerVoice::is_active (voice.rs:100-102)
 };
@@ -516,7 +531,7 @@ struct PgUnit {
   float call_max;               // peak of the call's output so far (submixer.rs:57: max_abs over the whole call)
   uint32_t call_frames;         // frames of the call rendered in earlier pieces
   int32_t call_idx;             // calls finished in the main mixer's current chunk
-  int32_t pad_call;
+  int32_t sampler;              // host, a source unit: index + 1 of the sampler whose whole pool the unit holds (pg_graph_add_sampler_to_main); 0: none
 };
 enum { PG_STAGE_ACTIVE = 1, PG_STAGE_INPUT_BYPASSED = 2, PG_STAGE_ALL_BYPASSED = 4, PG_STAGE_AUDIBLE = 8, PG_STAGE_SKIPPED = 16,
        PG_STAGE_FIRST = 32, PG_STAGE_LAST = 64 };  // the block is the first / last piece of its chunk
@@ -565,6 +580,9 @@ enum PgCmdType {
   CMD_SAMPLER_LFO_RATE = 28,      // as CMD_VOICE_LFO_RATE, for every slot                                                      (Lfo::set_rate)
   CMD_SAMPLER_LFO_WAVEFORM = 29,  // as CMD_VOICE_LFO_WAVEFORM, for every slot                                                  (Lfo::set_waveform)
   CMD_SAMPLER_GRAIN_LOOP = 30,    // as CMD_VOICE_GRAIN_LOOP, for every slot                                                    (GrainPool::set_loop_range)
+  // the generator's output stage of a main-mixer sampler (target = index of its PgSamplerRec; pg_unit_kernel applies them in front of `frame`):
+  CMD_SAMPLER_OUT_VOLUME = 31,    // value = volume                                                                             (MixerEvent::SetSourceVolume)
+  CMD_SAMPLER_OUT_PAN = 32,       // value = panning                                                                            (MixerEvent::SetSourcePanning)
 };
 // CMD_SAMPLER_ENV_PARAM's index: Sampler::envelope_parameters() (sampler.rs:173-181)
 enum { PG_SE_ATTACK = 0, PG_SE_HOLD, PG_SE_DECAY, PG_SE_SUSTAIN, PG_SE_RELEASE, PG_SE_COUNT };
@@ -585,6 +603,8 @@ struct PgCmd {
 #endif
 // A sampler's message: every CMD_SAMPLER_* (the host retires them with their sampler, pg_gsampler_kernel filters its command list by it) ...
 PG_HD inline bool pg_cmd_is_sampler_message(int type) { return type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_GRAIN_LOOP; }
+// ... the two of a main-mixer sampler's output stage: events of the main mixer addressed to the sampler's unit, not messages of the Sampler ...
+PG_HD inline bool pg_cmd_is_sampler_output(int type) { return type == CMD_SAMPLER_OUT_VOLUME || type == CMD_SAMPLER_OUT_PAN; }
 // ... and the ones pg_unit_kernel's note layer applies to a file sampler: the granular-only ones are not among them
 PG_HD inline bool pg_cmd_is_unit_note_message(int type) { return (type >= CMD_SAMPLER_NOTE_ON && type <= CMD_SAMPLER_STOP) || type == CMD_SAMPLER_ENV_PARAM; }
 // CMD_SAMPLER_NOTE_ON's value64: note | f32 bits of panning << 32

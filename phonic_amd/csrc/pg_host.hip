@@ -88,16 +88,22 @@ __global__ void pg_status_kernel(const PgVoice* voices, const int32_t* idx, int 
   if (threadIdx.x == 0) { *status = active; __threadfence_system(); }
 }
 
-static int new_unit(pg_graph* g, int kind) {
+static int new_unit(pg_graph* g, int kind, int sampler = 0) {
   PgUnit u;
   memset(&u, 0, sizeof u);
   u.kind = kind;
+  u.sampler = sampler;
   u.effects_bypassed = 1;  // MixedSource::new: effects_bypassed = true (mixed.rs:230)
   int idx = -1;
   if (g->d_units.push(u, &idx)) return -1;
   g->h_units.push_back(u);
   g->topo_dirty = true;
   return idx;
+}
+
+int graph_new_sampler_unit(pg_graph* g, int sampler_index) {
+  // (PgUnit::sampler is set once, with the unit: it is none of the topology fields pg_patch_units_kernel rewrites, and unit slots are never reused)
+  return new_unit(g, UNIT_SOURCE, sampler_index + 1);
 }
 
 static int rebuild_topology(pg_graph* g, hipStream_t stream) {
@@ -167,11 +173,16 @@ static int rebuild_topology(pg_graph* g, hipStream_t stream) {
     u.child_off = (int)child_rows.size(); u.n_children = (int)g->mixers[m].children.size();
     for (int c : g->mixers[m].children) child_rows.push_back(make_int2(row_of_mixer[c], g->mixers[c].unit_slot));
   }
+  int prev_slot = -1;
   for (int v : g->mixers[0].voices) {
     int slot = g->source_unit_of_voice[v];
     PgUnit& u = topo[slot];
+    // a main-mixer sampler's pool: ONE unit for the run of its voices — they share a start time and were added last slot first, so the list holds
+    // them side by side in slot order, and a source added later with that start time stands in front of all of them (mixed.rs:324-329)
+    if (slot == prev_slot) { u.n_voices += 1; vidx.push_back(g->voices[v].dev_index); continue; }
+    prev_slot = slot;
     u.voice_off = (int)vidx.size(); u.n_voices = 1; u.n_fx = 0; u.fx_off = 0;
-    u.static_defer = (g->voices[v].env_live || g->voices[v].gran_live) ? 1 : 0;
+    u.static_defer = (g->voices[v].env_live || g->voices[v].gran_live || g->voices[v].sampler >= 0) ? 1 : 0;   // (a sampler's unit: the exact kernel for as long as it lives)
     if (g->voices[v].outer) g->any_outer = true;
     u.voice0 = g->voices[v].dev_index;
     vidx.push_back(g->voices[v].dev_index);
@@ -318,7 +329,14 @@ void voice_init_neutral(const pg_graph* g, PgVoice& v, const pg_voice_options* o
   v.active = 1;
   v.persistent = opt->non_transient != 0;
 }
-int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind) {
+void genout_init(const pg_graph* g, PgGenOut& o, float volume, float panning) {
+  memset(&o, 0, sizeof o);
+  ParamSpec exp_spec = {0, PG_PARAM_FLOAT, 0, 0, 0, 0, 0, 0, 0, "", S_EXP, 0};   // ExponentialSmoothedValue::new(value, source.sample_rate()), as voice_init_neutral's
+  o.volume = make_smooth(exp_spec, volume, g->sample_rate);
+  o.panning = make_smooth(exp_spec, panning, g->sample_rate);
+  o.on = 1;
+}
+int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind, int source_unit) {
   const int id = (int)g->voices.size();
   hv.mixer = mixer_id; hv.dev_index = dev_index; hv.start_time = opt->start_time; hv.added_at_write = g->write_count; hv.transient = opt->non_transient == 0;
   g->voices.push_back(hv);
@@ -331,7 +349,7 @@ int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voic
   while (pos < mx.voices.size() && g->voices[mx.voices[pos]].start_time < opt->start_time) ++pos;
   mx.voices.insert(mx.voices.begin() + pos, id);
   if (mixer_id == 0) {
-    int slot = new_unit(g, UNIT_SOURCE);
+    int slot = source_unit >= 0 ? source_unit : new_unit(g, UNIT_SOURCE);
     if (slot < 0) return -graph_fail(g, PG_ERR_DEVICE);
     g->source_unit_of_voice[id] = slot;
     g->main_active_voices += 1;
@@ -1414,7 +1432,8 @@ void graph_begin_write(pg_graph* g, uint64_t pos) {
 bool graph_is_empty(const pg_graph* g) {
   bool no_sub_mixers = true;  // self.mixers.is_empty(): sub-mixers that were removed again do not count
   for (size_t m = 1; m < g->mixers.size(); ++m) no_sub_mixers &= g->mixers[m].removed;
-  return g->main_active_voices == 0 && g->mixers[0].fx.empty() && no_sub_mixers && g->mixers[0].events.empty();
+  // (a sampler on the main mixer is a playing source of it whether a note sounds or not: the mixer calls it, and it answers 0 — sampler.rs:974-981)
+  return g->main_active_voices == 0 && g->n_main_samplers == 0 && g->mixers[0].fx.empty() && no_sub_mixers && g->mixers[0].events.empty();
 }
 uint64_t graph_frames_to_main_event(const pg_graph* g, uint64_t now) {
   for (const Event& e : g->mixers[0].events) if (e.sample_time > now) return e.sample_time - now;
@@ -1527,7 +1546,7 @@ static void collect_piece_commands(pg_graph* g, std::vector<PgCmd>& cmds, uint64
   // and that matters, an exponential smoother snaps to a target that is close enough (smoothing.rs:221-226), so applying the earlier ones too
   // can leave another `current` behind. (Speed and seek messages travel through the file's 128-slot queue and all arrive.)
   for (size_t i = 0; i < cmds.size(); ++i) {
-    if (cmds[i].type != CMD_VOICE_VOLUME && cmds[i].type != CMD_VOICE_PAN) continue;
+    if (cmds[i].type != CMD_VOICE_VOLUME && cmds[i].type != CMD_VOICE_PAN && !pg_cmd_is_sampler_output(cmds[i].type)) continue;   // (a main-mixer sampler's wrappers have the same queues)
     for (size_t j = i + 1; j < cmds.size() && cmds[j].unit == cmds[i].unit && cmds[j].frame == cmds[i].frame; ++j)
       if (cmds[j].type == cmds[i].type && cmds[j].target == cmds[i].target) { cmds[i].type = CMD_NOP; break; }
   }
@@ -1682,7 +1701,10 @@ static void take_head_commands(pg_graph* g, uint64_t now, std::vector<PgCmd>& he
       continue;
     }
     c.frame = 0;
-    c.unit = cmd_is_bus_chain(c.type) ? main.unit_slot : g->source_unit_of_voice[c.param];  // voice commands carry the voice id in `param`
+    if (pg_cmd_is_sampler_message(c.type) || pg_cmd_is_sampler_output(c.type)) {   // a main-mixer sampler's: its own source unit (target: the sampler)
+      c.unit = g->samplers[c.target].unit;
+      sampler_stage_command(g, c);
+    } else c.unit = cmd_is_bus_chain(c.type) ? main.unit_slot : g->source_unit_of_voice[c.param];  // voice commands carry the voice id in `param`
     head.push_back(c);
     main.events.erase(main.events.begin());
   }

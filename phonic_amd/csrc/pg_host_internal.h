@@ -266,7 +266,7 @@ struct HostVoice {
   int sampler = -1;                // a pool voice of pg_graph::samplers[sampler] (pg_graph_add_sampler): no public id, its unit stays on the exact kernel
 };
 // What a sampler id stands for, as the message calls of any thread see it (pg_graph::sampler_alive_tab): one of the first two, plus what it was created with
-enum : int8_t { SAMPLER_TAB_FILE = 1, SAMPLER_TAB_GRANULAR = 2, SAMPLER_TAB_ENVELOPE = 4, SAMPLER_TAB_MATRIX = 8 };
+enum : int8_t { SAMPLER_TAB_FILE = 1, SAMPLER_TAB_GRANULAR = 2, SAMPLER_TAB_ENVELOPE = 4, SAMPLER_TAB_MATRIX = 8, SAMPLER_TAB_MAIN = 16 };   // (_MAIN: a source of the main mixer, with the generator's output stage)
 // A sampler (pg_graph_add_sampler): the pool's place in the graph; the note layer's state is the device's (PgSamplerRec `rec` of pg_graph::d_samp)
 struct HostSampler {
   int mixer = -1, rec = -1;
@@ -281,6 +281,8 @@ struct HostSampler {
   // slot k renders through PgGrainVoice record grain0 + k; with_mod: every slot has a modulation matrix
   bool granular = false, with_mod = false;
   int grain0 = -1;
+  // a sampler on the main mixer (pg_graph_add_sampler_to_main / _granular_sampler_to_main): mixer 0, and the ONE source unit that holds its whole pool
+  int unit = -1;
 };
 // A sample buffer on the device (pg_graph_add_sample_buffer): AudioFileBuffer behind an Arc (src/source/file/buffer.rs). The host holds one
 // reference until pg_graph_release_sample_buffer, every voice made from it one until its memory is released (graph_voice_release).
@@ -416,6 +418,7 @@ struct pg_graph {
   std::vector<int> source_unit_of_voice;  // main-mixer voices: unit slot
   uint64_t event_seq = 0;
   int main_active_voices = 0;           // feedback from the device (sync write only)
+  int n_main_samplers = 0;              // living samplers on the main mixer: sources of it whether a note sounds or not (graph_is_empty)
   bool ever_had_main_voice = false;
   // device tables
   DeviceVec<PgUnit> d_units;
@@ -558,7 +561,10 @@ int voice_message(pg_graph* g, int voice_id, VoiceKind need, int type, uint64_t 
 // The fields every new voice starts with: fader neutral, exponential smoothers at `volume` / `panning`, active, start time and persistence of `opt`
 void voice_init_neutral(const pg_graph* g, PgVoice& v, const pg_voice_options* opt, float volume, float panning);
 // MixerMessage::AddSource for a voice whose record is d_voices[dev_index]: fills in what every HostVoice holds and returns the new id (< 0: -PG_ERR_*)
-int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind);
+// source_unit >= 0: a voice of the main mixer that shares that source unit (a main-mixer sampler's pool: graph_new_sampler_unit); else a unit of its own
+int graph_register_voice(pg_graph* g, int mixer_id, int dev_index, const pg_voice_options* opt, HostVoice hv, VoiceKind kind, int source_unit = -1);
+int graph_new_sampler_unit(pg_graph* g, int sampler_index);   // a UNIT_SOURCE of the main mixer for the whole pool of that sampler (< 0: the device table could not take it)
+void genout_init(const pg_graph* g, PgGenOut& o, float volume, float panning);   // AmplifiedSource::new(.., volume) / PannedSource::new(.., panning) at the graph's rate, on a main-mixer sampler
 // Debug read-backs: waits for the graph's stream and the last write's, then copies `bytes` from device memory (PG_OK / PG_ERR_DEVICE)
 int graph_read_back(pg_graph* g, void* dst, const void* d_src, size_t bytes);
 bool graph_is_empty(const pg_graph* g);

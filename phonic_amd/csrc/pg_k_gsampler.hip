@@ -9,7 +9,9 @@
 // on the reference's grid, not where a message happens to arrive.
 // The host issues one launch per boundary of ANY sampler's grid (pg_sampler.hip: launch_gsampler_spans); the workgroup of a sampler whose mixer
 // has no cut there returns at once: the boundary is the sampler's own iff the chunk begins there, its start time lies there, or a command of its
-// unit — an event of the mixer, a call boundary of an ancestor (CMD_CALL_SPLIT) — stands at that frame of the piece's command list.
+// unit — an event of the mixer, a call boundary of an ancestor (CMD_CALL_SPLIT) — stands at that frame of the piece's command list. A sampler on
+// the MAIN mixer (pg_graph_add_granular_sampler_to_main) has its own source unit in note.unit: its messages are events of the main mixer, each
+// begins a chunk, so its boundaries are the chunk's first frame and its start time.
 // The arithmetic is pg_gsampler_dev.h's.
 #include "pg_host_internal.h"
 #include "pg_gsampler_dev.h"
@@ -39,6 +41,11 @@ __global__ void __launch_bounds__(256) pg_gsampler_kernel(PgGSamplerLaunch L) {
   if (span_t0 != PG_USIZE_MAX && span_t0 < L.t) gs_close(L, r, span_t0, L.t, S);
   const bool opens = !L.closing && L.t >= r.start_time;   // (the mixer does not call the sampler before its start time, mixed.rs:565-576)
   if (opens && !r.note.stopped) gs_open(L, r, S);          // (a stopped sampler returns empty-handed: sampler.rs:978-981)
+  if (!L.closing) {   // what the write that begins here returns (PgGSampler::delivers), the messages of its first frame applied
+    __syncthreads();
+    const int any_active = __syncthreads_or((tid < r.note.n_voices && r.active[tid] != 0) ? 1 : 0);
+    if (tid == 0) r.delivers = (opens && !r.note.stopped && (any_active || r.note.stopping)) ? 1 : 0;
+  }
   if (tid == 0) r.span_t0 = opens ? L.t : PG_USIZE_MAX;
 }
 

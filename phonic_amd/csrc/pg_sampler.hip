@@ -666,7 +666,11 @@ static void sampler_retire(pg_graph* g, int sampler_id) {
     g->voices[v].mixer = -1;
     g->retired_voices.push_back(v);
   }
-  for (Event& e : mx.events) if (pg_cmd_is_sampler_message(e.cmd.type) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
+  for (Event& e : mx.events) if ((pg_cmd_is_sampler_message(e.cmd.type) || pg_cmd_is_sampler_output(e.cmd.type)) && e.cmd.target == hs.rec) { e.cmd.type = CMD_NOP; e.cmd.target = 0; }
+  if (hs.unit >= 0) {   // a source of the main mixer is gone: a granular pool's voices all counted as live ones, a file pool's as their notes had it — the next count says
+    g->n_main_samplers -= 1;
+    if (hs.granular) g->main_active_voices = std::max(0, g->main_active_voices - hs.n_voices);
+  }
   hs.alive = false;
   if (hs.granular) g->gsamp_dirty = true;
   g->sampler_alive_tab.set((size_t)sampler_id, 0);
@@ -710,7 +714,7 @@ static int graph_samp_reserve(pg_graph* g, size_t n) {
 static hipError_t samp_head_upload(const pg_graph* g, size_t n) {
   PgSamplerTab head;
   memset(&head, 0, sizeof head);
-  head.n = (uint32_t)n; head.speed_tab = g->d_speed_tab; head.stopped = g->samp_stopped.d;
+  head.n = (uint32_t)n; head.speed_tab = g->d_speed_tab; head.stopped = g->samp_stopped.d; head.gsamp = g->d_gsamp;
   return pg_memcpy(g->d_samp, &head, sizeof head, hipMemcpyHostToDevice);
 }
 
@@ -733,9 +737,12 @@ static const SamplerEvent SAMPLER_EVENTS[] = {
   {pgc::CT_SAMPLER_LFO_RATE, CMD_SAMPLER_LFO_RATE, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value = m.value; c.value64 = (uint64_t)(uint32_t)m.param; }},
   {pgc::CT_SAMPLER_LFO_WAVEFORM, CMD_SAMPLER_LFO_WAVEFORM, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value64 = (uint64_t)(uint32_t)m.param; }},
   {pgc::CT_SAMPLER_GRAIN_LOOP, CMD_SAMPLER_GRAIN_LOOP, [](const pgc::CtrlMsg& m, PgCmd& c) { uint32_t end; memcpy(&end, &m.value2, 4); c.value = m.value; c.value64 = (uint64_t)(m.param & 1) | ((uint64_t)end << 32); }},
+  // the generator's output stage of a main-mixer sampler: events of the main mixer like a voice's SetSourceVolume / SetSourcePanning
+  {pgc::CT_SAMPLER_OUT_VOLUME, CMD_SAMPLER_OUT_VOLUME, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value = m.value; }},
+  {pgc::CT_SAMPLER_OUT_PAN, CMD_SAMPLER_OUT_PAN, [](const pgc::CtrlMsg& m, PgCmd& c) { c.value = m.value; }},
 };
 bool sampler_drain_message(pg_graph* g, const pgc::CtrlMsg& m) {
-  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_GRAIN_LOOP) return false;
+  if (m.type < pgc::CT_SAMPLER_NOTE_ON || m.type > pgc::CT_SAMPLER_OUT_PAN) return false;
   if (m.id < 0 || m.id >= (int)g->samplers.size() || !g->samplers[m.id].alive) return true;   // gone in the meantime: dropped
   if (m.type == pgc::CT_SAMPLER_REMOVE) { sampler_retire(g, m.id); return true; }
   const HostSampler& hs = g->samplers[m.id];
@@ -831,12 +838,14 @@ static const HostSampler* sampler_for_readback(pg_graph* g, int sampler_id) {
 }
 
 // ---- a pool's construction: what pg_graph_add_sampler and pg_graph_add_granular_sampler share, in three steps with each kind's own work between them ----
-// 1. The checks, in the order the calls make them: the options, a granular sampler's own options, the handle, the mixer, the buffer, the loop range.
-static int sampler_pool_check(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, bool granular, const pg_granular_sampler_options* gopt) {
+// 1. The checks, in the order the calls make them: the options, a granular sampler's own options, the generator's options (`to_main`: the entry
+// points that place the sampler on the main mixer; gen null = the defaults), the handle, the mixer, the buffer, the loop range.
+static int sampler_pool_check(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, bool granular, const pg_granular_sampler_options* gopt, bool to_main, const pg_generator_options* gen) {
   { const int rc = pg_sampler_options_check(opt); if (rc) return rc; }
   if (granular) { const int rc = pg_granular_sampler_options_check(gopt); if (rc) return rc; }
+  if (to_main && gen) { const int rc = pg_generator_options_check(gen); if (rc) return rc; }
   if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
-  if (mixer_id == PG_MAIN_MIXER) return set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, %s",
+  if (!to_main && mixer_id == PG_MAIN_MIXER) return set_error(PG_ERR_PARAMETER, "A sampler needs a sub-mixer: every source of the main mixer is a unit and a workgroup of its own, %s",
                                                   granular ? "the pool is one source of one mixer" : "the pool needs one workgroup that sees all of its voices");
   if (mixer_id < 0 || mixer_id >= (int)g->mixers.size() || g->mixers[mixer_id].removed) return set_error(PG_ERR_NOT_FOUND, "Mixer with id %d not found", mixer_id);
   const SampleBuffer* sb = sample_buffer_find(g, buffer_id);
@@ -874,11 +883,12 @@ static void note_rec_init(PgSamplerRec& r, int unit, int voice0, int n, const pg
 // 3. The records are on the device: the sampler's place in the graph. `hs` arrives with what is its kind's (a granular sampler's grain records),
 // `tab_kind` with its kind's SAMPLER_TAB_* bits, `stages` with a granular sampler's staging buffers, one per slot: each passes to its slot's voice,
 // and a failure frees those no voice owns yet. Returns the sampler's id (< 0: -PG_ERR_*).
-static int sampler_pool_register(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_voice_options& vo, int voice0, HostSampler hs, int tab_kind, std::vector<void*>* stages) {
+// `unit`: the source unit of a sampler on the main mixer, which every voice of the pool maps to (graph_new_sampler_unit); -1 in a sub-mixer.
+static int sampler_pool_register(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_voice_options& vo, int voice0, HostSampler hs, int tab_kind, std::vector<void*>* stages, int unit) {
   const int n = (int)opt->voice_count, sampler_id = (int)g->samplers.size();
   const SampleBuffer& sb = g->sample_buffers[buffer_id];
   g->samp_stopped[(size_t)sampler_id] = 0;
-  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
+  hs.mixer = mixer_id; hs.rec = sampler_id; hs.n_voices = n; hs.unit = unit; hs.has_envelope = opt->has_envelope != 0; hs.transient = opt->transient != 0; hs.start_time = opt->start_time;
   // the mixer's list inserts a new source in FRONT of those with the same start time (mixed.rs:324-329): the last slot goes in first, so that the
   // mixer — and the kernel that sums the pool — meets it in slot order (sampler.rs:989-1006)
   for (int k = n - 1; k >= 0; --k) {
@@ -887,14 +897,15 @@ static int sampler_pool_register(pg_graph* g, int mixer_id, int buffer_id, const
     if (stages) { hv.d_stage = (*stages)[(size_t)k]; (*stages)[(size_t)k] = nullptr; }   // (the voice owns it from here on)
     hv.file_channels = sb.channels; hv.file_rate = sb.rate; hv.file_samples = (uint64_t)sb.n_frames * sb.channels;
     g->sample_buffers[buffer_id].use_count += 1;
-    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD);   // (VOICE_DEAD: the id takes none of the public voice calls)
+    const int id = graph_register_voice(g, mixer_id, voice0 + k, &vo, hv, VOICE_DEAD, unit);   // (VOICE_DEAD: the id takes none of the public voice calls)
     if (id < 0) { if (stages) for (void* p : *stages) if (p) (void)pg_free(p); return id; }
     if (k == 0) hs.voice_id_slot0 = id;
   }
   if (opt->has_envelope) hs.env = ahdsr_build_params(opt->envelope, g->sample_rate);
   g->samplers.push_back(hs);
   if (hs.granular) { g->n_gsamplers += 1; g->gsamp_dirty = true; }
-  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) || !g->sampler_alive_tab.append((int8_t)(tab_kind | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
+  if (unit >= 0) g->n_main_samplers += 1;
+  if (!g->sampler_frames_tab.append((uint64_t)sb.n_frames) || !g->sampler_alive_tab.append((int8_t)(tab_kind | (opt->has_envelope ? SAMPLER_TAB_ENVELOPE : 0) | (unit >= 0 ? SAMPLER_TAB_MAIN : 0)))) return -set_error(PG_ERR_STATE, "too many samplers");
   return sampler_id;
 }
 
@@ -920,10 +931,12 @@ int pg_sampler_param(int index, pg_param_desc* out) {   // Sampler::base_paramet
   param_desc_from_spec(SAMPLER_PARAMS[index], out);
   return PG_OK;
 }
-int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt) {
+// pg_graph_add_sampler (a sub-mixer's pool) and pg_graph_add_sampler_to_main (`to_main`: mixer_id is PG_MAIN_MIXER; the pool is ONE source unit
+// of the main mixer, behind the generator's output stage with `gen`'s volume and panning — null: the defaults)
+static int add_file_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, bool to_main, const pg_generator_options* gen) {
   pg_sampler_options def;
   if (!opt) { pg_sampler_options_default(&def); opt = &def; }
-  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, false, nullptr); if (rc) return -rc; }
+  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, false, nullptr, to_main, gen); if (rc) return -rc; }
   drain_control_messages(g);
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
   const SampleBuffer sb = g->sample_buffers[buffer_id];
@@ -953,11 +966,55 @@ int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_samp
     std::vector<PgEnv> es((size_t)n, e);
     if (pg_memcpy(g->d_env + voice0, es.data(), es.size() * sizeof(PgEnv), hipMemcpyHostToDevice) != hipSuccess) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
   }
+  const int unit = to_main ? graph_new_sampler_unit(g, sampler_id) : -1;
+  if (to_main && unit < 0) return -graph_fail(g, PG_ERR_DEVICE);
   std::unique_ptr<PgSamplerRec> r(new PgSamplerRec);
-  note_rec_init(*r, g->mixers[mixer_id].unit_slot, voice0, n, opt);
+  note_rec_init(*r, to_main ? unit : g->mixers[mixer_id].unit_slot, voice0, n, opt);
+  if (to_main) { pg_generator_options go; if (gen) go = *gen; else pg_generator_options_default(&go); genout_init(g, r->out, go.volume, go.panning); }
   if (pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, r.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess || samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess ||
       graph_env_head_refresh(g)) return -graph_fail(g, set_error(PG_ERR_DEVICE, "sampler upload failed"));
-  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, HostSampler(), SAMPLER_TAB_FILE, nullptr);
+  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, HostSampler(), SAMPLER_TAB_FILE, nullptr, unit);
+}
+int pg_graph_add_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt) { return add_file_sampler(g, mixer_id, buffer_id, opt, false, nullptr); }
+int pg_graph_add_sampler_to_main(pg_graph* g, int buffer_id, const pg_sampler_options* opt, const pg_generator_options* gen) { return add_file_sampler(g, PG_MAIN_MIXER, buffer_id, opt, true, gen); }
+void pg_generator_options_default(pg_generator_options* o) {   // GeneratorPlaybackOptions::default (generator.rs:62-78)
+  if (!o) return;
+  o->volume = 1.0f; o->panning = 0.0f;
+}
+int pg_generator_options_check(const pg_generator_options* o) {   // GeneratorPlaybackOptions::validate (generator.rs:120-140)
+  if (!o) return set_error(PG_ERR_PARAMETER, "generator options must not be null");
+  if (o->volume < 0.0f || o->volume != o->volume) return set_error(PG_ERR_PARAMETER, "playback options 'volume' value is '%g'", (double)o->volume);
+  if (!(o->panning >= -1.0f && o->panning <= 1.0f)) return set_error(PG_ERR_PARAMETER, "playback options 'panning' value is '%g'", (double)o->panning);
+  return PG_OK;
+}
+// ---- the generator's output stage of a sampler on the main mixer (GeneratorPlaybackHandle::set_volume / set_panning, player/handles/generator.rs:
+// 119-196 -> MixerMessage::SetSourceVolume / SetSourcePanning): events of the main mixer, like a voice's. Any thread. ----
+static int sampler_output_message(pg_graph* g, int sampler_id, int type, float value, uint64_t sample_time) {
+  const int w = sampler_tab_word(g, sampler_id);
+  if (!w) return sampler_tab_error(g);
+  if (!(w & SAMPLER_TAB_MAIN)) return set_error(PG_ERR_STATE, "Sampler with id %d lives in a sub-mixer: its pool is summed there source by source, so no sum of the sampler exists to scale or pan (see pg_graph_add_sampler_to_main)", sampler_id);
+  return sampler_message(g, sampler_id, type, sample_time, 0, value);
+}
+int pg_graph_sampler_set_volume(pg_graph* g, int sampler_id, float volume, uint64_t sample_time) {
+  if (!(volume >= 0.0f) || !std::isfinite(volume)) return set_error(PG_ERR_PARAMETER, "Invalid volume: %g. Must be finite and >= 0", (double)volume);
+  return sampler_output_message(g, sampler_id, pgc::CT_SAMPLER_OUT_VOLUME, volume, sample_time);
+}
+int pg_graph_sampler_set_panning(pg_graph* g, int sampler_id, float panning, uint64_t sample_time) {
+  if (!std::isfinite(panning)) return set_error(PG_ERR_PARAMETER, "Invalid panning: %g. Must be finite", (double)panning);
+  return sampler_output_message(g, sampler_id, pgc::CT_SAMPLER_OUT_PAN, panning, sample_time);
+}
+int pg_graph_sampler_output_state(pg_graph* g, int sampler_id, pg_sampler_output_state* out) {
+  if (!out) return set_error(PG_ERR_PARAMETER, "output is null");
+  if (!g) return set_error(PG_ERR_PARAMETER, "graph handle is null");
+  const HostSampler* hs = sampler_for_readback(g, sampler_id);
+  if (!hs) return PG_ERR_NOT_FOUND;
+  if (hs->unit < 0) return set_error(PG_ERR_STATE, "Sampler with id %d lives in a sub-mixer: its pool is summed there source by source, so it has no output stage (see pg_graph_add_sampler_to_main)", sampler_id);
+  PgGenOut o;
+  { const int rc = graph_read_back(g, &o, (const char*)((const PgSamplerRec*)(g->d_samp + 1) + hs->rec) + offsetof(PgSamplerRec, out), sizeof o); if (rc) return rc; }
+  memset(out, 0, sizeof *out);
+  out->volume_current = o.volume.current; out->volume_target = o.volume.target; out->panning_current = o.panning.current; out->panning_target = o.panning.target;
+  out->volume_ramping = pgd::sm_need_ramp(o.volume) ? 1 : 0; out->panning_ramping = pgd::sm_need_ramp(o.panning) ? 1 : 0;
+  return PG_OK;
 }
 int pg_graph_remove_sampler(pg_graph* g, int sampler_id) {
   const int rc = sampler_message(g, sampler_id, pgc::CT_SAMPLER_REMOVE, 0);
@@ -1119,10 +1176,11 @@ void pg_granular_sampler_rng_state(const uint64_t given[4], uint32_t slot, uint3
   out[3] = (out[3] & ~0xFFull) | (index & 0xFFull);
   if ((out[0] | out[1] | out[2] | out[3]) == 0) out[0] = 1;
 }
-int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt) {
+// pg_graph_add_granular_sampler and pg_graph_add_granular_sampler_to_main: `to_main` and `gen` as add_file_sampler's
+static int add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt, bool to_main, const pg_generator_options* gen) {
   pg_sampler_options def;
   if (!opt) { pg_sampler_options_default(&def); opt = &def; }
-  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, true, gopt); if (rc) return -rc; }
+  { const int rc = sampler_pool_check(g, mixer_id, buffer_id, opt, true, gopt, to_main, gen); if (rc) return -rc; }
   { const int rc = pg_graph_prepare_granular_buffer(g, buffer_id); if (rc) return -rc; }   // Sampler::create_granular_sample_buffer, shared by all slots
   drain_control_messages(g);
   if (graph_quiesce(g)) return -graph_fail(g, PG_ERR_DEVICE);
@@ -1183,20 +1241,30 @@ int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, cons
   }
   g->gran_n += (size_t)n;
   // the note layer's record; the PgSamplerRec of the same index stays inert (n_voices 0): the unit kernel's sampler_command leaves the commands alone
+  const int unit = to_main ? graph_new_sampler_unit(g, sampler_id) : -1;
+  if (to_main && unit < 0) { release(); return -graph_fail(g, PG_ERR_DEVICE); }
   std::unique_ptr<PgGSampler> gs(new PgGSampler);
   memset(gs.get(), 0, sizeof(PgGSampler));
-  note_rec_init(gs->note, g->mixers[mixer_id].unit_slot, voice0, n, opt);
+  note_rec_init(gs->note, to_main ? unit : g->mixers[mixer_id].unit_slot, voice0, n, opt);
   gs->grain0 = grain0; gs->index = sampler_id; gs->start_time = opt->start_time; gs->span_t0 = UINT64_MAX;
   if (opt->has_envelope) gs->env_params = ahdsr_build_params(opt->envelope, g->sample_rate);   // (every slot's envelope: Idle until its first note_on)
   std::unique_ptr<PgSamplerRec> inert(new PgSamplerRec);
   memset(inert.get(), 0, sizeof(PgSamplerRec));
   inert->unit = -1;
+  // (the output stage of a sampler on the main mixer stands in THIS record for both kinds of pool: the unit kernel finds it by the sampler's index)
+  if (to_main) { pg_generator_options go; if (gen) go = *gen; else pg_generator_options_default(&go); genout_init(g, inert->out, go.volume, go.panning); }
   if (pg_memcpy(g->d_gsamp + sampler_id, gs.get(), sizeof(PgGSampler), hipMemcpyHostToDevice) != hipSuccess ||
       pg_memcpy((PgSamplerRec*)(g->d_samp + 1) + sampler_id, inert.get(), sizeof(PgSamplerRec), hipMemcpyHostToDevice) != hipSuccess ||
       samp_head_upload(g, (size_t)sampler_id + 1) != hipSuccess || graph_env_head_refresh(g)) return fail_upload();
   HostSampler hs;
   hs.granular = true; hs.with_mod = gopt->modulation != nullptr; hs.grain0 = grain0;
-  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, hs, SAMPLER_TAB_GRANULAR | (gopt->modulation ? SAMPLER_TAB_MATRIX : 0), &stages);
+  return sampler_pool_register(g, mixer_id, buffer_id, opt, vo, voice0, hs, SAMPLER_TAB_GRANULAR | (gopt->modulation ? SAMPLER_TAB_MATRIX : 0), &stages, unit);
+}
+int pg_graph_add_granular_sampler(pg_graph* g, int mixer_id, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt) {
+  return add_granular_sampler(g, mixer_id, buffer_id, opt, gopt, false, nullptr);
+}
+int pg_graph_add_granular_sampler_to_main(pg_graph* g, int buffer_id, const pg_sampler_options* opt, const pg_granular_sampler_options* gopt, const pg_generator_options* gen) {
+  return add_granular_sampler(g, PG_MAIN_MIXER, buffer_id, opt, gopt, true, gen);
 }
 int pg_graph_sampler_set_granular_parameter(pg_graph* g, int sampler_id, uint32_t fourcc, float value, int is_normalized, uint64_t sample_time) {
   const int pi = find_granular_param(fourcc);

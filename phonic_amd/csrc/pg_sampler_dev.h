@@ -82,15 +82,85 @@ DEVO void sampler_command(const PgLaunch& L, const PgCmd& cmd, uint64_t now) {
 }
 
 // Behind the source stage of a segment that ends a chunk of unit `u`: the end of a Sampler::write (note_end_of_write) for the unit's samplers
-// that were told to stop. Lane 0 of the workgroup.
-DEVO void sampler_end_of_write(const PgLaunch& L, int u) {
+// that were told to stop — a sub-mixer's (`only` < 0: every record of the table that names the unit) or the one sampler `only` whose pool a source
+// unit of the main mixer holds. Lane 0 of the workgroup.
+DEVO void sampler_end_of_write(const PgLaunch& L, int u, int only = -1) {
   if (!L.voices || !L.env || !L.env->samplers) return;
   PgSamplerTab* const tab = L.env->samplers;
-  for (uint32_t k = 0; k < tab->n; ++k) {
+  const uint32_t k0 = only < 0 ? 0u : (uint32_t)only, k1 = only < 0 ? tab->n : ((uint32_t)only < tab->n ? (uint32_t)only + 1u : 0u);
+  for (uint32_t k = k0; k < k1; ++k) {
     PgSamplerRec& r = ((PgSamplerRec*)(tab + 1))[k];
     if (r.unit != u || !r.stopping || r.stopped || !sampler_pool_ok(L, r)) continue;
     note_end_of_write(FilePool{L, r}, tab->stopped + k);
   }
+}
+
+// ---- the generator's output stage of a main-mixer sampler: AmplifiedSource(options.volume) -> PannedSource(options.panning) over the Sampler's
+// sum (player.rs:1048-1133; amplified.rs:93-104, panned.rs:93-104; apply_smoothed_gain / _panning, smoothing.rs:59-125). The smoothers and the pan law
+// are the voices' own (pg_dsp_dev.h: sm_set_target, sm_need_ramp, sm_sequence, panning_factors); here: what a Sampler::write decides once, and the
+// walk over a piece of its buffer. ----
+// The record of sampler `index` if it is a source of the main mixer
+DEVO PgGenOut* genout_rec(const PgLaunch& L, int index) {
+  PgSamplerRec* const rp = sampler_rec(L, index);
+  return (rp != nullptr && rp->out.on) ? &rp->out : nullptr;
+}
+// A SetSourceVolume / SetSourcePanning event in front of its frame: the wrapper's process_messages at the top of its write, whatever the Sampler
+// then returns (amplified.rs:64-73). One lane.
+DEVO void genout_command(const PgLaunch& L, const PgCmd& cmd) {
+  PgGenOut* const o = genout_rec(L, cmd.target);
+  if (o == nullptr) return;
+  PgSmooth s = cmd.type == CMD_SAMPLER_OUT_VOLUME ? o->volume : o->panning;
+  sm_set_target(s, cmd.value);
+  if (cmd.type == CMD_SAMPLER_OUT_VOLUME) o->volume = s; else o->panning = s;
+}
+// The top of a Sampler::write, the messages of its first frame applied: does it return its buffer (sampler.rs:974-981: not stopped, and a slot is
+// active or the sampler is stopping), and do the two smoothers ramp over it — need_ramp() is asked ONCE per write (smoothing.rs:60, :80), and a
+// write of the main mixer's chunk is rendered as several pieces. Called by all 64 lanes of wave 0 in front of the source stage of the chunk's
+// first piece: the pieces behind it, and every lane of this one behind a barrier, read the decision from the record.
+// A file pool: one lane per slot asks its voice. A granular pool: pg_gsampler_kernel left the answer at the boundary that opened the write.
+DEVO void genout_begin_write(const PgLaunch& L, int index) {
+  PgSamplerRec* const rp = sampler_rec(L, index);
+  if (rp == nullptr || !rp->out.on) return;
+  const int lane = (int)(threadIdx.x & 63);
+  int delivers = 0;
+  if (sampler_pool_ok(L, *rp)) {
+    const bool active = lane < rp->n_voices && sampler_slot_active(L.voices[rp->voice0 + lane]);
+    delivers = (!rp->stopped && (__ballot(active) != 0ull || rp->stopping)) ? 1 : 0;
+  } else if (rp->n_voices == 0 && rp->unit == -1 && L.env->samplers->gsamp != nullptr) delivers = L.env->samplers->gsamp[index].delivers != 0 ? 1 : 0;   // (a granular sampler's inert record: its own record of that index exists)
+  if (lane == 0)
+    rp->out.flags = !delivers ? 0 : (PG_GENOUT_DELIVERS | (sm_need_ramp(rp->out.volume) ? PG_GENOUT_VOLUME_RAMPS : 0) | (sm_need_ramp(rp->out.panning) ? PG_GENOUT_PAN_RAMPS : 0));
+}
+// `frames` stereo frames of the write's buffer at `buf` (LDS), by every lane of the workgroup; `seq`: room for 2 * frames floats (LDS). Which branch
+// runs was decided by genout_begin_write, in front of at least one barrier: no lane reads a smoother here that lane 0 rewrites in the same branch
+// (ADVICE.md on voice_write: a wave that evaluates need_ramp behind lane 0's store takes the other branch and misses the barriers).
+// While a smoother ramps one lane lays out its value sequence and all lanes apply it, like voice_write; behind the ramp's end sm_sequence hands
+// out the target, which is what next() returns to the reference's loop for the rest of the write.
+DEVO void genout_apply(PgGenOut& o, float* buf, int frames, float* seq) {
+  const int tid = pg_tid(), nt = blockDim.x, written = 2 * frames;
+  const int flags = o.flags;
+  if (!(flags & PG_GENOUT_DELIVERS)) return;   // the smoothers stand still over a write that returned 0
+  if (flags & PG_GENOUT_VOLUME_RAMPS) {   // one next() per interleaved sample
+    if (tid == 0) { PgSmooth s = o.volume; sm_sequence(s, seq, written); o.volume = s; }
+    __syncthreads();
+    for (int i = tid; i < written; i += nt) buf[i] *= seq[i];
+  } else {
+    const float gain = o.volume.target;
+    if (fabsf(1.0f - gain) > 0.000001f) for (int i = tid; i < written; i += nt) buf[i] = buf[i] * gain;
+  }
+  __syncthreads();
+  if (flags & PG_GENOUT_PAN_RAMPS) {   // one next() per frame
+    if (tid == 0) { PgSmooth s = o.panning; sm_sequence(s, seq, frames); o.panning = s; }
+    __syncthreads();
+    for (int f = tid; f < frames; f += nt) { float l, r; panning_factors(seq[f], l, r); buf[2 * f] *= l; buf[2 * f + 1] *= r; }
+  } else {
+    const float pan = o.panning.target;
+    if (fabsf(pan) > 0.000001f) {
+      float l, r;
+      panning_factors(pan, l, r);
+      for (int i = tid; i < written; i += nt) buf[i] *= (i & 1) ? r : l;
+    }
+  }
+  __syncthreads();
 }
 
 }  // namespace pgd

@@ -561,6 +561,7 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         else if (cmd.type == CMD_VOICE_STOP) { L.voices[cmd.target].has_stop = 1; L.voices[cmd.target].stop_time = cmd.value64; }
         else if (cmd.type == CMD_VOICE_SPEED) voice_set_speed(&L.voices[cmd.target], __longlong_as_double((long long)cmd.value64), cmd.value);
         else if (cmd.type == CMD_VOICE_SEEK) voice_seek(&L.voices[cmd.target], __longlong_as_double((long long)cmd.value64));
+        else if (pg_cmd_is_sampler_output(cmd.type)) genout_command(L, cmd);   // a main-mixer sampler's SetSourceVolume / SetSourcePanning
         else if (cmd.type == CMD_VOICE_RELEASE) {  // SamplerVoice::stop (voice.rs:196-212): the envelope's release, or a plain stop without one
           PgEnv* const e = (L.voices && L.env && (uint64_t)cmd.target < L.env->cap) ? (PgEnv*)(L.env + 1) + cmd.target : nullptr;   // (PgEnvTable::cap: entries the table holds)
           if (e && e->on) { PgEnvState st = e->state; ahdsr_note_off(st, e->params); e->state = st; }
@@ -612,6 +613,9 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         call_end_pos = call_end_mark;
         if (!FAST_ONLY) for (int cj = ci; cj < L.n_cmds && L.cmds[cj].unit == u; ++cj) if (L.cmds[cj].type == CMD_CALL_SPLIT && (int)L.cmds[cj].frame > frame0 && (int)L.cmds[cj].frame < N) { call_end_pos = pos0 + (uint64_t)L.cmds[cj].frame; break; }
       }
+      // (a source unit that holds a sampler's whole pool: what its Sampler::write decides at its top, the messages of the chunk's first frame applied)
+      const int own_sampler = (!FAST_ONLY && PG_UL(kind) == UNIT_SOURCE) ? PG_UL(sampler) - 1 : -1;
+      if (!FAST_ONLY && own_sampler >= 0 && seg_first) { __syncthreads(); if (tid < 64) genout_begin_write(L, own_sampler); __syncthreads(); }
       int later = 0;
       for (int vi = 0; vi < PG_UL(n_voices); ++vi) {
         PgVoice* gv = &L.voices[vi == 0 ? PG_UL(voice0) : L.voice_index[PG_UL(voice_off) + vi]];
@@ -637,7 +641,20 @@ __device__ __forceinline__ void pg_unit_body(const PgLaunch& L, const int slot, 
         later |= r & 2;
       }
       // (samplers of this mixer: the end of a Sampler::write — a stopping sampler without an active slot is stopped, sampler.rs:1011-1024)
-      if (!FAST_ONLY && seg_last && tid == 0 && PG_UL(kind) == UNIT_SUBMIXER) sampler_end_of_write(L, u);
+      if (!FAST_ONLY && seg_last && tid == 0 && (PG_UL(kind) == UNIT_SUBMIXER || own_sampler >= 0)) sampler_end_of_write(L, u, own_sampler);
+      if (!FAST_ONLY && own_sampler >= 0) {
+        // The generator's output stage over the pool's sum, and the unit's result: `produced_output` of the mixer is `written > 0` of the one
+        // source the sampler is (mixed.rs:585-610), and Sampler::write returns all or nothing (sampler.rs:974-981). For a file pool that is the
+        // rule, not the OR over its voices: the two agree while a slot that is active at the top of the write also writes frames in it — they
+        // part in the one write a stopping sampler finds no voice left in, and where an active slot's source has nothing left to give. A granular
+        // pool keeps the OR (DESIGN.md "Samplers on the main mixer": a living granular sampler counts as having delivered).
+        __syncthreads();
+        PgSamplerRec* const srec = sampler_rec(L, own_sampler);
+        if (srec != nullptr && srec->out.on) {
+          if (srec->n_voices > 0) audible_input = (srec->out.flags & PG_GENOUT_DELIVERS) != 0;   // (a granular sampler's record is inert for its notes: n_voices 0)
+          genout_apply(srec->out, sseg, seg, tmp);
+        }
+      }
       if (PG_UL(kind) == UNIT_SOURCE) {  // (no chain: the unit's result is whether its source produced output anywhere in the chunk)
         if (audible_input && tid == 0) { unit.chunk_any_audible = 1; PG_UL(chunk_any_audible) = 1; }
       } else {

@@ -140,6 +140,35 @@ class Graph(GraphHandle):
         has = loop_range is not None
         self._check(self._lib.pg_graph_sampler_set_loop_range(self._h, sampler, 1 if has else 0, int(loop_range[0]) if has else 0, int(loop_range[1]) if has else 0, sample_time))
 
+    # -- samplers on the main mixer: Player::play_generator / add_generator without a target mixer, with the generator's volume and panning ----
+    def add_sampler_to_main(self, buffer_id, volume=None, panning=None, options=None, **kw):
+        """A file sampler as ONE source of the main mixer behind AmplifiedSource(volume) -> PannedSource(panning) (GeneratorPlaybackOptions;
+        defaults 1.0 / 0.0). `options` / keywords as for add_sampler. Every sampler_* call works on the returned id."""
+        o = options if options is not None else _capi.sampler_options(**kw)
+        gen = _capi.generator_options(volume, panning)
+        return self._id(self._lib.pg_graph_add_sampler_to_main(self._h, buffer_id, C.byref(o), C.byref(gen)))
+
+    def add_granular_sampler_to_main(self, buffer_id, params=None, modulation=None, rng_states=None, volume=None, panning=None, options=None, **kw):
+        """A granular-mode sampler on the main mixer: add_granular_sampler's arguments, add_sampler_to_main's placement and output stage."""
+        o = options if options is not None else _capi.sampler_options(**kw)
+        go = _capi.granular_sampler_options(params if params is not None else _capi.granular_params(), modulation, rng_states)
+        gen = _capi.generator_options(volume, panning)
+        return self._id(self._lib.pg_graph_add_granular_sampler_to_main(self._h, buffer_id, C.byref(o), C.byref(go), C.byref(gen)))
+
+    def sampler_set_volume(self, sampler, volume, sample_time=0):
+        """GeneratorPlaybackHandle::set_volume of a sampler on the main mixer (PG_ERR_STATE for one in a sub-mixer)."""
+        self._check(self._lib.pg_graph_sampler_set_volume(self._h, sampler, float(volume), sample_time))
+
+    def sampler_set_panning(self, sampler, panning, sample_time=0):
+        """GeneratorPlaybackHandle::set_panning of a sampler on the main mixer (PG_ERR_STATE for one in a sub-mixer)."""
+        self._check(self._lib.pg_graph_sampler_set_panning(self._h, sampler, float(panning), sample_time))
+
+    def sampler_output_state(self, sampler):
+        """The two smoothers of a main-mixer sampler's output stage (_capi.sampler_output_state_dict). Debug read-back: waits for the graph's work."""
+        st = _capi.SamplerOutputState()
+        self._check(self._lib.pg_graph_sampler_output_state(self._h, sampler, C.byref(st)))
+        return _capi.sampler_output_state_dict(st)
+
     def sampler_state(self, sampler):
         """The slot table and the sampler's own state as a dict (debug read-back: waits for the graph's work)."""
         st = _capi.SamplerState()
